@@ -2,6 +2,14 @@
 """Benchmark of the batched PCGRL hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C2|C3|C3d|C4|C5|C5b|M1|D1|S1|C2w|C3w] [--envs E]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line (value, ms_per_step and the HBM roofline of those steps).
+Everything else the line can carry -- the per-kernel event pass, the steady state, pcgrl_rollout, the search and asynchronous
+figures, the CPU baseline, the legs of the other configs -- is measured only with --full.
+
+--dump-outputs DIR writes what the last timed step returned (observation arrays, reward, done, info table) as DIR/<name>.npy in
+float32 / float64, at most 64 MB in all: beyond that a fixed seeded sample of environments (DIR/env_index.npy holds their indices).
 
 With --gpus N > 1 and no RANK in the environment the script launches itself under torch.distributed.run with one rank per
 GPU (127.0.0.1 rendezvous, RCCL barrier, max-over-ranks time) and prints the one JSON line of rank 0 with n_gpus = N; it
@@ -17,10 +25,11 @@ Extra objects on the JSON line:
   roofline      HBM roofline of the step pipeline: achieved = E * B_alg / (GPU time of the step's
                 kernels, from HIP events recorded around every launch on the launch stream, over
                 the same timed steps), B_alg = 2*H*W + 64 bytes per env-step.
-  configs       (default workload, one GPU) short driver-timed legs of the other BASELINE.json configs (C3, C4, C5), of smb
+                (--full adds the dominant kernel and the per-phase times of a second, event-timed pass.)
+  configs       (--full, default workload, one GPU) short driver-timed legs of the other BASELINE.json configs (C3, C4, C5), of smb
                 (S1) and of the trainer-shaped wrapped steps (C2w, C3w): first window + steady state, roofline fraction,
                 dominant kernel -- so that every config has a number under the same clock as `value`.
-  cpu_baseline  the CPU oracle (oracle/pcgrl_oracle.c, a bit-exact port of the reference) timed on
+  cpu_baseline  (--full) the CPU oracle (oracle/pcgrl_oracle.c, a bit-exact port of the reference) timed on
                 this box's host cores on a bounded sample of the same workload (rank 0, N=1 only).
 """
 import argparse
@@ -57,8 +66,8 @@ WORKLOADS = {
     "C3w": ("zelda", "wide", (dict(width=11, height=16),), 65536, "zelda-wide-v0 11x16 behind ActionMapImagePCGRLWrapper: flat actions, step + one-hot [N,16,11,8] image, 65536 envs/GPU"),
 }
 WRAPPED = {"C2w": ("cropped", 28), "C3w": ("actionmap", None)}
-# legs of the default run besides the headline workload: every BASELINE.json config (and smb, and the wrapped steps) gets a
-# driver-timed figure.  (steps, warmup, steady warm-up) are sized so that the whole default run stays well under a minute of GPU time.
+# legs of the --full run besides the headline workload: every BASELINE.json config (and smb, and the wrapped steps) gets a
+# driver-timed figure.  (steps, warmup, steady warm-up) are sized so that the whole --full run stays well under a minute of GPU time.
 LEGS = {"C3": (20, 5, 800), "C4": (10, 3, 40), "C5": (20, 5, 800), "S1": (5, 2, 45), "C2w": (20, 5, 800), "C3w": (20, 5, 800),
         "B1": (50, 10, 7000)}       # (B1: an episode is ~6 000 steps long -- max_changes 2 000, a third of the random actions change a tile)
 # asynchronous ticks of the search problems (pcgrl_step_async): (workload, ticks, warm-up ticks, pop budget per search and tick)
@@ -441,6 +450,32 @@ def make_actions(torch, rep, steps, n, W, H, nt, device, seed, flat=False):
                         torch.randint(0, nt, (steps, n), generator=g, device=device, dtype=torch.int32)], -1).contiguous()
 
 
+DUMP_BYTES = 60 << 20    # --dump-outputs: under 64 MB on disk with the .npy headers (split evenly over the ranks)
+
+
+def dump_outputs(torch, out_dir, last, n, rank, world):
+    """--dump-outputs: what the last timed step returned -- (obs, reward, done, info), obs a dict of tensors or the wrapper's image --
+    as <out_dir>/<name>.npy (float32; float64 for reward and the int32 info table).  Over the byte budget, the rows of a fixed seeded
+    sample of environments (the same for every array, env_index.npy).  Under N > 1 every rank writes its own shard (<name>.rank<r>.npy)."""
+    import numpy as np
+    obs, reward, done, info = last[:4]
+    arrays = [("obs_" + k, v) for k, v in obs.items()] if isinstance(obs, dict) else [("obs", obs)]
+    arrays += [("reward", reward), ("done", done), ("info", info.table)]
+    wide = (torch.float64, torch.int32, torch.int64)
+    as_dtype = lambda t: torch.float64 if t.dtype in wide else torch.float32
+    per_env = sum(t[0].numel() * (8 if as_dtype(t) == torch.float64 else 4) for _, t in arrays)
+    budget = DUMP_BYTES // world
+    idx = None
+    if n * per_env > budget:
+        idx = np.sort(np.random.RandomState(0).choice(n, budget // per_env, replace=False))
+        sel = torch.as_tensor(idx, device=reward.device)
+        arrays = [(k, t.index_select(0, sel)) for k, t in arrays] + [("env_index", torch.as_tensor(idx + rank * n, dtype=torch.float64))]
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = ".rank%d" % rank if world > 1 else ""
+    for name, t in arrays:
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), t.to(as_dtype(t)).cpu().numpy())
+
+
 def measured_traffic(workload):
     """-> (bytes per step, file, hash of the kernel sources the passes ran on).  HBM bytes per step from the last committed rocprofv3 PMC passes (profiles/*/<W>_traffic.json: FETCH_SIZE and
     WRITE_SIZE summed over the step's kernels), corrected as calibrated on this GPU with tools/traffic_calib.hip
@@ -616,11 +651,14 @@ def main():
     ap.add_argument("--no-rollout", action="store_true", help="skip the secondary pcgrl_rollout measurement")
     ap.add_argument("--dry-run", action="store_true", help="process plumbing only (launcher, rendezvous, barrier, max-over-ranks reduction over gloo); "
                                                           "no GPU, no environment: the line carries value null and dry_run true")
-    ap.add_argument("--no-legs", action="store_true", help="skip the short legs of the other configs (the `configs` object of the default line)")
-    ap.add_argument("--legs", default="C3,C4,C4_async,M1_async,C5,S1,B1,C2w,C3w,C2_sub2,C3_sub2,n1_facade,collector,node_driver", help="which legs the default line carries")
+    ap.add_argument("--no-legs", action="store_true", help="skip the short legs of the other configs (the `configs` object of the --full line)")
+    ap.add_argument("--legs", default="C3,C4,C4_async,M1_async,C5,S1,B1,C2w,C3w,C2_sub2,C3_sub2,n1_facade,collector,node_driver", help="which legs the --full line carries")
     ap.add_argument("--tuning", default="", help="developer switches of the library for A/B runs: field=value[,field=value...] "
                                                  "(include/pcgrl_hip.h pcgrl_tuning, e.g. no_fused=1,step_epb=128)")
     ap.add_argument("--steady-warmup", type=int, default=800, help="steps before the steady_state measurement (0: skip it)")
+    ap.add_argument("--full", action="store_true", help="also measure what is not the headline: per-kernel event pass, steady state, pcgrl_rollout, "
+                                                        "search / async figures, CPU baseline, the legs of the other configs (N > 1: configs.C5)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned as DIR/<name>.npy (float32 / float64, <= 64 MB)")
     a = ap.parse_args()
     if a.gpus < 1:
         ap.error("--gpus must be at least 1")
@@ -662,7 +700,7 @@ def main():
         if rank == 0:
             line = {"metric": "env-steps/sec (whole node)", "value": None, "unit": "env-steps/s", "n_gpus": world, "steps": a.steps,
                     "warmup": a.warmup, "dry_run": True, "max_over_ranks_s": float(tt[0]), "scaling": "weak"}
-            if world > 1:      # the shape of the N > 1 line: BASELINE config 5 is timed on every rank as well (tall_maps_leg)
+            if world > 1 and a.full:      # the shape of the N > 1 --full line: BASELINE config 5 is timed on every rank as well (tall_maps_leg)
                 line["configs"] = {TALL: {"workload": WORKLOADS[TALL][4], "envs_per_gpu": WORKLOADS[TALL][3], "n_gpus": world, "value": None,
                                           "unit": "env-steps/s (whole job, max-over-ranks time)", "dry_run": True}}
             print(json.dumps(line))
@@ -707,7 +745,7 @@ def main():
     t0 = time.perf_counter()
     ev0.record()                # torch's current stream IS the stream the kernels are launched on
     for t in range(a.warmup, a.warmup + a.steps):
-        step(acts[t])
+        last = step(acts[t])
     ev1.record()
     barrier()
     dt = time.perf_counter() - t0
@@ -716,14 +754,16 @@ def main():
         tt = torch.tensor([dt, gpu_ms_per_step], device="cpu" if same_gpu else device, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt, gpu_ms_per_step = float(tt[0].item()), float(tt[1].item())
+    if a.dump_outputs:        # (before --full steps the batch on: the returned tensors are views of the live state)
+        dump_outputs(torch, a.dump_outputs, last, n, rank, world)
     # N > 1: BASELINE config 5 (north_star: 8 192 tall-map environments per GPU, the 8-GPU configuration) on every rank as well
     tall = None
-    if world > 1 and a.workload == "C2" and n == n_default and not a.no_legs:
+    if a.full and world > 1 and a.workload == "C2" and n == n_default and not a.no_legs:
         tall = tall_maps_leg(torch, dist, device, rank, world, use_dist, same_gpu)
     # informational per-kernel breakdown: a second pass with HIP events around every launch
     # (each event record costs a few us on the stream, so it is kept out of the timed region)
     phase_ms, prof_steps = {}, 0
-    if rank == 0:
+    if rank == 0 and a.full:
         env.profile(True)
         for t in range(a.warmup, a.warmup + min(a.steps, 50)):
             step(acts[t])
@@ -733,7 +773,7 @@ def main():
     # steady state: the driver's short window right after a reset sees almost no episode end and every map at 50 % density.
     # The same K steps again once the batch has run for >= --steady-warmup steps (tape rows reused cyclically).
     steady = None
-    if rank == 0 and a.steady_warmup > 0:
+    if rank == 0 and a.full and a.steady_warmup > 0:
         L = acts.shape[0]
         t_now = a.warmup + a.steps + prof_steps
         for t in range(t_now, max(t_now, a.steady_warmup)):
@@ -757,7 +797,7 @@ def main():
     # secondary figure: the same K steps as ONE pcgrl_rollout call on the action tape (a single launch where the fused
     # step kernel applies; per-step reward / done / info still written for every step).  Not the headline `value`.
     rollout = None
-    if rank == 0 and not a.no_rollout and not wrapped:
+    if rank == 0 and a.full and not a.no_rollout and not wrapped:
         # a second batch brought to the same state as the first one had when its timed loop started: same seeds, same
         # warm-up actions -- the tape below is then exactly the work of the timed loop above
         env2 = BatchedPcgrlEnv(prob=prob, rep=rep, num_envs=n, device=device, seed=rank * n)
@@ -781,30 +821,31 @@ def main():
                    "what": "pcgrl_rollout on the same action tape: K steps in one call, per-step reward/done/info kept"}
 
     if rank == 0:
-        # dominant kernel (k_stats; for sokoban the solver): its share of the step from the event pass -- the idle
-        # intervals of that pass measure the cost of an event pair, which is subtracted -- and, from the committed
-        # SQ counters, how close it runs to the VALU issue limit (measured: one wave64 VALU instruction per SIMD per 2.45 cycles)
-        ph = {k: 1e3 * v / max(prof_steps, 1) for k, v in phase_ms.items()}
-        ev_us = min(ph.values()) if ph else 0.0
-        # binary maps of <= 16 rows run the whole step as ONE launch (k_step): the "stats" interval is then empty and
-        # the kernel's duration is the step time of the timed region itself
         solver = prob in ("sokoban", "mdungeon", "ddave", "smb")     # problems with a search kernel after k_stats
-        fused = not solver and ph.get("update", 0.0) > 4 * max(ph.get("stats", 0.0), 1e-3)
-        dom_name = "k_sokoban" if prob == "sokoban" else "k_mdungeon" if prob == "mdungeon" else "k_ddave" if prob == "ddave" else "k_smb" if prob == "smb" else "k_step" if fused else (
-            "k_stats_wide" if (prob == "binary" and H > 16) else "k_stats")
-        dom_us = max((ph.get("solver_or_reset", 0.0) if solver else ph.get("stats", 0.0)) - ev_us, 0.0)
-        if fused:
-            dom_us = gpu_ms_per_step * 1e3
-        elif not solver:          # the event pass perturbs short steps: never more than the step minus the other kernel
-            dom_us = min(dom_us, max(gpu_ms_per_step * 1e3 - max(ph.get("update", 0.0) - ev_us, 0.0), 0.0))
         head = tree_hash()
-        valu, valu_src, valu_head = measured_valu(a.workload, "k_step" if fused else "k_stats") if n == n_default else (None, None, None)
-        dominant = {"name": dom_name, "avg_us": dom_us, "event_pair_overhead_us": ev_us}
-        if valu and dom_us > 0 and not solver:
-            peak = VALU_ISSUE_PEAK              # measured on this GPU: profiles/r3a_round3/valu_calibration.md (tools/valu_calib.hip)
-            dominant.update({"valu_wave_instr_per_launch": valu, "valu_source": valu_src, "valu_head": valu_head, "valu_stale": valu_head != head,
-                             "valu_issue_rate": valu / (dom_us * 1e-6), "valu_issue_peak": peak,
-                             "valu_issue_frac": valu / (dom_us * 1e-6) / peak})
+        if a.full:
+            # dominant kernel (k_stats; for sokoban the solver): its share of the step from the event pass -- the idle
+            # intervals of that pass measure the cost of an event pair, which is subtracted -- and, from the committed
+            # SQ counters, how close it runs to the VALU issue limit (measured: one wave64 VALU instruction per SIMD per 2.45 cycles)
+            ph = {k: 1e3 * v / max(prof_steps, 1) for k, v in phase_ms.items()}
+            ev_us = min(ph.values()) if ph else 0.0
+            # binary maps of <= 16 rows run the whole step as ONE launch (k_step): the "stats" interval is then empty and
+            # the kernel's duration is the step time of the timed region itself
+            fused = not solver and ph.get("update", 0.0) > 4 * max(ph.get("stats", 0.0), 1e-3)
+            dom_name = "k_sokoban" if prob == "sokoban" else "k_mdungeon" if prob == "mdungeon" else "k_ddave" if prob == "ddave" else "k_smb" if prob == "smb" else "k_step" if fused else (
+                "k_stats_wide" if (prob == "binary" and H > 16) else "k_stats")
+            dom_us = max((ph.get("solver_or_reset", 0.0) if solver else ph.get("stats", 0.0)) - ev_us, 0.0)
+            if fused:
+                dom_us = gpu_ms_per_step * 1e3
+            elif not solver:          # the event pass perturbs short steps: never more than the step minus the other kernel
+                dom_us = min(dom_us, max(gpu_ms_per_step * 1e3 - max(ph.get("update", 0.0) - ev_us, 0.0), 0.0))
+            valu, valu_src, valu_head = measured_valu(a.workload, "k_step" if fused else "k_stats") if n == n_default else (None, None, None)
+            dominant = {"name": dom_name, "avg_us": dom_us, "event_pair_overhead_us": ev_us}
+            if valu and dom_us > 0 and not solver:
+                peak = VALU_ISSUE_PEAK              # measured on this GPU: profiles/r3a_round3/valu_calibration.md (tools/valu_calib.hip)
+                dominant.update({"valu_wave_instr_per_launch": valu, "valu_source": valu_src, "valu_head": valu_head, "valu_stale": valu_head != head,
+                                 "valu_issue_rate": valu / (dom_us * 1e-6), "valu_issue_peak": peak,
+                                 "valu_issue_frac": valu / (dom_us * 1e-6) / peak})
         total_steps = float(n) * world * a.steps
         value = total_steps / dt
         b_alg = 2 * H * W + 64
@@ -826,25 +867,26 @@ def main():
                          "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic, "traffic_source": traffic_src,
                          "traffic_head": traffic_head, "tree_head": head, "traffic_stale": (traffic is not None and traffic_head != head),
                          "algorithmic_bytes_per_launch": n * b_alg,
-                         "kernel": ("one step = one launch of k_step (state of 64 / 128 / 256 environments per block staged in LDS: update + stats + resets)" if fused else
-                                    "one step = k_update + k_stats (resets inside k_stats); the search problems add k_reset + their search kernel"),
-                         "dominant_kernel": dominant,
-                         "algorithmic_bytes_per_env_step": b_alg, "gpu_ms_per_step": gpu_ms_per_step,
-                         "phase_us_per_step_with_event_overhead": ph},
+                         "algorithmic_bytes_per_env_step": b_alg, "gpu_ms_per_step": gpu_ms_per_step},
         }
+        if a.full:
+            out["roofline"].update({
+                "kernel": ("one step = one launch of k_step (state of 64 / 128 / 256 environments per block staged in LDS: update + stats + resets)" if fused else
+                           "one step = k_update + k_stats (resets inside k_stats); the search problems add k_reset + their search kernel"),
+                "dominant_kernel": dominant, "phase_us_per_step_with_event_overhead": ph})
         if steady is not None:
             steady["roofline_frac"] = n * b_alg / (steady["gpu_ms_per_step"] * 1e-3) / 1e9 / HBM_PEAK_GBPS
             out["steady_state"] = steady
         if rollout is not None:
             out["rollout"] = rollout
-        if solver and prob != "smb" and not wrapped:
+        if a.full and solver and prob != "smb" and not wrapped:
             out["search"] = search_chain(torch, env, step, acts, 0)
             if n == n_default and (a.workload + "_async") in ASYNC_LEGS:
                 env.close()
                 out["async"] = async_leg(torch, device, *ASYNC_LEGS[a.workload + "_async"])
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(prob, rep, calls)
-        if world == 1 and not a.no_legs and a.workload == "C2" and n == n_default:
+        if a.full and world == 1 and not a.no_legs and a.workload == "C2" and n == n_default:
             # every other BASELINE.json config (and smb, and the wrapped steps) under the same clock: short legs, rank 0
             env.close()
             legs = {}

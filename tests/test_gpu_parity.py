@@ -1557,6 +1557,47 @@ def test_bench_self_launch_two_ranks():
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("workload,envs", [("C2", None), ("C3w", 4096)])
+def test_bench_plain_line_and_dump_outputs(workload, envs, tmp_path):
+    """A plain `bench.py` run times --steps steps and measures nothing else; --dump-outputs holds what its last timed step returned:
+    the same arrays as the batch stepped here with the bench's seeds and action tape (C2 at its full batch: a seeded sample of rows)."""
+    import json, subprocess, sys
+    torch = _torch()
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    steps, warmup = 5, 3
+    args = ["--gpus", "1", "--workload", workload, "--steps", str(steps), "--warmup", str(warmup), "--dump-outputs", str(tmp_path)]
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + args + (["--envs", str(envs)] if envs else []),
+                         capture_output=True, text=True, timeout=600)
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert out.returncode == 0 and len(lines) == 1, out.stderr[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == steps and d["ms_per_step"] > 0 and d["higher_is_better"] is True and d["dtype"] == "u8"
+    assert not {"configs", "cpu_baseline", "steady_state", "rollout", "search", "async"} & set(d)
+    assert "dominant_kernel" not in d["roofline"]
+    files = {f[:-4]: np.load(os.path.join(tmp_path, f)) for f in os.listdir(tmp_path)}
+    assert sum(os.path.getsize(os.path.join(tmp_path, f)) for f in os.listdir(tmp_path)) < 64e6
+    assert all(x.dtype in (np.float32, np.float64) for x in files.values())
+    n = envs or bench.WORKLOADS[workload][3]
+    device = torch.device("cuda", 0)
+    env, step, reset, _ = bench.make_stepper(torch, workload, n, device, 0)
+    reset()
+    acts = bench.make_actions(torch, bench.WORKLOADS[workload][1], steps + warmup, n, env._prob._width, env._prob._height, env.get_num_tiles(),
+                              device, 1234, flat=(workload == "C3w"))
+    for t in range(steps + warmup):
+        obs, rew, done, info = step(acts[t])[:4]
+    idx = files["env_index"].astype(np.int64) if "env_index" in files else np.arange(n)
+    assert ("env_index" in files) == (envs is None)
+    exp = {"reward": rew, "done": done, "info": info.table}
+    exp.update({"obs_" + k: v for k, v in obs.items()} if isinstance(obs, dict) else {"obs": obs})
+    assert set(files) - {"env_index"} == set(exp)
+    for k, v in exp.items():
+        assert np.array_equal(files[k], v.cpu().numpy()[idx].astype(files[k].dtype)), k
+    env.close()
+
+
+@pytest.mark.gpu
 def test_gym_make_and_vector_env_under_a_gym_module():
     """With a gym module present (the test shim; gym itself is not on the image): `gym.make('zelda-narrow-v0')` gives a
     gym.Env that a gym.Wrapper built the way the reference's wrappers are (wrappers.py:11,21-24: gym.make(game), find the
@@ -1827,7 +1868,7 @@ def test_bench_eight_ranks_tall_maps_on_one_gpu():
 
 @pytest.mark.gpu
 def test_bench_two_ranks_carry_the_tall_map_config_on_the_headline_line():
-    """under N > 1 the default line (C2 headline) also carries `configs.C5` -- BASELINE config 5, 8 192 tall-map
+    """under N > 1 the --full line (C2 headline) also carries `configs.C5` -- BASELINE config 5, 8 192 tall-map
     environments per rank, first window and steady state, max-over-ranks -- so that the day an 8-GPU node runs it the one line tells
     both stories.  Two ranks on cuda:0 over gloo here."""
     import json, subprocess, sys
@@ -1837,7 +1878,7 @@ def test_bench_two_ranks_carry_the_tall_map_config_on_the_headline_line():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--steady-warmup", "0", "--no-rollout",
-                          "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                          "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True, timeout=900)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert out.returncode == 0 and len(lines) == 1, out.stderr[-2000:]
     d = json.loads(lines[0])

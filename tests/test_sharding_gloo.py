@@ -109,15 +109,18 @@ def test_bench_gpus2_starts_its_own_ranks():
     """`python bench.py --gpus 2` without torch.distributed.run around it: the script launches two ranks itself, they meet
     over 127.0.0.1 (gloo here: --dry-run is the GPU-less skeleton of the measurement), and exactly one line with
     n_gpus == 2 comes out."""
-    rc, lines, err = _run_bench(["--gpus", "2", "--steps", "7", "--warmup", "2", "--dry-run"])
+    rc, lines, err = _run_bench(["--gpus", "2", "--steps", "7", "--warmup", "2", "--dry-run", "--full"])
     assert rc == 0 and len(lines) == 1, err[-2000:]
     d = lines[0]
     assert d["n_gpus"] == 2 and d["steps"] == 7 and d["warmup"] == 2 and d["dry_run"] is True and d["value"] is None
     assert d["max_over_ranks_s"] >= 0.02          # rank 1 sleeps 20 ms: the reduction is a max over the ranks
-    # the N > 1 line also carries BASELINE config 5 (north_star's 8-GPU configuration: 8 192 tall-map environments per GPU), timed on
+    # the N > 1 --full line also carries BASELINE config 5 (north_star's 8-GPU configuration: 8 192 tall-map environments per GPU), timed on
     # every rank between barriers (bench.py tall_maps_leg); the dry run shows its place on the line
     c5 = d["configs"]["C5"]
     assert c5["n_gpus"] == 2 and c5["envs_per_gpu"] == 8192 and "64x64" in c5["workload"] and c5["value"] is None
+    # a plain run measures the headline only: no other configuration on its line
+    rc, lines, err = _run_bench(["--gpus", "2", "--steps", "7", "--warmup", "2", "--dry-run"])
+    assert rc == 0 and len(lines) == 1 and lines[0]["n_gpus"] == 2 and "configs" not in lines[0], err[-2000:]
 
 
 def test_bench_refuses_to_report_fewer_gpus_than_asked():

@@ -15,5 +15,5 @@ else:
     subprocess.check_call([os.environ.get("HIPCC", "hipcc")] + _lib.HIPCC_FLAGS + sys.argv[1].split() + _lib.SOURCES + ["-o", so], stderr=subprocess.DEVNULL)
 _lib.SO = so
 import bench
-sys.argv = ["bench.py", "--workload", wl, "--no-legs", "--no-cpu-baseline", "--no-rollout"] + sys.argv[3:]
+sys.argv = ["bench.py", "--full", "--workload", wl, "--no-legs", "--no-cpu-baseline", "--no-rollout"] + sys.argv[3:]
 bench.main()

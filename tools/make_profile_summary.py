@@ -3,7 +3,7 @@
     python tools/make_profile_summary.py <name> C2 [C3 ...]"""
 import collections, csv, json, os, shutil, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-G = os.path.join(ROOT, "gpurun_out")
+G = os.path.join(ROOT, os.environ.get("PCGRL_PROFILE_OUT", "profile_out"))      # where tools/profile_gpu.sh wrote
 name, workloads = sys.argv[1], sys.argv[2:]
 dst = os.path.join(ROOT, "profiles", name)
 os.makedirs(dst, exist_ok=True)
@@ -14,14 +14,14 @@ def agg(path):
             d[r["Kernel_Name"].split("(")[0]][r["Counter_Name"]].append(float(r["Counter_Value"]))
     return d
 out = ["# %s (MI355X, rocprofv3)\n" % name,
-       "Commands: `tools/profile_gpu.sh <workload> trace sq mem` = `rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --workload W --steps 100 --no-cpu-baseline --no-rollout`,",
-       "then separate `--pmc` passes (SQ_* counters; FETCH_SIZE; WRITE_SIZE).  Bench lines: `bench_<W>.json`; the default line as the driver runs it: "
+       "Commands: `tools/profile_gpu.sh <workload> trace sq mem` = `rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --full --workload W --steps 100 --no-cpu-baseline --no-rollout --no-legs`,",
+       "then separate `--pmc` passes (SQ_* counters; FETCH_SIZE; WRITE_SIZE).  Bench lines (`bench.py --full`): `bench_<W>.json`; the default workload's --full line with every config as a leg: "
        "`bench_default.json` (+ `.time`); cycles per pop of the two wavefronts of a capped A* search: `sok_prof.txt`, `md_prof_duo.txt` (`tools/sok_prof.py 4000`, "
        "`tools/sok_prof.py 1000 mdungeon`); the image kernel's store stream: `obs_bench.txt`.\n"]
 for W in workloads:
     out.append("## %s\n" % W)
     if W.endswith("R"):
-        out.append("`bench.py --workload %s --steps 200` *with* its pcgrl_rollout leg: the two calls of `k_step<..., true>` / `k_step_solver` are the 20-step "
+        out.append("`bench.py --full --workload %s --steps 200` *with* its pcgrl_rollout leg: the two calls of `k_step<..., true>` / `k_step_solver` are the 20-step "
                    "warm-up tape and the timed 200-step tape (max us / 200 = the `rollout.ms_per_step` of the bench line).\n" % W[:-1])
     ks = os.path.join(G, "prof_" + W, W + "_kernel_stats.csv")
     if os.path.exists(ks):
