@@ -278,7 +278,7 @@ __global__ __launch_bounds__(EPB * 4) __attribute__((amdgpu_waves_per_eu(4, 8)))
             const int q = a / dim;
             t3[0] = q % W; t3[1] = q / W; t3[2] = a - q * dim;
         }
-        if (e < ne) u = update_env<REP, MaskT, true, true>(P, B, act_lds, e, &mid);      // the decision part: everything the task lists need
+        if (e < ne) u = update_env<REP, MaskT, true, true, true>(P, B, act_lds, e, &mid);      // the decision part: everything the task lists need
         TL(2);
         const bool first = u.rst || u.sure_done;               // reset-only, or certain to end: k_stats' "lone" items
         const bool packed_full = PROB == PCGRL_PROB_ZELDA && B.zelda_inc;

@@ -187,7 +187,7 @@ __global__ __launch_bounds__(SS_THREADS) void k_step_solver(PcgrlParams P, DevBu
         for (int sub = wv * 64; sub < ne; sub += SS_THREADS) {
             const int e = e0 + sub + lane64;
             UpdateOut u = {};
-            if (sub + lane64 < ne) u = update_env<REP, MaskT>(P, B, actions_t, e);
+            if (sub + lane64 < ne) u = update_env<REP, MaskT, false, false, true>(P, B, actions_t, e);     // (auto-reset handles only)
             const uint64_t mc = __ballot(u.chg), mr = __ballot(u.rst);
             const uint64_t below = (1ull << lane64) - 1ull;
             int bc = 0, br = 0;
@@ -219,7 +219,7 @@ __global__ __launch_bounds__(SS_THREADS) void k_step_solver(PcgrlParams P, DevBu
                 for (int i = wv; i < nr; i += SS_THREADS / 64) {
                     const int e = e0 + (int)s_lists.items[rst_list][i];
                     ResetRows rr;
-                    wave_reset_env<PROB>(P, B, e, gen_map, mt, (uint8_t*)nullptr, lane64, 0, lane64 < G ? lane64 : -1, &rr);
+                    wave_reset_env<PROB, true, true>(P, B, e, gen_map, mt, (uint8_t*)nullptr, lane64, 0, lane64 < G ? lane64 : -1, &rr);
                     MaskT b0, b1, b2;
                     reset_rows_to_planes<MaskT>(P, reinterpret_cast<MaskT*>(B.planes) + (size_t)e * P.nplanes * G, lane64 < G ? lane64 : -1, rr.m0, rr.m1, rr.m2, b0, b1, b2);
                     const MaskT valid = (lane64 < G) ? rowmask : (MaskT)0;

@@ -28,8 +28,9 @@ struct UpdateOut {
 // environments finished -- so that the block's task lists are complete before the narrow representation's cursor draws (the
 // longest piece of an update: up to eight tempered words and a rejection loop) and the heat-map increment are done; those follow
 // in update_env_cursor, behind the block's list barrier, while the other wavefronts already compute.  `mid` carries what they need.
+// AR_ONLY: the caller runs for auto-reset handles only (k_step, k_step_solver): 16-bit heat counters (heat_increment).
 struct UpdateMid { int x, y, hx, hy, cur; bool chg, dead; };
-template <int REP, class MaskT, bool FIFO = false, bool SPLIT = false>
+template <int REP, class MaskT, bool FIFO = false, bool SPLIT = false, bool AR_ONLY = false>
 __device__ __forceinline__ UpdateOut update_env(const PcgrlParams& P, const DevBufs& B, const int32_t* __restrict__ actions, int e, UpdateMid* mid = nullptr) {
     bool chg = false, rst = false, cheap = false, sure_done = false, touch_item = false;
     int bucket = 0, inc_item = 0, k_used = 0, cur0 = 0;
@@ -270,7 +271,7 @@ __device__ __forceinline__ UpdateOut update_env(const PcgrlParams& P, const DevB
             changes += 1;
             const bool dead_writes = FIFO && P.auto_reset && B.inline_reset && (changes >= P.max_changes || iter >= P.max_iterations);
             dead_heat = dead_writes;
-            if (!dead_writes && !(SPLIT && REP == PCGRL_REP_NARROW)) heat_increment(B, B.heat + ((size_t)e * H + hy) * W + hx);
+            if (!dead_writes && !(SPLIT && REP == PCGRL_REP_NARROW)) heat_increment<AR_ONLY>(B, ((size_t)e * H + hy) * W + hx);
         }
         reinterpret_cast<int2*>(B.counters)[e] = make_int2(iter, changes);
         if (bad) atomicOr(B.status, PCGRL_STATUS_BAD_ACTION);
@@ -366,7 +367,7 @@ __device__ __forceinline__ void update_env_cursor(const PcgrlParams& P, const De
         x += 1;
         if (x >= W) { x = 0; y += 1; if (y >= H) y = 0; }
     }
-    if (mid.chg && !mid.dead) heat_increment(B, B.heat + ((size_t)e * H + y) * W + x);
+    if (mid.chg && !mid.dead) heat_increment<true>(B, ((size_t)e * H + y) * W + x);      // (k_step: auto-reset handles only)
     reinterpret_cast<uchar2*>(B.pos)[e] = make_uchar2((unsigned char)x, (unsigned char)y);
 }
 
@@ -523,7 +524,7 @@ __global__ __launch_bounds__(PCGRL_BLOCK) void k_update_block(PcgrlParams P, Dev
         if (change > 0) {
             chg = true;
             changes += change;
-            heat_increment(B, B.heat + ((size_t)e * H + y) * W + x);
+            heat_increment(B, ((size_t)e * H + y) * W + x);
         }
         reinterpret_cast<int2*>(B.counters)[e] = make_int2(iter, changes);
         reinterpret_cast<uchar2*>(B.pos)[e] = make_uchar2((unsigned char)x, (unsigned char)y);

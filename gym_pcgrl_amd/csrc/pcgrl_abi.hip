@@ -192,7 +192,9 @@ static int validate_config(const pcgrl_config* c) {
         }
     }
     if (c->max_changes < 1 || c->max_iterations < 1) return PCGRL_EINVAL;
-    if (c->max_changes > 65535) return PCGRL_EINVAL;          // the heat map counts changes per cell in 16 bits (a cell's count <= the episode's changes)
+    // auto-reset: the heat map counts changes per cell in 16 bits (a cell's count <= the episode's changes <= max_changes).  Without
+    // it an episode goes on past done, a count is unbounded and takes 32 bits (pcgrl_query_layout)
+    if (c->auto_reset && c->max_changes > 65535) return PCGRL_EINVAL;
     if (solver_prob(c->prob)) {
         if (c->prob != PCGRL_SMB && (c->width + 2) * (c->height + 2) > PCGRL_MAX_LEVEL_CELLS) return PCGRL_EINVAL;
         if (c->solver_power < 1 || c->solver_power > (c->prob == PCGRL_SMB ? 16383 : PCGRL_MAX_SOLVER_POWER)) return PCGRL_EINVAL;
@@ -347,7 +349,7 @@ int pcgrl_query_layout(const pcgrl_config* c, pcgrl_layout* L) {
     const size_t n = (size_t)c->num_envs, cells = (size_t)c->width * c->height;
     memset(L, 0, sizeof(*L));
     L->group = P.group; L->mask_bytes = P.mask_bytes; L->nplanes = P.nplanes; L->nstats = num_stats(c->prob);
-    L->map = n * cells; L->old_map = n * cells; L->heatmap = n * cells * 2; L->pos = n * 2;
+    L->map = n * cells; L->old_map = n * cells; L->heatmap = n * cells * (c->auto_reset ? 2 : 4); L->pos = n * 2;
     L->planes = n * P.nplanes * P.group * P.mask_bytes;
     L->counters = n * 8; L->stats = n * 32; L->start_stats = n * 32; L->info = n * 40;
     L->reward = n * 8; L->done = n; L->tile_p = n * 16;
@@ -449,6 +451,7 @@ int pcgrl_bind(pcgrl_env* h, const pcgrl_buffers* b, void* stream) {
     DevBufs& B = h->B;
     B.map = (uint8_t*)b->map; B.old_map = (uint8_t*)b->old_map; B.heat = (uint16_t*)b->heatmap; B.pos = (uint8_t*)b->pos;
     B.heat_end = B.heat + (size_t)h->cfg.num_envs * h->cfg.width * h->cfg.height;
+    B.heat32 = h->cfg.auto_reset ? 0 : 1;
     B.ep_return = nullptr; B.ep_length = nullptr; B.last_return = nullptr; B.last_length = nullptr;
     B.local = nullptr;
     B.planes = b->planes; B.counters = (int32_t*)b->counters; B.stats = (int32_t*)b->stats;

@@ -115,7 +115,8 @@ struct ResetRows { uint64_t m0, m1, m2; };      // bit planes of the tile ids of
 // lanes with row < 0 or >= H get zeros.  `tiles` may be null when nobody needs the tile bytes in LDS.
 // PARTIAL (compile time): stage only the stretches of the ring a small map's reset reads (below).  Off in the fused step kernel: its
 // BASELINE shapes make 350-400 words -- all of the ring is read -- and the second path cost the kernel registers (C2 + 0.4 us a step).
-template <int PROB, bool PARTIAL = true>
+// AR_ONLY: the caller runs for auto-reset handles only (the fused step kernels): 16-bit heat counters, no flag read (heat_clear).
+template <int PROB, bool PARTIAL = true, bool AR_ONLY = false>
 __device__ __forceinline__ void wave_reset_env(const PcgrlParams& P, const DevBufs& B, int e, int gen_map, uint32_t* mt,
                                                uint8_t* tiles, int lane, int step_draws = 0, int row = -1, ResetRows* rows = nullptr, int pend = 0) {
     const int W = P.width, H = P.height, cells = W * H;
@@ -293,8 +294,7 @@ __device__ __forceinline__ void wave_reset_env(const PcgrlParams& P, const DevBu
             ring_g[i] = mt[i];
         }
     }
-    uint16_t* heat_g = B.heat + (size_t)e * cells;
-    for (int c = lane; c < cells; c += 64) heat_g[c] = 0;        // pcgrl_env.py:72
+    heat_clear<AR_ONLY>(B, e, cells, lane, 64);        // pcgrl_env.py:72
     if (lane == 0) {
         B.rng_cur[2 * e] = cur;
         reinterpret_cast<int2*>(B.counters)[e] = make_int2(0, 0);   // pcgrl_env.py:67-68
@@ -427,8 +427,7 @@ __device__ __forceinline__ MaskT block_reset_env(const PcgrlParams& P, const Dev
         if (tid == 0) B.fifo_tag[e] = cur;
     }
     for (int i = tid; i < PCGRL_MT_N; i += NTHREADS) ring_g[i] = mt[i];
-    uint16_t* heat_g = B.heat + (size_t)e * cells;
-    for (int c = tid; c < cells; c += NTHREADS) heat_g[c] = 0;        // pcgrl_env.py:72
+    heat_clear(B, e, cells, tid, NTHREADS);        // pcgrl_env.py:72
     if (tid == 0) {
         B.rng_cur[2 * e] = cur;
         reinterpret_cast<int2*>(B.counters)[e] = make_int2(0, 0);   // pcgrl_env.py:67-68

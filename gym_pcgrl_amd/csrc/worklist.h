@@ -133,6 +133,7 @@ struct DevBufs {
     // ... and the slots of the suspended searches, for the update kernel's side job: the threads of its first blocks list the
     // runnable slots (async_run[0 .. *async_run_n)) for the search kernel that follows
     const uint8_t* async_slots; size_t async_slot_bytes; int32_t async_nslots; int32_t* async_run; int32_t* async_run_n;
+    int32_t heat32;                  // no auto-reset: `heat` holds one 32-bit count per cell (pcgrl_query_layout), else 16-bit ones
 };
 #define PCGRL_FIFO_N 8
 
@@ -355,14 +356,29 @@ __device__ __forceinline__ void episode_account(const DevBufs& B, int e, double 
     B.ep_return[e] = R; B.ep_length[e] = L;
 }
 
-// heatmap[cell] += 1 (pcgrl_env.py:137) without waiting for the old value: a no-return 32-bit atomic add on the
-// word that holds the 16-bit counter (counts stay below 2^16, so a half never carries into the other).  Only the
-// very last counter of a buffer with an odd number of cells has no complete word; it takes the plain path.
-__device__ __forceinline__ void heat_increment(const DevBufs& B, uint16_t* cell) {
+// heatmap[cell] += 1 (pcgrl_env.py:137) without waiting for the old value, `idx` = the cell's index in the whole buffer.
+// Auto-reset handles count in 16 bits: a no-return 32-bit atomic add on the word that holds the counter (a count is at most
+// the episode's changes <= max_changes <= 65 535, so a half never carries into the other); only the very last counter of a
+// buffer with an odd number of cells has no complete word and takes the plain path.  Without auto-reset an episode goes on
+// past done and a cell's count is unbounded: B.heat32, one 32-bit counter per cell.  AR_ONLY: the caller is a kernel that
+// only auto-reset handles launch (the fused step kernels) -- the 16-bit path alone, no flag read.
+template <bool AR_ONLY = false>
+__device__ __forceinline__ void heat_increment(const DevBufs& B, size_t idx) {
+    if (!AR_ONLY && B.heat32) { atomicAdd(reinterpret_cast<uint32_t*>(B.heat) + idx, 1u); return; }
+    uint16_t* cell = B.heat + idx;
     const uintptr_t a = reinterpret_cast<uintptr_t>(cell);
     uint32_t* word = reinterpret_cast<uint32_t*>(a & ~(uintptr_t)3);
     if (reinterpret_cast<uintptr_t>(word) + 4 <= reinterpret_cast<uintptr_t>(B.heat_end)) atomicAdd(word, 1u << ((a & 2) * 8));
     else *cell += 1;
+}
+// heatmap[e] = 0 for the environment's `cells` counters (pcgrl_env.py:72), threads `t` = 0, `step`, 2 * step, ...  One loop over
+// 16-bit halves either way (a 32-bit counter is two of them): a second loop cost the statistics kernels registers.
+template <bool AR_ONLY = false>
+__device__ __forceinline__ void heat_clear(const DevBufs& B, int e, int cells, int t, int step) {
+    const int sh = AR_ONLY ? 0 : B.heat32;
+    uint16_t* heat_g = B.heat + ((size_t)e * cells << sh);
+    const int n = cells << sh;
+    for (int c = t; c < n; c += step) heat_g[c] = 0;
 }
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }

@@ -152,7 +152,7 @@ class BatchedPcgrlEnv:
         b = OrderedDict()
         b["map"] = z((n, h, w), torch.uint8)
         b["old_map"] = z((n, h, w), torch.uint8)
-        b["heatmap"] = z((n, h, w), torch.int16)
+        b["heatmap"] = z((n, h, w), torch.int16 if lay.heatmap == 2 * n * h * w else torch.int32)     # 32-bit counts without auto-reset
         b["pos"] = z((n, 2), torch.uint8)
         b["planes"] = z((n, lay.group, lay.nplanes), mask_dtype) if lay.nplanes else z((2,), mask_dtype)   # smb keeps no bit planes
         b["counters"] = z((n, 2), torch.int32)
@@ -276,10 +276,12 @@ class BatchedPcgrlEnv:
         if self._rep.has_pos:
             o["pos"] = b["pos"]
         o["map"] = b["map"]
-        # the device counts changes per cell in 16 bits (pcgrl_env.py:35,137 keeps a float64): the view is int16 while a count cannot
-        # pass 32 767 (max_changes, which bounds it, does not: every configuration of the reference's defaults) -- full operator
-        # support in torch -- and uint16 beyond (maps of more than 32 767 cells with a change_percentage to match)
-        o["heatmap"] = b["heatmap"] if self._max_changes <= 32767 else b["heatmap"].view(self._torch.uint16)
+        # pcgrl_env.py:35,137 keeps a float64 count per cell.  With auto-reset the device counts in 16 bits (a count is at most the
+        # episode's changes <= max_changes): the view is int16 while a count cannot pass 32 767 (every configuration of the reference's
+        # defaults) -- full operator support in torch -- and uint16 beyond (maps of more than 32 767 cells with a change_percentage to
+        # match).  Without auto-reset an episode goes on past done and the counts are unbounded: int32, as the device keeps them
+        hm = b["heatmap"]
+        o["heatmap"] = hm if (hm.dtype == self._torch.int32 or self._max_changes <= 32767) else hm.view(self._torch.uint16)
         return o
 
     def reset(self):
@@ -483,6 +485,14 @@ class BatchedPcgrlEnv:
         decode = self._prob.decode_rows if self._prob.packed_rows else None
         info = InfoBatch(self._prob.info_keys, b["info"], self._max_iterations, self._max_changes, decode)
         return self._obs(), b["reward"], b["done"].view(self._torch.bool), info, self._async["pending"]
+
+    def async_idle(self):
+        """bool [N] device tensor (a new one, not a view): the environments that take their action at the next tick -- those with no
+        step in flight.  Read from the live pending state, so it is right after anything that finished or dropped pending steps
+        in between (adjust_param() / step() / rollout() flush them, reset() / set_maps() drop them)."""
+        if self._async is None:
+            return self._torch.ones(self.num_envs, dtype=self._torch.bool, device=self.device)
+        return self._async["pending"] == 0
 
     def flush(self):
         """Finish every pending step (searches with an unbounded budget)."""

@@ -63,7 +63,9 @@ class RolloutCollector:
         """pop_budget: collect with asynchronous ticks (BatchedPcgrlEnv.tick; sokoban / mdungeon / ddave) -- a row of the buffer is then a
         tick, `took` / `fresh` say which environments acted in it and which completed a step (an environment whose search is
         suspended sits ticks out; the policy's action for it is ignored; its reward and done in those rows are zero).  Per environment the rows with `took` / `fresh` set, in
-        order, are the transitions a lockstep rollout holds.  No host synchronisation either way."""
+        order, are the transitions a lockstep rollout holds.  No host synchronisation either way.  Steps in flight that something
+        finishes between two rows (adjust_param() flushes them) complete outside any row: their outcomes are dropped, and a `took` row
+        followed by another `took` row of the environment with no `fresh` row in between marks such a step (BatchedVecEnv likewise)."""
         self.begin(pop_budget)
         for t in range(self.buffer.n_steps):
             self.step(t, policy, pop_budget)
@@ -73,8 +75,6 @@ class RolloutCollector:
         """The head of a rollout: the first observation in row 0 (a reset the first time, afterwards where the previous rollout stopped).
         collect() = begin() + step(t) for every row; DoubleBufferedCollector calls the two itself, sub-batch by sub-batch."""
         torch, b = self.torch, self.buffer
-        if pop_budget is not None and getattr(self, "_pending", None) is None:
-            self._pending = torch.zeros(self.env.num_envs, dtype=torch.bool, device=b.obs.device)
         w = self.env.env                                  # the image wrapper below the Monitor layer: no host sync
         if self._obs is None:
             if self.direct:
@@ -100,10 +100,9 @@ class RolloutCollector:
         if direct:
             w.set_observation_target(nxt)             # the step writes the next row itself
         if asynchronous:
-            b.took[t].copy_(~self._pending)
+            b.took[t].copy_(w.pcgrl_env.async_idle())     # the live pending state (a flush -- adjust_param() -- may have finished steps since)
             self._obs, rew, done, _, pend = w.tick(actions, pop_budget=pop_budget)
-            self._pending = pend != 0
-            b.fresh[t].copy_(~self._pending)
+            b.fresh[t].copy_(pend == 0)
         else:
             self._obs, rew, done, _ = w.step(actions)
         if not direct:

@@ -26,7 +26,10 @@ class BatchedVecEnv:
     four values; `infos.took` / `infos.fresh` (bool [N] device tensors) say which environments took their action in this call and
     which completed a step in it -- reward is 0 and done False where `fresh` is not set, so sums over calls stay right, and per
     environment the (took action -> fresh outcome) pairs are bitwise the lockstep transitions.  A problem without an asynchronous
-    form steps in lockstep with both masks all true."""
+    form steps in lockstep with both masks all true.  Something that finishes the steps in flight between two calls -- adjust_param()
+    flushes them -- completes them outside any call: their outcomes are dropped (no call reports them as `fresh`), and the next call
+    has those environments take their action again.  Per environment, a `took` call that is followed by another `took` call with
+    no `fresh` one in between is such a dropped step."""
 
     def __init__(self, wrapped, image_shape, n_actions, monitor=False, async_ticks=None):
         self.env = wrapped
@@ -40,21 +43,16 @@ class BatchedVecEnv:
         self.async_ticks = int(async_ticks) if async_ticks else None
         if self.async_ticks is not None and self.async_ticks < 1:
             raise ValueError("async_ticks: a pop budget >= 1")
-        self._sitting_out = None           # bool [N]: environments whose search is suspended (they ignore the next action)
 
     def reset(self):
-        self._sitting_out = None           # (reset() drops what was pending)
         return self.env.reset()
 
     def _tick(self, actions):
         e = self.env.pcgrl_env
         torch = e._torch
-        if self._sitting_out is None:
-            self._sitting_out = torch.zeros(self.num_envs, dtype=torch.bool, device=e.device)
-        took = ~self._sitting_out
+        took = e.async_idle()                # the live pending state: a flush since the last call is in it (a cached copy was not)
         obs, rew, done, infos, pend = self.env.tick(actions, pop_budget=self.async_ticks)
-        self._sitting_out = pend != 0
-        fresh = ~self._sitting_out
+        fresh = pend == 0
         return obs, torch.where(fresh, rew, torch.zeros_like(rew)), done & fresh, _TickInfos(infos, took, fresh)
 
     def step(self, actions):

@@ -37,8 +37,9 @@ extern "C" {
  * 5: + the ddave problem: pcgrl_config grew (max_diamonds, min_spikes, target_jumps).  6: + pcgrl_rollout.
  * 7: + the smb problem: pcgrl_config grew (min_empty, min_enemies, min_jumps; `reserved_` is gone); pcgrl_status reports
  *    clamped actions.  10: + pcgrl_tuning / pcgrl_set_tuning (the library reads no environment variables any more); pcgrl_config
- *    grew (prob_width, prob_height); maps up to 255 x 255, search levels up to 16 384 bordered cells, solver_power up to 1 000 000. */
-#define PCGRL_ABI_VERSION 14
+ *    grew (prob_width, prob_height); maps up to 255 x 255, search levels up to 16 384 bordered cells, solver_power up to 1 000 000.
+ * 15: without auto_reset the heat map holds 32-bit counts (an episode goes on past done); max_changes beyond 65 535 there. */
+#define PCGRL_ABI_VERSION 15
 #define PCGRL_OK 0
 #define PCGRL_EINVAL (-1)   /* bad argument / unsupported configuration */
 #define PCGRL_EHIP (-2)     /* a HIP runtime call failed (see pcgrl_last_hip_error) */
@@ -79,7 +80,8 @@ typedef struct pcgrl_layout {
     int32_t nstats;       /* used slots of a stats row: 2 binary, 7 zelda, 6 sokoban, 8 mdungeon / ddave (packed, see below), 8 smb */
     size_t map;           /* u8  [N,H,W]   observation "map" */
     size_t old_map;       /* u8  [N,H,W]   Representation._old_map */
-    size_t heatmap;       /* i16 [N,H,W]   observation "heatmap" (counts) */
+    size_t heatmap;       /* i16 [N,H,W]   observation "heatmap" (counts; auto_reset: at most max_changes <= 65 535, read as u16);
+                                 i32 [N,H,W] without auto_reset (stepping past done: unbounded counts) */
     size_t pos;           /* u8  [N,2]     observation "pos" (x,y); unused for wide */
     size_t planes;        /* mask[N,group,nplanes] row bitboards of the tile-id bits (the planes of a row are adjacent) */
     size_t counters;      /* i32 [N,2]     iteration, changes */

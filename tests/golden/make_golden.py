@@ -16,6 +16,7 @@ Fixture families:
   range_reward.npz exhaustive small table of helper.get_range_reward
   adjust_param.npz  the adjust_param ordering quirk (Q9) and spaces
   traj_*.npz       full env trajectories (obs map/pos/heatmap, reward, done, info) with auto-reset
+  noreset.npz      stepping past done with no reset; one cell's heat count past 2^16
 """
 import argparse
 import os
@@ -1034,6 +1035,57 @@ def gen_heat_boundary():
     print("heat_boundary", heat.max(), "%.0f s" % (time.time() - t0))
 
 
+NORESET_RUNS = [("binary", "wide", 11), ("zelda", "narrow", 12)]     # (problem, representation, seed)
+
+
+def gen_noreset():
+    """Stepping past done with no reset (pcgrl_env.py:130-150: the reference's PcgrlEnv goes on after done -- map, counters and the
+    float64 heat map keep changing).  binary-wide 14 x 14 and zelda-narrow 11 x 7 at change_percentage 0.05, 300 random actions each:
+    the per-step reward / done / info, the final map and the final heat map as (cell, count) pairs.  Then one cell of binary-wide
+    14 x 14 rewritten 66 000 times with alternating tiles, every write a change: its count passes 2^16 (per-step outputs of the first
+    and last 200 steps and every 1000th one, the final heat map as pairs)."""
+    t0 = time.time()
+    T, out = 300, {}
+    for k, (prob, rep, seed) in enumerate(NORESET_RUNS):
+        env = gym.make("%s-%s-v0" % (prob, rep))
+        env.adjust_param(change_percentage=0.05)
+        env.seed(seed)
+        obs = env.reset()
+        W, H, nt = env._prob._width, env._prob._height, env.get_num_tiles()
+        acts = sample_actions(np.random.RandomState(100 + k), rep, T, 1, W, H, nt)[:, 0]
+        rew, done, info = [], [], []
+        for t in range(T):
+            obs, r, d, inf = env.step(int(acts[t, 0]) if rep == "narrow" else [int(v) for v in acts[t]])
+            rew.append(r); done.append(d); info.append([int(inf[key]) for key in INFO_KEYS[prob]] + [inf["iterations"], inf["changes"]])
+        assert sum(done) > T // 2          # most steps past done
+        heat = np.asarray(obs["heatmap"])
+        cells = np.argwhere(heat != 0)
+        p = "%s_" % prob
+        out.update({p + "cfg": np.array([W, H, env._max_changes, env._max_iterations, seed], np.int64), p + "actions": acts,
+                    p + "reward": np.array(rew, np.float64), p + "done": np.array(done, np.bool_), p + "info": np.array(info, np.int64),
+                    p + "map": np.asarray(obs["map"]).astype(np.uint8), p + "heat_cells": cells.astype(np.int64),
+                    p + "heat_counts": np.array([heat[y, x] for y, x in cells], np.int64)})
+    # one cell past 2^16
+    T, x, y = 66000, 5, 9
+    env = gym.make("binary-wide-v0")
+    env.seed(13)
+    obs = env.reset()
+    m0 = int(obs["map"][y][x])
+    keep = sorted(set(list(range(200)) + list(range(0, T, 1000)) + list(range(T - 200, T))))
+    rew, done, info = [], [], []
+    for t in range(T):
+        obs, r, d, inf = env.step([x, y, 1 - m0 if t % 2 == 0 else m0])
+        if t in keep:
+            rew.append(r); done.append(d); info.append([inf[key] for key in INFO_KEYS["binary"]] + [inf["iterations"], inf["changes"]])
+    heat = np.asarray(obs["heatmap"])
+    cells = np.argwhere(heat != 0)
+    out.update(long_cfg=np.array([14, 14, 13, T, x, y, m0], np.int64), long_steps=np.array(keep, np.int64),
+               long_reward=np.array(rew, np.float64), long_done=np.array(done, np.bool_), long_info=np.array(info, np.int64),
+               long_heat_cells=cells.astype(np.int64), long_heat_counts=np.array([heat[yy, xx] for yy, xx in cells], np.int64))
+    save("noreset", **out)
+    print("noreset", heat.max(), "%.0f s" % (time.time() - t0))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default=None)
@@ -1042,6 +1094,7 @@ def main():
         "rng": gen_rng, "stats_binary": gen_stats_binary, "stats_zelda": gen_stats_zelda,
         "stats_sokoban": gen_stats_sokoban, "stats_mdungeon": gen_stats_mdungeon, "stats_ddave": gen_stats_ddave, "stats_smb": gen_stats_smb, "range_reward": gen_range_reward, "adjust_param": gen_adjust_param,
         "wrappers": gen_wrappers, "stats_big": gen_stats_big, "stats_big_search": gen_stats_big_search, "stats_huge_search": gen_stats_huge_search, "heat_boundary": gen_heat_boundary,
+        "noreset": gen_noreset,
     }
     for k, fn in jobs.items():
         if a.only in (None, k):

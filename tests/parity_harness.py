@@ -113,20 +113,31 @@ def draw_config(rs, only=None):
 MAP_EVERY = 5      # stepping: the cursor and the heat map are compared at every step, the whole map every MAP_EVERY steps and at the end
 
 
-def _obs_mismatch(obs, exp, t, has_pos, sel=None):
+def _obs_mismatch(obs, exp, t, has_pos, sel=None, map_every=MAP_EVERY):
     """Observation of step t (device tensors, optionally the rows `sel`) against the oracle's: cursor and heat map always,
-    the map every MAP_EVERY steps.  -> None or the name of what differs."""
+    the map every `map_every` steps.  -> None or the name of what differs."""
     pick = (lambda x: x) if sel is None else (lambda x: x[sel])
     if has_pos and not np.array_equal(pick(obs["pos"]).cpu().numpy().astype(np.int64), np.stack([x["pos"][t] for x in exp])):
         return "pos"
     if not np.array_equal(pick(obs["heatmap"]).cpu().numpy().astype(np.int64), np.stack([x["heatmap"][t] for x in exp]).astype(np.int64)):
         return "heatmap"
-    if t % MAP_EVERY == 0 and not np.array_equal(pick(obs["map"]).cpu().numpy(), np.stack([x["maps"][t] for x in exp])):
+    if t % map_every == 0 and not np.array_equal(pick(obs["map"]).cpu().numpy(), np.stack([x["maps"][t] for x in exp])):
         return "map"
     return None
 
 
-def _oracle_rollouts(prob, rep, calls, seeds, acts_by_env):
+def oracle_noreset(o, actions):
+    """The oracle stepped through `actions` [T, k] with PcgrlEnv.step and no reset at done (pcgrl_env.py:130-150: an episode goes
+    on past done, the heat map keeps counting) -> the dict of OracleEnv.rollout, the heat map as the oracle's float64 counts."""
+    keys = ol.INFO_KEYS[o.prob] + ["iterations", "changes"]
+    steps = [o.step(a) for a in np.asarray(actions, dtype=np.int32).reshape(len(actions), -1)]
+    return dict(maps=np.stack([s[0]["map"] for s in steps]), heatmap=np.stack([s[0]["heatmap"] for s in steps]),
+                pos=np.stack([s[0].get("pos", np.zeros(2, np.uint8)) for s in steps]).astype(np.int32),
+                reward=np.array([s[1] for s in steps], np.float64), done=np.array([s[2] for s in steps], bool),
+                info=np.array([[s[3][k] for k in keys] for s in steps], np.int64).reshape(len(steps), len(keys)))
+
+
+def _oracle_rollouts(prob, rep, calls, seeds, acts_by_env, auto_reset=True):
     out = []
     for seed, a in zip(seeds, acts_by_env):
         o = ol.OracleEnv(prob, rep)
@@ -134,18 +145,18 @@ def _oracle_rollouts(prob, rep, calls, seeds, acts_by_env):
             o.adjust_param(**kw)
         o.seed(int(seed))
         o.reset()
-        out.append(o.rollout(a))
+        out.append(o.rollout(a) if auto_reset else oracle_noreset(o, a))
     return out
 
 
-def run_config(prob, rep, calls, E, T, seed0, rs, use_rollout, mixed=False, steps_scale=1.0):
+def run_config(prob, rep, calls, E, T, seed0, rs, use_rollout, mixed=False, steps_scale=1.0, auto_reset=True, map_every=MAP_EVERY):
     """One configuration on the GPU against the oracle.  `mixed`: the first part of the tape as one rollout of ODD length,
-    the rest as single steps on the same handle (switching between the fused and the work-list pipelines).  Returns None
-    or a string describing the first mismatch."""
+    the rest as single steps on the same handle (switching between the fused and the work-list pipelines).  auto_reset=False:
+    the environments step on past done, the oracle without reset().  Returns None or a string describing the first mismatch."""
     import torch
     from gym_pcgrl_amd.envs import BatchedPcgrlEnv
     T = max(4, int(T * steps_scale))
-    env = BatchedPcgrlEnv(prob=prob, rep=rep, num_envs=E, seed=seed0)
+    env = BatchedPcgrlEnv(prob=prob, rep=rep, num_envs=E, seed=seed0, auto_reset=auto_reset)
     try:
         for kw in calls:
             env.adjust_param(**kw)
@@ -155,7 +166,7 @@ def run_config(prob, rep, calls, E, T, seed0, rs, use_rollout, mixed=False, step
             acts = rs.randint(0, sp.n, size=(T, E, 1)).astype(np.int32)
         else:
             acts = np.stack([rs.randint(0, int(k), size=(T, E)) for k in sp.nvec], -1).astype(np.int32)
-        exp = _oracle_rollouts(prob, rep, calls, [seed0 + i for i in range(E)], [acts[:, i] for i in range(E)])
+        exp = _oracle_rollouts(prob, rep, calls, [seed0 + i for i in range(E)], [acts[:, i] for i in range(E)], auto_reset)
         keys = list(env._prob.info_keys) + ["iterations", "changes"]
         t_roll = 0
         obs = env._obs()
@@ -176,7 +187,7 @@ def run_config(prob, rep, calls, E, T, seed0, rs, use_rollout, mixed=False, step
                 np.array_equal(np.stack([info[k].cpu().numpy() for k in keys], 1).astype(np.int64), np.stack([x["info"][t] for x in exp]))
             if not ok:
                 return "MISMATCH %s %s %s E %d seed %d step %d" % (prob, rep, calls, E, seed0, t)
-            bad = _obs_mismatch(obs, exp, t, env._rep.has_pos)
+            bad = _obs_mismatch(obs, exp, t, env._rep.has_pos, map_every=map_every)
             if bad:
                 return "OBS MISMATCH (%s) %s %s %s E %d seed %d step %d" % (bad, prob, rep, calls, E, seed0, t)
         # the state the tape / the steps end in: map, cursor, heat map
@@ -265,16 +276,17 @@ def fullsize_case(name, use_rollout, max_steps=None):
     return len(idx)
 
 
-def async_case(prob, rep, calls, E, ticks, seed0, rs, pop_budget, nslots, sample=None, flush_every=0, tuning=None):
+def async_case(prob, rep, calls, E, ticks, seed0, rs, pop_budget, nslots, sample=None, flush_every=0, tuning=None, auto_reset=True):
     """Asynchronous stepping (BatchedPcgrlEnv.tick, pcgrl_step_async) against the oracle: `ticks` ticks of random actions; per
     environment the actions it *took* (the ticks it was not pending at) and the outputs of every step it completed are recorded,
     and afterwards the oracle is stepped through exactly the taken actions -- reward, done, info, cursor, heat map and map of
     every completed step must be equal, bit for bit.  `sample`: indices of the environments compared (default: all).
     flush_every > 0: every that many ticks the pending steps are finished by flush() and a lockstep step() is taken in between
-    (the two kinds of stepping on one handle).  Returns a dict of counters; raises AssertionError on a mismatch."""
+    (the two kinds of stepping on one handle).  auto_reset=False: past done, against the oracle without reset().  Returns a dict
+    of counters; raises AssertionError on a mismatch."""
     import torch
     from gym_pcgrl_amd.envs import BatchedPcgrlEnv
-    env = BatchedPcgrlEnv(prob=prob, rep=rep, num_envs=E, seed=seed0, tuning=tuning)
+    env = BatchedPcgrlEnv(prob=prob, rep=rep, num_envs=E, seed=seed0, tuning=tuning, auto_reset=auto_reset)
     try:
         for kw in calls:
             env.adjust_param(**kw)
@@ -325,7 +337,7 @@ def async_case(prob, rep, calls, E, ticks, seed0, rs, pop_budget, nslots, sample
         for j in np.nonzero(pending)[0]:
             got[j].append(tuple(x[j] for x in rows))
         cnt = env.async_counters()
-        exp = _oracle_rollouts(prob, rep, calls, [seed0 + int(i) for i in idx], [np.asarray(tk) for tk in taken])
+        exp = _oracle_rollouts(prob, rep, calls, [seed0 + int(i) for i in idx], [np.asarray(tk) for tk in taken], auto_reset)
         for j, x in enumerate(exp):
             assert len(got[j]) == len(taken[j]), ("steps completed vs actions taken", prob, idx[j], len(got[j]), len(taken[j]))
             for k, (rew_k, done_k, info_k, pos_k, heat_k, map_k) in enumerate(got[j]):

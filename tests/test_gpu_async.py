@@ -206,3 +206,105 @@ def test_make_vec_envs_async_ticks_gives_the_lockstep_transitions_per_environmen
         assert eps_a[:m] == eps_l[:m], e
         n_eps += m
     assert n_eps > 0
+
+
+def _pairs(took, fresh, a, r, d):
+    """One environment's calls -> its (action, reward, done) transitions in order; a step whose outcome no call reported (a flush
+    between two calls finished it: a `took` call followed by another `took` call with no `fresh` one in between) gets None."""
+    out, open_ = [], None
+    for t in range(len(took)):
+        if took[t]:
+            if open_ is not None:
+                out.append((open_, None, None))
+            open_ = a[t]
+        if fresh[t]:
+            out.append((open_, r[t], d[t]))
+            open_ = None
+    return out
+
+
+def _check_flushed_run(lock, asy, n_flushed_min=1):
+    """Per environment the asynchronous run's transitions (with dropped outcomes) against the lockstep ones."""
+    dropped = 0
+    for e in range(lock["a"].shape[1]):
+        pairs = _pairs(asy["took"][:, e], asy["fresh"][:, e], asy["a"][:, e], asy["r"][:, e], asy["d"][:, e])
+        k = min(len(pairs), len(lock["a"]))
+        for j in range(k):
+            act, rew, done = pairs[j]
+            assert act == lock["a"][j, e], ("action", e, j)
+            if rew is None:
+                dropped += 1
+            else:
+                assert rew == lock["r"][j, e] and done == lock["d"][j, e], ("outcome", e, j)
+    assert dropped >= n_flushed_min, dropped
+
+
+def test_make_vec_envs_async_ticks_across_a_flush():
+    """adjust_param() with an unchanged value in the middle of an asynchronous run flushes the steps in flight.  The environments
+    that had one take their action at the next call (`took`: read from the live pending state), the flushed steps' outcomes are
+    dropped -- a `took` call followed by another `took` call -- and per environment the transitions are still the lockstep ones."""
+    import torch
+    from gym_pcgrl_amd.utils import make_vec_envs
+    N, T_lock, T_tick, t_flush = 64, 24, 40, 6
+
+    def policy(obs, n_act):
+        flat = obs.reshape(obs.shape[0], -1).to(torch.int64)
+        w = torch.arange(1, flat.shape[1] + 1, device=obs.device, dtype=torch.int64) % 89 + 1
+        return (flat * w).sum(1) % n_act
+
+    rec = []
+    for budget in (None, 4):
+        venv = make_vec_envs("sokoban-narrow-v0", "narrow", n_cpu=N, seed=29, device="cuda:0", async_ticks=budget, change_percentage=0.6)
+        n_act = int(venv.action_space.n)
+        obs = venv.reset()
+        rows = dict(a=[], r=[], d=[], took=[], fresh=[])
+        flushed, t_flushed = 0, None
+        for t in range(T_lock if budget is None else T_tick):
+            if budget is not None and t >= t_flush and t_flushed is None and not rows["fresh"][-1].all():   # the first call after t_flush
+                pend = venv.env.pcgrl_env._async["pending"].cpu().numpy()                                  # with steps in flight
+                flushed, t_flushed = int((pend != 0).sum()), t
+                venv.env.adjust_param(change_percentage=0.6)          # unchanged: only the flush
+                assert not venv.env.pcgrl_env._async["pending"].any()
+            a = policy(obs, n_act)
+            obs, rew, done, infos = venv.step(a)
+            rows["a"].append(a.cpu().numpy()); rows["r"].append(rew.cpu().numpy()); rows["d"].append(done.cpu().numpy())
+            rows["took"].append(infos.took.cpu().numpy() if budget else np.ones(N, bool))
+            rows["fresh"].append(infos.fresh.cpu().numpy() if budget else np.ones(N, bool))
+        rec.append({k: np.stack(v) for k, v in rows.items()})
+        venv.close()
+    assert flushed > 0, "nothing was in flight at the flush"
+    lock, asy = rec
+    assert asy["took"][t_flushed].sum() >= flushed
+    _check_flushed_run(lock, asy, flushed)
+
+
+def test_async_collector_across_a_flush():
+    """RolloutCollector.collect(policy, pop_budget=4) with adjust_param() (unchanged value: a flush) called by the policy in the middle
+    of the rollout: `took` comes from the live pending state, the flushed steps' outcomes are dropped, and per environment the
+    transitions are the lockstep collector's."""
+    import torch
+    from gym_pcgrl_amd.rollout import RolloutCollector
+    from gym_pcgrl_amd.utils import make_vec_envs
+    N, T_lock, T_tick, t_flush = 64, 24, 40, 6
+    out, flushed = [], [0]
+    for budget in (None, 4):
+        venv = make_vec_envs("sokoban-narrow-v0", "narrow", n_cpu=N, seed=31, device="cuda:0", change_percentage=0.6)
+        n_act = int(venv.action_space.n)
+        calls = [0]
+
+        def policy(obs):
+            if budget is not None and calls[0] == t_flush:
+                flushed[0] = int((venv.env.pcgrl_env._async["pending"] != 0).sum().item())
+                venv.env.adjust_param(change_percentage=0.6)           # unchanged: only the flush (finishes the images of obs too)
+            calls[0] += 1
+            flat = obs.reshape(obs.shape[0], -1).to(torch.int64)
+            w = torch.arange(1, flat.shape[1] + 1, device=obs.device, dtype=torch.int64) % 97 + 1
+            return (flat * w).sum(1) % n_act
+        col = RolloutCollector(venv, T_lock if budget is None else T_tick)
+        b = col.collect(policy, pop_budget=budget)
+        torch.cuda.synchronize()
+        d = {k: v.cpu().numpy() for k, v in b.as_dict().items() if k in ("actions", "rewards", "dones", "took", "fresh")}
+        out.append(dict(a=d["actions"], r=d["rewards"], d=d["dones"], took=d["took"], fresh=d["fresh"]))
+        venv.close()
+    assert flushed[0] > 0, "nothing was in flight at the flush"
+    _check_flushed_run(out[0], out[1], flushed[0])

@@ -2015,3 +2015,74 @@ def test_solver_power_beyond_the_allocated_arena_reallocates():
     exp = np.stack([ol.get_stats("sokoban", m, solver_power=300) for m in maps])
     assert np.array_equal(env.stats.cpu().numpy().astype(np.int64), exp)
     env.close()
+
+
+# ------------------------------------------------------------------ the developer switches no other test sets
+# include/pcgrl_hip.h promises that every alternative of pcgrl_tuning gives the same results; tests/test_switch_coverage.py fails when
+# a switch is set by no GPU test.
+_BIG_MAP_CASES = [c for c in ORACLE_CASES if c[0] in ("binary", "zelda") and any(k.get("width", 0) > 64 or k.get("height", 0) > 64 for k in c[2])]
+_TALL_SOAK = [i for i, c in enumerate(SOAK_CASES) if c[0] == "binary" and 16 < max([k.get("height", 14) for k in c[2]] + [14]) <= 64]
+_TALL_TRAJ = [p for p in sorted(glob.glob(os.path.join(G, "traj_binary_*.npz")))
+              if 16 < int(np.load(p)["cfg"][1]) <= 64 and int(np.load(p)["cfg"][0]) <= 64]
+# the Sokoban cases of the compact searches (levels of at most 256 bordered cells, solver_power <= 16 383): the BFS that publishes its
+# level to idle blocks is theirs (search_big.h runs the general searches)
+def _compact_search(calls):
+    kw = {k: v for c in calls for k, v in c.items()}
+    return kw.get("solver_power", 0) <= 16383 and (kw.get("width", 5) + 2) * (kw.get("height", 5) + 2) <= 256
+
+
+_SOKOBAN_CASES = [c for c in ORACLE_CASES if c[0] == "sokoban" and _compact_search(c[2])]
+
+
+_RESET_LIST_RUNS = [("soak", i) for i in range(len(SOAK_CASES))] + \
+                   [("traj", os.path.join(G, n)) for n in ("traj_binary_narrow.npz", "traj_zelda_wide_11x16.npz")] + \
+                   [("oracle", c) for c in _BIG_MAP_CASES]
+
+
+def _run(kind, arg):
+    if kind == "soak":
+        test_incremental_routes_soak(*SOAK_CASES[arg])
+    elif kind == "traj":
+        test_golden_trajectory(arg)
+    else:
+        test_rollout_vs_oracle(*arg)
+
+
+def _run_id(v):
+    if isinstance(v, str):
+        return os.path.basename(v)
+    if isinstance(v, int):
+        return str(v)
+    return "%s-%s-%dx%d" % (v[0], v[1], v[2][0].get("width"), v[2][0].get("height"))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind,arg", _RESET_LIST_RUNS, ids=_run_id)
+def test_resets_through_the_reset_list(kind, arg, monkeypatch):
+    """inline_reset = 0: binary and zelda reset through the reset list and k_reset instead of inside k_stats / k_step / k_big (which
+    also turns the fused k_step off and takes the !inline_reset branches of k_update) -- binary's k_reset after a step draws the
+    problem ring (rng_prob, tile_p) too.  The soak cases, two of the reference's trajectories and the maps beyond 64 x 64 step for
+    step as before."""
+    _tune(monkeypatch, "inline_reset", 0)
+    _run(kind, arg)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind,arg", [("soak", i) for i in _TALL_SOAK] + [("traj", p) for p in _TALL_TRAJ], ids=_run_id)
+def test_tall_maps_on_one_wavefront_per_map(kind, arg, monkeypatch):
+    """no_wide = 1: tall binary maps (17..64 rows) on k_stats<BINARY, 64, *> -- one wavefront per map -- instead of k_stats_wide:
+    the tall soak cases and the reference's trajectories of tall binary maps."""
+    _tune(monkeypatch, "no_wide", 1)
+    _run(kind, arg)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("spawn,cap", [(1, None), (16, None), (100000, None), (1, 0), (1, 1)])
+@pytest.mark.parametrize("prob,rep,calls,E,T", _SOKOBAN_CASES, ids=lambda v: str(v) if isinstance(v, (str, int)) else "cfg")
+def test_sokoban_spawn_thresholds(prob, rep, calls, E, T, spawn, cap, monkeypatch):
+    """sok_spawn: pops after which a Sokoban BFS publishes its level to idle blocks (default 128) -- at once, soon, never; at once
+    with the publishing list shrunk to 0 / 1 entries (sok_hard_cap).  The rollouts must not change."""
+    _tune(monkeypatch, "sok_spawn", spawn)
+    if cap is not None:
+        _tune(monkeypatch, "sok_hard_cap", cap)
+    test_rollout_vs_oracle(prob, rep, calls, E, T)

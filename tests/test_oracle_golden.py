@@ -199,3 +199,49 @@ def test_heat_map_beyond_int16_matches_reference():
     assert np.array_equal(got, d["heat_cells"]) and np.array_equal(heat[got[:, 0], got[:, 1]].astype(np.int64), d["heat_counts"])
     assert int(d["heat_counts"].max()) == T > 32767
     assert np.array_equal(np.argwhere(o.obs()["map"] == 0), d["empty_cells"])
+
+
+def _noreset_keys(prob):
+    return ol.INFO_KEYS[prob] + ["iterations", "changes"]
+
+
+@pytest.mark.parametrize("prob,rep", [("binary", "wide"), ("zelda", "narrow")])
+def test_stepping_past_done_matches_reference(prob, rep):
+    """noreset.npz (make_golden.py gen_noreset): the reference's PcgrlEnv stepped 300 times past done with no reset
+    (pcgrl_env.py:130-150); the oracle, stepped the same way, must give every step's reward / done / info, the final map and the
+    final float64 heat map."""
+    d = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "noreset.npz"))
+    p = prob + "_"
+    W, H, max_changes, max_iter, seed = [int(v) for v in d[p + "cfg"]]
+    o = ol.OracleEnv(prob, rep)
+    o.adjust_param(change_percentage=0.05)
+    o.seed(seed)
+    o.reset()
+    assert (o.width, o.height, o.max_changes, o.max_iterations) == (W, H, max_changes, max_iter)
+    keys = _noreset_keys(prob)
+    for t, a in enumerate(d[p + "actions"]):
+        obs, r, done, inf = o.step(a)
+        assert r == d[p + "reward"][t] and done == d[p + "done"][t], ("reward/done", t)
+        assert [inf[k] for k in keys] == list(d[p + "info"][t]), ("info", t)
+    assert np.array_equal(obs["map"], d[p + "map"])
+    cells = np.argwhere(obs["heatmap"] != 0)
+    assert np.array_equal(cells, d[p + "heat_cells"]) and np.array_equal(obs["heatmap"][cells[:, 0], cells[:, 1]], d[p + "heat_counts"])
+
+
+def test_heat_map_past_16_bits_without_reset_matches_reference():
+    """noreset.npz: one cell of binary-wide 14 x 14 rewritten 66 000 times past done, every write a change -- the reference's float64
+    count passes 2^16; the oracle's must be the same, and every other cell 0."""
+    d = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "noreset.npz"))
+    W, H, seed, T, x, y, m0 = [int(v) for v in d["long_cfg"]]
+    o = ol.OracleEnv("binary", "wide")
+    o.seed(seed)
+    assert int(o.reset()["map"][y, x]) == m0
+    steps, j, keys = set(int(s) for s in d["long_steps"]), 0, _noreset_keys("binary")
+    for t in range(T):
+        obs, r, done, inf = o.step([x, y, 1 - m0 if t % 2 == 0 else m0])
+        if t in steps:
+            assert r == d["long_reward"][j] and done == d["long_done"][j] and [inf[k] for k in keys] == list(d["long_info"][j]), t
+            j += 1
+    cells = np.argwhere(obs["heatmap"] != 0)
+    assert np.array_equal(cells, d["long_heat_cells"]) and np.array_equal(obs["heatmap"][cells[:, 0], cells[:, 1]], d["long_heat_counts"])
+    assert d["long_heat_counts"].tolist() == [T] and T > 65535
