@@ -2,15 +2,36 @@
 // Part of the single translation unit pcgrl_abi.hip (see its header comment for the overall picture).
 #pragma once
 // ActionMap.step for the wide representation (wrappers.py:139-154): flat index into (h, w, tiles) -> (x, y, tile)
-__global__ void k_action_map(const int32_t* __restrict__ flat, int32_t* __restrict__ xyv, int n, int w, int h, int dim, int32_t* status) {
+// (ash = 1: `flat` holds int64 values, the low word is the index -- pcgrl_row::actions_i64)
+__global__ void k_action_map(const int32_t* __restrict__ flat, int32_t* __restrict__ xyv, int n, int w, int h, int dim, int32_t* status, int ash) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) {
-        int a = flat[i];
+        int a = flat[(size_t)i << ash];
         if (a < 0 || a >= w * h * dim) atomicOr(status, PCGRL_STATUS_BAD_ACTION);     // clamped and reported
         a = a < 0 ? 0 : (a >= w * h * dim ? w * h * dim - 1 : a);
         const int v = a % dim, x = (a / dim) % w, y = a / (dim * w);
         xyv[3 * i] = x; xyv[3 * i + 1] = y; xyv[3 * i + 2] = v;
     }
+}
+
+// The columns of a rollout row (pcgrl_bind_row) behind a step that is not the row-writing k_step: one thread per environment forms
+// reward / done / episode start / Monitor columns from the handle's buffers as the step left them, the first n_act threads widen
+// the actions.  pending != null: an asynchronous tick -- an outcome counts where the environment's step is complete after the tick
+// (state 2, "a search ended the episode", becomes fresh one tick later: hence from the persistent buffers, at the end of the tick);
+// `took` was written by the tick's update kernel, before it changed the pending state.
+__global__ void k_row(DevBufs B, RowBind R, const uint8_t* __restrict__ pending, const int32_t* __restrict__ act, int n_act, int ash, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (R.actions_out && i < n_act) R.actions_out[i] = ash ? reinterpret_cast<const int64_t*>(act)[i] : (int64_t)act[i];
+    if (i >= n) return;
+    const bool fresh = pending ? pending[i] == 0 : true;
+    const uint8_t d = (fresh && B.done[i]) ? 1 : 0;
+    if (R.reward) R.reward[i] = fresh ? B.reward[i] : 0.0;
+    if (R.done) R.done[i] = d;
+    if (R.start_out) R.start_out[i] = fresh ? d : (R.start_in ? R.start_in[i] : (uint8_t)0);
+    if (R.ep_return) R.ep_return[i] = d ? B.last_return[i] : __longlong_as_double(0x7FF8000000000000ll);
+    if (R.ep_length) R.ep_length[i] = d ? B.last_length[i] : 0;
+    if (R.fresh) R.fresh[i] = fresh ? 1 : 0;
+    if (R.took && !pending) R.took[i] = 1;
 }
 
 // pcgrl_selftest_range_reward: helper.py:366-376 in the integer form every reward of the step kernels goes through (range_reward_i,

@@ -126,7 +126,11 @@ __device__ __forceinline__ void step_set_prio(int p) {
 // OBS (single step, 32-bit row masks, an observation bound whose shape has a lean routine): the images are written while the step
 // runs -- a kernel of its own so that the steps without an image carry none of it (the observation view is fourteen scalar registers:
 // in zelda's kernel, which is at its limit of 100, they were 80 bytes of scratch and 2.7 us of the bare C3 step).
-template <int PROB, int REP, class MaskT, bool MULTI, int EPB, bool OBS = false>
+// ROW (single step, pcgrl_bind_row): the actions are the caller's tensor as it is -- int64 values whose low words are staged, or
+// int32 -- and the block writes the other columns of the rollout row from its LDS copy of reward / done at the end, a store stream
+// per column.  A switch of its own, as OBS is: the row pointers sit at the end of DevBufs and only these instantiations load them,
+// a step without a binding runs exactly the code it ran before.
+template <int PROB, int REP, class MaskT, bool MULTI, int EPB, bool OBS = false, bool ROW = false>
 __global__ __launch_bounds__(EPB * 4) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_step(PcgrlParams P, DevBufs Bg, const int32_t* __restrict__ actions, int parity, int gen_map,
                                                                                                      int steps, size_t action_stride, double* reward_out, uint8_t* done_out, int32_t* info_out) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];   // the block's state copy, then per wave MT ring + tile bytes (in-kernel resets)
@@ -137,6 +141,7 @@ __global__ __launch_bounds__(EPB * 4) __attribute__((amdgpu_waves_per_eu(4, 8)))
     __shared__ StepLocal s_loc;
     __shared__ int s_obs_ticket;        // (OBS) the observation tasks' own ticket
     static_assert(!(OBS && MULTI), "the tape form writes its images at the end");
+    static_assert(!(ROW && MULTI), "the tape form has its own outputs (pcgrl_rollout ignores the row binding)");
     constexpr int G = 16, GPW = 4;
     constexpr int NPL = (PROB == PCGRL_PROB_BINARY) ? 1 : 3;
     constexpr int kPlaneRow = G * NPL * (int)sizeof(MaskT);
@@ -182,6 +187,19 @@ __global__ __launch_bounds__(EPB * 4) __attribute__((amdgpu_waves_per_eu(4, 8)))
     const int32_t* act_lds = reinterpret_cast<const int32_t*>(smem + L.act);
     const uint8_t* g_planes = reinterpret_cast<const uint8_t*>(Bg.planes) + (size_t)e0 * kPlaneRow;
     const uint8_t* g_champ = has_champ ? reinterpret_cast<const uint8_t*>(Bg.champ) + (size_t)e0 * champ_row : nullptr;
+    // ROW: the policy's action tensor as it is: int64 (the low word is the action: what a conversion to int32 keeps, clamping and
+    // status bit included) or int32, one value per thread (ne * AW <= TPB).  The load is issued here, in front of the prefetch, and
+    // its value is used behind it: one round trip for both.
+    const bool row_fl = ROW && AW == 3 && Bg.flat;
+    const int row_per = row_fl ? 1 : AW;
+    const size_t row_a0 = (size_t)e0 * row_per + threadIdx.x;
+    const bool row_have = ROW && (int)threadIdx.x < ne * row_per;
+    int64_t row_act = 0;
+    static_assert(AW <= 4, "one action value per thread");
+    if (row_have) {
+        const int32_t* src = row_fl ? Bg.flat : actions;
+        row_act = Bg.act_i64 ? reinterpret_cast<const int64_t*>(src)[row_a0] : (int64_t)src[row_a0];
+    }
     if (ne == EPB) {
         // a full block: every load of every segment first, then one wait, then the LDS stores -- one round trip
         static_assert(L.in_total / 16 <= 9 * TPB, "nine 16-byte slots per thread");
@@ -198,10 +216,12 @@ __global__ __launch_bounds__(EPB * 4) __attribute__((amdgpu_waves_per_eu(4, 8)))
             PCGRL_SEG_LOAD(L.tag / 16, EPB / 4, has_fifo ? Bg.fifo_tag + e0 : nullptr, has_fifo);
         }
         PCGRL_SEG_LOAD(L.pos / 16, EPB / 8, Bg.pos + (size_t)e0 * 2, true);
-        PCGRL_SEG_LOAD(L.act / 16, EPB / 4 * AW, actions + (size_t)e0 * AW, !(AW == 3 && Bg.flat));
-        if (AW == 3) PCGRL_SEG_LOAD(L.flat / 16, (AW == 3 ? EPB / 4 : 1), Bg.flat ? Bg.flat + e0 : nullptr, Bg.flat != nullptr);
+        // (ROW: the action segments -- the last two of the prefetch -- are staged below, from the caller's tensor)
+        if (!ROW) PCGRL_SEG_LOAD(L.act / 16, EPB / 4 * AW, actions + (size_t)e0 * AW, !(AW == 3 && Bg.flat));
+        if (!ROW && AW == 3) PCGRL_SEG_LOAD(L.flat / 16, (AW == 3 ? EPB / 4 : 1), Bg.flat ? Bg.flat + e0 : nullptr, Bg.flat != nullptr);
         asm volatile("" ::: "memory");      // every load above is issued before the first LDS store below waits for its data
-        constexpr int TOT = L.in_total / 16;
+        static_assert(L.act % 16 == 0, "the prefetch ends on a slot boundary in front of the actions");
+        constexpr int TOT = (ROW ? L.act : L.in_total) / 16;
         seg_store_c<TPB, 0, TOT>(smem, r0, tid0); seg_store_c<TPB, 1, TOT>(smem, r1, tid0); seg_store_c<TPB, 2, TOT>(smem, r2, tid0);
         seg_store_c<TPB, 3, TOT>(smem, r3, tid0); seg_store_c<TPB, 4, TOT>(smem, r4, tid0); seg_store_c<TPB, 5, TOT>(smem, r5, tid0);
         seg_store_c<TPB, 6, TOT>(smem, r6, tid0); seg_store_c<TPB, 7, TOT>(smem, r7, tid0); seg_store_c<TPB, 8, TOT>(smem, r8, tid0);
@@ -217,8 +237,13 @@ __global__ __launch_bounds__(EPB * 4) __attribute__((amdgpu_waves_per_eu(4, 8)))
             blk_copy<TPB>(smem + L.fifo, reinterpret_cast<const uint8_t*>(Bg.fifo + (size_t)e0 * PCGRL_FIFO_N), ne * PCGRL_FIFO_N * 4);
             blk_copy<TPB>(smem + L.tag, reinterpret_cast<const uint8_t*>(Bg.fifo_tag + e0), ne * 4);
         }
-        if (AW == 3 && Bg.flat) blk_copy<TPB>(smem + L.flat, reinterpret_cast<const uint8_t*>(Bg.flat + e0), ne * 4);
+        if (ROW) {}
+        else if (AW == 3 && Bg.flat) blk_copy<TPB>(smem + L.flat, reinterpret_cast<const uint8_t*>(Bg.flat + e0), ne * 4);
         else blk_copy<TPB>(smem + L.act, reinterpret_cast<const uint8_t*>(actions + (size_t)e0 * AW), ne * 4 * AW);
+    }
+    if (row_have) {      // the low words are the step's actions, the widened values row t's `actions` column
+        reinterpret_cast<int32_t*>(smem + (row_fl ? L.flat : L.act))[threadIdx.x] = (int32_t)row_act;
+        if (Bg.row.actions_out) Bg.row.actions_out[row_a0] = row_act;
     }
     if (threadIdx.x < EPB) { s_loc.dirty[threadIdx.x] = 0; if (OBS) { s_loc.obs_skip[threadIdx.x] = 0; s_loc.late[threadIdx.x] = 0; } }
     if (threadIdx.x < 8) s_n[threadIdx.x >> 2][threadIdx.x & 3] = 0;
@@ -445,6 +470,24 @@ __global__ __launch_bounds__(EPB * 4) __attribute__((amdgpu_waves_per_eu(4, 8)))
     blk_copy_rows<TPB>(reinterpret_cast<uint8_t*>(Bg.planes) + (size_t)e0 * kPlaneRow, smem + L.planes, ne, kPlaneRow, s_loc.dirty);
     if (has_champ) blk_copy_rows<TPB>(reinterpret_cast<uint8_t*>(Bg.champ) + (size_t)e0 * champ_row, smem + L.champ, ne, champ_row, s_loc.dirty);
     blk_copy_rows<TPB>(reinterpret_cast<uint8_t*>(Bg.start_stats + (size_t)e0 * 8), smem + L.start, ne, 32, s_loc.dirty);
+    if (ROW) {
+        // the columns of the rollout row from the LDS copy of reward / done, a quarter of the block (EPB threads) per group of columns;
+        // the Monitor columns read what episode_account latched in this launch (the block's own global stores: visible behind the barrier)
+        const RowBind& R = Bg.row;
+        const int q = (int)threadIdx.x / EPB, i = (int)threadIdx.x % EPB;
+        if (i < ne) {
+            const uint8_t d = smem[L.done + i] ? 1 : 0;
+            if (q == 0) { if (R.reward) R.reward[e0 + i] = reinterpret_cast<const double*>(smem + L.rew)[i]; }
+            else if (q == 1) {
+                if (R.done) R.done[e0 + i] = d;
+                if (R.start_out) R.start_out[e0 + i] = d;
+                if (R.took) R.took[e0 + i] = 1;
+                if (R.fresh) R.fresh[e0 + i] = 1;
+            }
+            else if (q == 2) { if (R.ep_return) R.ep_return[e0 + i] = d ? Bg.last_return[e0 + i] : __longlong_as_double(0x7FF8000000000000ll); }
+            else if (R.ep_length) R.ep_length[e0 + i] = d ? Bg.last_length[e0 + i] : 0;
+        }
+    }
     // ---- the wrapped observation of the block's environments (pcgrl_bind_observation), straight from the LDS copy: the row
     // planes are the map, the cursors are there too -- no byte map is read.  A store stream that overlaps with the blocks that
     // are still computing (the step is latency-bound, the memory system nearly idle).

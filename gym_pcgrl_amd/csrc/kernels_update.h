@@ -31,7 +31,8 @@ struct UpdateOut {
 // AR_ONLY: the caller runs for auto-reset handles only (k_step, k_step_solver): 16-bit heat counters (heat_increment).
 struct UpdateMid { int x, y, hx, hy, cur; bool chg, dead; };
 template <int REP, class MaskT, bool FIFO = false, bool SPLIT = false, bool AR_ONLY = false>
-__device__ __forceinline__ UpdateOut update_env(const PcgrlParams& P, const DevBufs& B, const int32_t* __restrict__ actions, int e, UpdateMid* mid = nullptr) {
+// ash = 1: `actions` holds int64 values whose low word is the action (pcgrl_row::actions_i64; k_step stages the low words itself: 0).
+__device__ __forceinline__ UpdateOut update_env(const PcgrlParams& P, const DevBufs& B, const int32_t* __restrict__ actions, int e, UpdateMid* mid = nullptr, const int ash = 0) {
     bool chg = false, rst = false, cheap = false, sure_done = false, touch_item = false;
     int bucket = 0, inc_item = 0, k_used = 0, cur0 = 0;
     uint32_t fw[PCGRL_FIFO_N];
@@ -42,8 +43,8 @@ __device__ __forceinline__ UpdateOut update_env(const PcgrlParams& P, const DevB
         // ---- round trip 1
         const int2 c = reinterpret_cast<const int2*>(B.counters)[e];
         int a0_ = 0, a1_ = 0, a2_ = 0;
-        if (REP == PCGRL_REP_WIDE) { a0_ = actions[3 * e + 0]; a1_ = actions[3 * e + 1]; a2_ = actions[3 * e + 2]; }
-        else a0_ = actions[e];
+        if (REP == PCGRL_REP_WIDE) { a0_ = actions[(size_t)(3 * e + 0) << ash]; a1_ = actions[(size_t)(3 * e + 1) << ash]; a2_ = actions[(size_t)(3 * e + 2) << ash]; }
+        else a0_ = actions[(size_t)e << ash];
         uchar2 p0 = make_uchar2(0, 0);
         if (REP != PCGRL_REP_WIDE) p0 = reinterpret_cast<const uchar2*>(B.pos)[e];
         const bool draws = REP == PCGRL_REP_NARROW && P.random_tile;
@@ -388,9 +389,10 @@ __global__ __launch_bounds__(PCGRL_BLOCK) void k_update(PcgrlParams P, DevBufs B
         const int cnt = __popcll(__ballot(live));
         if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(B.async_stats + 8 + 8 * (blockIdx.x & 15), (unsigned long long)cnt);
         if (pv == 2) { u.rst = true; B.pending[e] = 0; }      // (a search of the new map that is cut short marks it pending again)
+        if (B.row.took && e < P.num_envs) B.row.took[e] = live ? 1 : 0;      // (pcgrl_bind_row: who acts, before the tick changes it)
         async_list_runnable(B, e);
     }
-    if (live) u = update_env<REP, MaskT>(P, B, actions, e);
+    if (live) u = update_env<REP, MaskT>(P, B, actions, e, nullptr, B.act_i64);
     const bool chg = u.chg, rst = u.rst, cheap = u.cheap, sure_done = u.sure_done;
     int bucket = u.bucket;
     const int inc_item = u.inc_item;
@@ -445,8 +447,10 @@ __global__ __launch_bounds__(PCGRL_BLOCK) void k_update_block(PcgrlParams P, Dev
         const int cnt = __popcll(__ballot(act));
         if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(B.async_stats + 8 + 8 * (blockIdx.x & 15), (unsigned long long)cnt);
         if (pv == 2) { rst = true; B.pending[e] = 0; }
+        if (B.row.took && e < P.num_envs) B.row.took[e] = act ? 1 : 0;
         async_list_runnable(B, e);
     }
+    const int ash = B.act_i64;      // (int64 actions: the low words, pcgrl_row::actions_i64)
     if (act) {
         const int W = P.width, H = P.height, G = P.group, NPL = P.nplanes, NT = P.ntiles;
         const int2 c = reinterpret_cast<const int2*>(B.counters)[e];
@@ -459,10 +463,10 @@ __global__ __launch_bounds__(PCGRL_BLOCK) void k_update_block(PcgrlParams P, Dev
         bool bad = false;     // out-of-range actions are clamped and reported (see update_env)
         if (REP == PCGRL_REP_NARROW_MULTI) {
 #pragma unroll
-            for (int i = 0; i < 9; i++) { const int raw = actions[9 * e + i], a = clampi(raw, 0, NT); bad = bad || a != raw; vals[i] = a - 1; }
+            for (int i = 0; i < 9; i++) { const int raw = actions[(size_t)(9 * e + i) << ash], a = clampi(raw, 0, NT); bad = bad || a != raw; vals[i] = a - 1; }
         } else {
-            const int type = actions[2 * e], value = clampi(actions[2 * e + 1], 0, NT - 1);
-            bad = value != actions[2 * e + 1] || type < 0 || type > (REP == PCGRL_REP_NARROW_CAST ? 2 : 5);
+            const int type = actions[(size_t)(2 * e) << ash], raw_value = actions[(size_t)(2 * e + 1) << ash], value = clampi(raw_value, 0, NT - 1);
+            bad = value != raw_value || type < 0 || type > (REP == PCGRL_REP_NARROW_CAST ? 2 : 5);
             if (REP == PCGRL_REP_NARROW_CAST) {
                 const int t = clampi(type, 0, 2);
                 if (t == 1) vals[4] = value;

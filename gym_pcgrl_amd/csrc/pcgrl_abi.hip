@@ -120,6 +120,9 @@ struct pcgrl_env {
     int obs_incremental;       // pcgrl_bind_observation(incremental): the bound target is the library's to update in place
     const uint8_t* obs_synced; // the buffer that holds the image of the current state (written by the last step / reset), or NULL
     int obs_hold;     // inside pcgrl_rollout's loop of steps: the bound observation is written once, at the end
+    // pcgrl_bind_row: the caller's columns of a rollout row and whether `actions` are int64; row_live: inside a step that fills them
+    // (h->B.row / h->B.act_i64 are set for that step only: pcgrl_rollout and the flushes run without)
+    RowBind row; int row_on, row_i64, row_live;
     // pcgrl_step_async (kernels_search_async.h): the caller's arena, whether any step may be pending, the tick counter
     AsyncCtl async;
     int async_on, async_dirty, async_split;
@@ -366,6 +369,7 @@ int pcgrl_create(const pcgrl_config* c, pcgrl_env** out) {
     pcgrl_env* h = new pcgrl_env();
     h->bound = h->has_old = h->was_reset = h->parity = h->device = 0;
     h->profiling = 0; h->ev_used = 0; h->prof_steps = 0; h->obs_hold = 0; h->obs_incremental = 0; h->obs_synced = nullptr;
+    memset(&h->row, 0, sizeof(h->row)); h->row_on = h->row_i64 = h->row_live = 0;
     memset(&h->async, 0, sizeof(h->async)); h->async_on = h->async_dirty = 0;
     memset(&h->B, 0, sizeof(h->B));
     pcgrl_tuning_defaults(&h->tun);
@@ -780,16 +784,21 @@ static int launch_step_pme(pcgrl_env* h, const int32_t* actions, int parity, hip
     const size_t lds = (size_t)SL.total + (EPB / 16) * (size_t)(PCGRL_MT_N * 4 + ((P.width * P.height + 15) & ~15));
     const int grid = (P.num_envs + EPB - 1) / EPB;
     const int gen = (P.random_start || !h->has_old) ? 1 : 0;
-#define PCGRL_LAUNCH_STEP(REPV, MULTI, OBSV) do { \
-        { const int rca = lds_cap<k_step<PROB, REPV, MaskT, MULTI, EPB, OBSV>>(h->device, lds); if (rca) return rca; } \
-        hipLaunchKernelGGL((k_step<PROB, REPV, MaskT, MULTI, EPB, OBSV>), dim3(grid), dim3(EPB * 4), lds, st, P, h->B, actions, \
+#define PCGRL_LAUNCH_STEP(REPV, MULTI, OBSV, ROWV) do { \
+        { const int rca = lds_cap<k_step<PROB, REPV, MaskT, MULTI, EPB, OBSV, ROWV>>(h->device, lds); if (rca) return rca; } \
+        hipLaunchKernelGGL((k_step<PROB, REPV, MaskT, MULTI, EPB, OBSV, ROWV>), dim3(grid), dim3(EPB * 4), lds, st, P, h->B, actions, \
                            parity, gen, R.steps, R.action_stride, R.reward_out, R.done_out, R.info_out); } while (0)
     const bool multi = R.steps > 1 || R.reward_out || R.done_out || R.info_out;
     // a single step with a bound observation of a lean shape: the instantiation that writes the images while it runs (32-bit row masks)
     constexpr bool kObsKernel = sizeof(MaskT) == 4;
     const bool obs = kObsKernel && !multi && h->B.obs.out && h->B.obs.fused && !h->obs_at_end;
-#define PCGRL_LAUNCH_STEP3(REPV) do { if (multi) PCGRL_LAUNCH_STEP(REPV, true, false); else if (obs) PCGRL_LAUNCH_STEP(REPV, false, kObsKernel); \
-                                      else PCGRL_LAUNCH_STEP(REPV, false, false); } while (0)
+    // a step that fills a rollout row (pcgrl_bind_row; never the tape form): the row-writing instantiation
+    const bool row = h->row_live != 0;
+#define PCGRL_LAUNCH_STEP3(REPV) do { if (multi) PCGRL_LAUNCH_STEP(REPV, true, false, false); \
+                                      else if (obs && row) PCGRL_LAUNCH_STEP(REPV, false, kObsKernel, true); \
+                                      else if (obs) PCGRL_LAUNCH_STEP(REPV, false, kObsKernel, false); \
+                                      else if (row) PCGRL_LAUNCH_STEP(REPV, false, false, true); \
+                                      else PCGRL_LAUNCH_STEP(REPV, false, false, false); } while (0)
     switch (P.rep) {
         case PCGRL_REP_NARROW: PCGRL_LAUNCH_STEP3(PCGRL_REP_NARROW); break;
         case PCGRL_REP_WIDE: PCGRL_LAUNCH_STEP3(PCGRL_REP_WIDE); break;
@@ -1127,6 +1136,35 @@ static int step_one(pcgrl_env* h, const int32_t* actions, void* stream, bool* us
     return PCGRL_OK;
 }
 
+// ---- pcgrl_bind_row: the step fills the caller's columns of a rollout row --------------------------
+int pcgrl_bind_row(pcgrl_env* h, const pcgrl_row* r) {
+    if (!h || !h->bound) return PCGRL_ESTATE;
+    if (!r) { memset(&h->row, 0, sizeof(h->row)); h->row_on = h->row_i64 = 0; return PCGRL_OK; }
+    if ((r->ep_return || r->ep_length) && !h->B.last_return) return PCGRL_ESTATE;      // pcgrl_bind_episode_stats first
+    h->row = RowBind{r->actions_out, r->reward, r->done, r->start_in, r->start_out, r->ep_return, r->ep_length, r->took, r->fresh};
+    h->row_i64 = r->actions_i64 ? 1 : 0;
+    h->row_on = 1;
+    return PCGRL_OK;
+}
+// What a step with a bound row is handed: src / n = the action values of the row's `actions` column (pcgrl_step_flat: the flat
+// indices, not the decoded triples), src_i64 / step_i64: whether they, and the step's `actions` argument, are int64.
+struct RowCall { bool on; const int32_t* src; int n; int src_i64, step_i64; };
+static void row_devbufs(pcgrl_env* h, bool on, int step_i64) {      // (for the launches of one step, like async_devbufs)
+    if (on) { h->B.row = h->row; h->B.act_i64 = step_i64; }
+    else { memset(&h->B.row, 0, sizeof(h->B.row)); h->B.act_i64 = 0; }
+    h->row_live = on ? 1 : 0;
+}
+// the columns behind a step whose kernels do not write them (every pipeline but k_step): one small launch, the last of the step
+static int launch_row(pcgrl_env* h, const uint8_t* pending, const RowCall& rc_, hipStream_t st) {
+    const RowBind& R = h->row;
+    if (!R.actions_out && !R.reward && !R.done && !R.start_out && !R.ep_return && !R.ep_length && !R.took && !R.fresh) return PCGRL_OK;   // (int64 actions only)
+    if ((R.ep_return || R.ep_length) && !h->B.last_return) return PCGRL_ESTATE;
+    const int n = h->P.num_envs, nt = rc_.n > n ? rc_.n : n;
+    hipLaunchKernelGGL(k_row, dim3((nt + 255) / 256), dim3(256), 0, st, h->B, h->row, pending, rc_.src, rc_.n, rc_.src_i64, n);
+    HIPCHK(hipGetLastError());
+    return PCGRL_OK;
+}
+
 // ---- pcgrl_step_async (kernels_search_async.h) ------------------------------------------------
 static bool async_applies(const pcgrl_config* c) {
     return solver_prob(c->prob) && c->prob != PCGRL_SMB && !big_search(c) && !big_map(c) && c->solver_power <= SOK_LDS_POWER;
@@ -1236,9 +1274,13 @@ int pcgrl_step_async(pcgrl_env* h, const int32_t* actions, int32_t pop_budget, v
     const int par = h->parity;
     const bool ar = h->P.auto_reset != 0;
     int rc;
+    const RowCall row = {h->row_on != 0, actions, h->cfg.num_envs * action_width(h->cfg.rep), h->row_i64, h->row_i64};
+    if (row.on && (h->row.ep_return || h->row.ep_length) && !h->B.last_return) return PCGRL_ESTATE;
     HIPCHK(hipMemsetAsync(h->B.sok_sync, 0, 8 * sizeof(int32_t), st));       // the search launches' tickets, the counts of runnable slots and of handed-over jobs
     async_devbufs(h, true);
+    if (row.on) row_devbufs(h, true, row.step_i64);      // (the update kernel reads the actions and writes `took`: who acts, before the tick changes it)
     rc = launch_update(h, actions, par, st);        // (also lists the runnable slots)
+    if (row.on) row_devbufs(h, false, 0);
     async_devbufs(h, false);
     if (rc) return rc;
     if ((rc = launch_stats(h, WL_CHG, par, MODE_STEP, -1, 0, st))) return rc;
@@ -1247,6 +1289,7 @@ int pcgrl_step_async(pcgrl_env* h, const int32_t* actions, int32_t pop_budget, v
     h->parity ^= 1;
     h->async_dirty = 1;
     if (h->B.obs.out) { h->B.obs.delta = 0; if ((rc = launch_obs(h, h->B.obs, st))) return rc; }
+    if (row.on) return launch_row(h, h->async.pending, row, st);       // the row from the persistent buffers, at the end of the tick
     return PCGRL_OK;
 }
 
@@ -1263,21 +1306,30 @@ int pcgrl_reset(pcgrl_env* h, void* stream) {
     return PCGRL_OK;
 }
 
-int pcgrl_step(pcgrl_env* h, const int32_t* actions, void* stream) {
+static int step_impl(pcgrl_env* h, const int32_t* actions, void* stream, const RowCall& row) {
     if (!h || !h->bound || !h->was_reset) return PCGRL_ESTATE;
     if (!actions) return PCGRL_EINVAL;
     if (h->async_dirty) { const int rf = pcgrl_async_flush(h, stream); if (rf) return rf; }
+    if (row.on && (h->row.ep_return || h->row.ep_length) && !h->B.last_return) return PCGRL_ESTATE;
     DeviceGuard guard(h->device);
     bool used_lists = true;
     h->B.obs.delta = (h->B.obs.out && h->B.obs.fused && h->obs_incremental && !h->obs_hold && h->obs_synced == h->B.obs.out) ? 1 : 0;
+    if (row.on) row_devbufs(h, true, row.step_i64);
     int rc = step_one(h, actions, stream, &used_lists);
+    if (row.on) row_devbufs(h, false, 0);
     if (rc) return rc;
     if (h->B.obs.out && !h->obs_hold) h->obs_synced = h->B.obs.out;      // (every path below leaves the image of the new state there)
     if (used_lists) h->parity ^= 1;
     if (h->profiling) h->prof_steps++;
     // the wrapped observation: the fused step kernel wrote it; every other pipeline gets one more launch
     if ((used_lists || !h->B.obs.fused) && h->B.obs.out && !h->obs_hold && (rc = launch_obs(h, h->B.obs, (hipStream_t)stream))) return rc;
+    if (row.on && used_lists) return launch_row(h, nullptr, row, (hipStream_t)stream);      // (the fused kernel wrote the row itself)
     return PCGRL_OK;
+}
+int pcgrl_step(pcgrl_env* h, const int32_t* actions, void* stream) {
+    if (!h) return PCGRL_ESTATE;
+    const RowCall row = {h->row_on != 0, actions, h->cfg.num_envs * action_width(h->cfg.rep), h->row_i64, h->row_i64};
+    return step_impl(h, actions, stream, row);
 }
 
 // pcgrl_step on `count` handles (the shards of one batch: one per GPU of a node, or several on one GPU) in ONE call: step k is issued
@@ -1340,17 +1392,21 @@ int pcgrl_selftest_step_pool(int32_t count, int32_t calls, int32_t fail_at, int3
 
 // ActionMap.step + PcgrlEnv.step: where the fused step kernel applies the flat indices are decoded by its update wavefronts (one launch
 // less: the decode kernel was 4-5 us of a 35 us step with the image); elsewhere k_action_map fills xyv and the step takes that.
+static int action_map_impl(pcgrl_env* h, const int32_t* flat, int32_t* xyv, void* stream, int ash);      // (ash = 1: int64 indices, the low words)
 int pcgrl_step_flat(pcgrl_env* h, const int32_t* flat, int32_t* xyv, void* stream) {
     if (!h || !h->bound || !h->was_reset) return PCGRL_ESTATE;
     if (!flat || !xyv || h->cfg.rep != PCGRL_REP_WIDE) return PCGRL_EINVAL;
+    // (a bound row: its `actions` column takes the flat indices, int64 where the caller says so; the decoded triples are int32)
+    RowCall row = {h->row_on != 0, flat, h->cfg.num_envs, h->row_i64, h->row_i64};
     if (fused_step_applies(h, false)) {
         h->B.flat = flat;
-        const int rc = pcgrl_step(h, xyv, stream);        // (xyv is not read: the action segment of the kernel's prefetch is off)
+        const int rc = step_impl(h, xyv, stream, row);        // (xyv is not read: the action segment of the kernel's prefetch is off)
         h->B.flat = nullptr;
         return rc;
     }
-    const int rc = pcgrl_action_map(h, flat, xyv, stream);
-    return rc ? rc : pcgrl_step(h, xyv, stream);
+    const int rc = action_map_impl(h, flat, xyv, stream, row.on ? row.src_i64 : 0);
+    row.step_i64 = 0;
+    return rc ? rc : step_impl(h, xyv, stream, row);
 }
 
 // `steps` consecutive pcgrl_step calls on a tape of actions.  Where the fused step kernel applies this is ONE launch: a block
@@ -1388,7 +1444,7 @@ int pcgrl_rollout(pcgrl_env* h, const int32_t* actions, int32_t steps, double* r
         if (reward_out) h->B.reward = reward_out + (size_t)t * n;
         if (done_out) h->B.done = done_out + (size_t)t * n;
         if (info_out) h->B.info = info_out + (size_t)t * n * 10;
-        rc = pcgrl_step(h, actions + (size_t)t * stride, stream);
+        rc = step_impl(h, actions + (size_t)t * stride, stream, RowCall{false, nullptr, 0, 0, 0});     // (no row: the tape has its own outputs)
     }
     h->B.reward = reward0; h->B.done = done0; h->B.info = info0;
     h->obs_hold = 0;
@@ -1472,12 +1528,13 @@ int pcgrl_bind_observation(pcgrl_env* h, uint8_t* out, int32_t out_h, int32_t ou
     return PCGRL_OK;
 }
 
-int pcgrl_action_map(pcgrl_env* h, const int32_t* flat, int32_t* xyv, void* stream) {
+int pcgrl_action_map(pcgrl_env* h, const int32_t* flat, int32_t* xyv, void* stream) { return action_map_impl(h, flat, xyv, stream, 0); }
+static int action_map_impl(pcgrl_env* h, const int32_t* flat, int32_t* xyv, void* stream, int ash) {
     if (!h || !h->bound) return PCGRL_ESTATE;
     if (!flat || !xyv) return PCGRL_EINVAL;
     DeviceGuard guard(h->device);
     const int n = h->P.num_envs;
-    hipLaunchKernelGGL(k_action_map, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, flat, xyv, n, h->P.width, h->P.height, h->P.ntiles, h->B.status);
+    hipLaunchKernelGGL(k_action_map, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, flat, xyv, n, h->P.width, h->P.height, h->P.ntiles, h->B.status, ash);
     HIPCHK(hipGetLastError());
     return PCGRL_OK;
 }

@@ -82,6 +82,10 @@ struct LocalLists;
 struct ObsSpec { uint8_t* out; int32_t oh, ow, depth, centered, pad;
                  int32_t fused,        // k_step writes the image itself (a shape with a lean routine, kernels_obs.h); else k_obs follows the step
                          delta; };     // ... and may update it in place: `out` holds the image of the state the step starts from
+// The caller's columns of a rollout row (pcgrl_bind_row): the step writes them itself -- k_step's row-writing instantiation from its
+// LDS copy, every other pipeline by k_row behind the step.  A null pointer: column not wanted.
+struct RowBind { int64_t* actions_out; double* reward; uint8_t* done; const uint8_t* start_in; uint8_t* start_out;
+                 double* ep_return; int32_t* ep_length; uint8_t* took; uint8_t* fresh; };
 struct DevBufs {
     uint8_t* map; uint8_t* old_map; uint16_t* heat; uint8_t* pos; void* planes;
     void* champ;                     // mask [N][16]: rows of the champion component (binary, 16-row maps); stats[e][2] = it is valid
@@ -134,6 +138,10 @@ struct DevBufs {
     // runnable slots (async_run[0 .. *async_run_n)) for the search kernel that follows
     const uint8_t* async_slots; size_t async_slot_bytes; int32_t async_nslots; int32_t* async_run; int32_t* async_run_n;
     int32_t heat32;                  // no auto-reset: `heat` holds one 32-bit count per cell (pcgrl_query_layout), else 16-bit ones
+    // pcgrl_bind_row, set only inside pcgrl_step / pcgrl_step_flat / pcgrl_step_async (last in the struct: the kernels that write no
+    // row never load them).  act_i64 = 1: the step's `actions` (and `flat`) hold int64 values, the low word is the action -- the
+    // read sites index 32-bit words shifted left by it.
+    RowBind row; int32_t act_i64;
 };
 #define PCGRL_FIFO_N 8
 

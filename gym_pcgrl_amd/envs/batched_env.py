@@ -89,6 +89,8 @@ class BatchedPcgrlEnv:
         self._obs_spec = None          # bind_observation(): (out tensor, h, w, centered, pad, onehot)
         self._async = None             # enable_async(): arena tensor + views (pending, counters)
         self._async_nslots = 0
+        self._row = None               # bind_rollout_row(): (column pointers in _lib.ROW_FIELDS order, the tensors kept alive)
+        self._row_applied = None       # what the handle was last told (pcgrl_bind_row): (column pointers, actions are int64)
         self._update_spaces()
         self.seed(seed)
 
@@ -193,6 +195,7 @@ class BatchedPcgrlEnv:
         if self._episode is not None:      # rebinding after a reallocation keeps the running episodes' sums
             self._bind_episode_stats()
         self._apply_observation()
+        self._row_applied = None       # (a new handle: the row binding is applied again by the next step)
         self._async = None
         if self._async_nslots:
             self._bind_async()
@@ -306,15 +309,98 @@ class BatchedPcgrlEnv:
         actions = actions.reshape(self.num_envs, aw) if aw > 1 else actions.reshape(self.num_envs)
         return actions.contiguous()
 
+    def _pass_actions(self, actions, width=None):
+        """The action tensor the library is handed: a contiguous int64 or int32 device tensor of the right size goes through as it
+        is (pcgrl_row::actions_i64: the kernels read the low words of int64 values -- what .to(int32) keeps -- so a policy's argmax
+        needs no conversion kernel); anything else is converted by _as_actions as ever.  Tells the handle which of the two it is."""
+        torch = self._torch
+        aw = self._rep.action_width() if width is None else width
+        if not (torch.is_tensor(actions) and actions.device == self.device and actions.dtype in (torch.int64, torch.int32)
+                and actions.numel() == self.num_envs * aw and actions.is_contiguous()):
+            actions = self._as_actions(actions) if width is None else \
+                torch.as_tensor(actions).to(device=self.device, dtype=torch.int32).reshape(self.num_envs * aw).contiguous()
+        self._apply_row(actions.dtype == torch.int64)
+        return actions
+
+    # ---- the rest of a rollout row, written by the step itself (pcgrl_bind_row)
+    _ROW_DTYPES = dict(actions_out=("int64",), reward=("float64",), done=("bool", "uint8"), start_in=("bool", "uint8"), start_out=("bool", "uint8"),
+                       ep_return=("float64",), ep_length=("int32",), took=("bool", "uint8"), fresh=("bool", "uint8"))
+
+    def bind_rollout_row(self, **columns):
+        """From the next step() / step_flat() / tick() on, the step writes these columns of a rollout row itself (include/pcgrl_hip.h
+        pcgrl_row; where the step is one fused kernel: no extra launch, elsewhere one small kernel behind it): actions_out int64
+        [N] / [N, k] (the actions it was handed), reward float64 [N], done / start_out / took / fresh bool or uint8 [N], start_in
+        (read by tick() only), ep_return float64 [N] and ep_length int32 [N] (the finished episodes' return / length, NaN / 0
+        elsewhere: need enable_episode_stats()).  Contiguous tensors on this device, kept alive here; call again with other
+        tensors for the next row (host work only).  The live views step() returns are written as ever."""
+        torch = self._torch
+        row = {}
+        for name, t in columns.items():
+            if name not in self._ROW_DTYPES:
+                raise TypeError("bind_rollout_row(): unknown column %r (known: %s)" % (name, ", ".join(_lib.ROW_FIELDS)))
+            if t is None:
+                continue
+            aw = self._rep.action_width()
+            shapes = [(self.num_envs,)] if (name != "actions_out" or aw == 1) else [(self.num_envs, aw)]
+            if name == "actions_out" and self._rep.name == "wide":
+                shapes.append((self.num_envs,))          # step_flat(): the flat indices
+            want = "expected a contiguous %s tensor of shape %s on %s" % (" / ".join(self._ROW_DTYPES[name]), " or ".join(str(x) for x in shapes), self.device)
+            if not torch.is_tensor(t) or str(t.dtype).replace("torch.", "") not in self._ROW_DTYPES[name]:
+                raise ValueError("bind_rollout_row(%s=...): wrong dtype %s: %s" % (name, getattr(t, "dtype", type(t).__name__), want))
+            if tuple(t.shape) not in shapes:
+                raise ValueError("bind_rollout_row(%s=...): wrong shape %s: %s" % (name, tuple(t.shape), want))
+            if not t.is_contiguous():
+                raise ValueError("bind_rollout_row(%s=...): not contiguous: %s" % (name, want))
+            if t.device != self.device:
+                raise ValueError("bind_rollout_row(%s=...): wrong device %s: %s" % (name, t.device, want))
+            row[name] = t
+        if ("ep_return" in row or "ep_length" in row) and self._episode is None:
+            raise RuntimeError("bind_rollout_row(ep_return / ep_length): call enable_episode_stats() first")
+        self._set_row(tuple(row[n].data_ptr() if n in row else None for n in _lib.ROW_FIELDS) if row else None, row)
+
+    def _set_row(self, ptrs, keep):
+        """bind_rollout_row() without the checks: `ptrs` in _lib.ROW_FIELDS order (None: column not wanted).  RolloutCollector checks
+        its [T, N] columns once and walks down them with this."""
+        self._row = (ptrs, keep) if ptrs is not None else None
+
+    def unbind_rollout_row(self):
+        """No row from now on; the handle is told at once, so that nothing that steps it by another way (MultiGpuPcgrlEnv's one-call
+        step) finds a row, or the int64 reading of `actions`, still in place."""
+        self._row = None
+        self._row_rest()
+
+    def _row_plain(self):
+        """The handle takes int32 actions and writes no row: what a caller that hands it raw pointers (pcgrl_step_multi) relies on."""
+        return self._row is None and self._row_applied in (None, (None, False))
+
+    def _row_rest(self):
+        """Behind every step: without a bound row the handle goes back to plain int32 actions -- the int64 reading of `actions` holds
+        for the call that passed an int64 tensor, never for a later one."""
+        if self._row is None and self._handle is not None and self._row_applied not in (None, (None, False)):
+            self._apply_row(False)
+
+    def _apply_row(self, i64):
+        """Tell the handle the row binding in effect for the step that follows (a host call, and only when something changed)."""
+        key = (self._row[0] if self._row else None, bool(i64))
+        if key == self._row_applied:
+            return
+        if key[0] is None and not i64:
+            _lib.check(self._lib.pcgrl_bind_row(self._handle, None), "pcgrl_bind_row")
+        else:
+            r = _lib.Row(*(key[0] or (None,) * len(_lib.ROW_FIELDS)), 1 if i64 else 0)
+            _lib.check(self._lib.pcgrl_bind_row(self._handle, C.byref(r)), "pcgrl_bind_row")
+        self._row_applied = key
+
     def step(self, actions):
         """pcgrl_env.py:129-150 for every environment.  actions: int [N] (narrow/turtle) or [N,3]
         (wide: x, y, tile).  Returns (obs, reward f64[N], done bool[N], InfoBatch); tensors are views
         of the live state and are overwritten by the next step."""
         if self._needs_reset:
             raise RuntimeError("reset() must be called before step()" + (": " + self._reset_reason if getattr(self, "_reset_reason", None) else ""))
-        a = self._as_actions(actions)
+        a = self._pass_actions(actions)
         self._last_actions = a   # keep the buffer alive until the launches are done
         _lib.check(self._lib.pcgrl_step(self._handle, C.c_void_p(a.data_ptr()), self._stream()), "pcgrl_step")
+        self._row_rest()
         if self.strict_actions:
             self.check_status()
         b = self._bufs
@@ -323,12 +409,14 @@ class BatchedPcgrlEnv:
         return self._obs(), b["reward"], b["done"].view(self._torch.bool), info
 
     def step_flat(self, flat, xyv):
-        """ActionMap.step + step() for the wide representation in one call of the library (pcgrl_step_flat): `flat` int32 [N] device
+        """ActionMap.step + step() for the wide representation in one call of the library (pcgrl_step_flat): `flat` int32 or int64 [N] device
         tensor of indices into (H, W, tiles), `xyv` int32 [N, 3] device scratch.  Same return value as step()."""
         if self._needs_reset:
             raise RuntimeError("reset() must be called before step()")
+        flat = self._pass_actions(flat, width=1)
         self._last_actions = (flat, xyv)
         _lib.check(self._lib.pcgrl_step_flat(self._handle, C.c_void_p(flat.data_ptr()), C.c_void_p(xyv.data_ptr()), self._stream()), "pcgrl_step_flat")
+        self._row_rest()
         if self.strict_actions:
             self.check_status()
         b = self._bufs
@@ -476,9 +564,10 @@ class BatchedPcgrlEnv:
                 if getattr(self, "_never_pending", None) is None:
                     self._never_pending = self._torch.zeros(self.num_envs, dtype=self._torch.uint8, device=self.device)
                 return o, r, d, i, self._never_pending
-        a = self._as_actions(actions)
+        a = self._pass_actions(actions)
         self._last_actions = a
         _lib.check(self._lib.pcgrl_step_async(self._handle, C.c_void_p(a.data_ptr()), int(pop_budget), self._stream()), "pcgrl_step_async")
+        self._row_rest()
         if self.strict_actions:
             self.check_status()
         b = self._bufs

@@ -90,6 +90,13 @@ def side_by_side_streams(torch, device, k, tries=None):
     return chosen
 
 
+def _row_plain(sh):
+    """The shard's handle takes raw int32 action pointers and writes no rollout row (BatchedPcgrlEnv._row_plain; a shard object
+    without the notion has neither)."""
+    f = getattr(sh, "_row_plain", None)
+    return f is None or f()
+
+
 class MultiGpuPcgrlEnv:
     def __init__(self, prob="binary", rep="narrow", num_envs=1, devices=None, seed=0, auto_reset=True, gather="list", sync_streams=True):
         """gather: what reset()/step() return per output -- "list": a ShardedTensor of live per-device views (zero copy, no
@@ -254,10 +261,10 @@ class MultiGpuPcgrlEnv:
 
     def _multi_valid(self, M):
         """The cached handles are the shards' current ones and no shard asks for the per-shard path (strict actions, a pending
-        reset): three attribute reads per shard and call, against a use-after-free of a destroyed handle."""
+        reset, a bound rollout row -- the one call hands the handles raw int32 pointers): a few attribute reads per shard and call, against a use-after-free of a destroyed handle."""
         for sh, hv in zip(self.shards, M["hvals"]):
             h = sh._handle
-            if h is None or h.value != hv or sh.strict_actions or sh._needs_reset:
+            if h is None or h.value != hv or sh.strict_actions or sh._needs_reset or not _row_plain(sh):
                 return False
         return True
 
@@ -270,7 +277,7 @@ class MultiGpuPcgrlEnv:
         M = self._multi
         if M is not None and not self._multi_valid(M):
             M = self._multi = None             # (a shard was closed / re-allocated / switched to strict actions behind the cache's back)
-        if M is None and self.gather == "list" and not any(sh.strict_actions or sh._needs_reset or sh._handle is None for sh in self.shards):
+        if M is None and self.gather == "list" and not any(sh.strict_actions or sh._needs_reset or sh._handle is None or not _row_plain(sh) for sh in self.shards):
             self._prepare_multi()              # (dropped again by reset() / adjust_param(): the shards are then looked at anew)
             M = self._multi
         if M is not None:

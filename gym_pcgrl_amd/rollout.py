@@ -4,7 +4,10 @@ observations, actions, rewards and episode starts).
 
 Everything stays on the GPU: the step writes the wrapped observation of step t+1 straight into row t+1 of the preallocated
 `[T, N, ...]` storage (the observation target of the environment is moved from row to row: no copy of the image, which is
-the bulk of a rollout's bytes); rewards / dones are small and copied from the environment's own tensors.
+the bulk of a rollout's bytes); the small columns of row t -- actions, rewards, dones, episode starts, the Monitor's episode
+returns / lengths, took / fresh -- are written by the step too (BatchedPcgrlEnv.bind_rollout_row, include/pcgrl_hip.h pcgrl_bind_row),
+so that a row is the policy's kernels plus the step's launch; `kernel_rows=False` keeps the loop that copies them from the
+environment's own tensors with a handful of small torch kernels per row.
 No policy or optimiser lives here (out of scope): `policy(obs) -> actions` is any callable on device
 tensors.
 """
@@ -29,6 +32,10 @@ class RolloutBuffer:
         # collector writes reward 0 and done False.  Lockstep: all true.
         self.took = torch.ones((n_steps, num_envs), dtype=torch.bool, device=device)
         self.fresh = torch.ones((n_steps, num_envs), dtype=torch.bool, device=device)
+        # Monitor columns (a vec_env with monitor=True, rows written by the step): the return / length of the episode that ended in
+        # (t, e), NaN / 0 elsewhere -- RolloutCollector.episode_returns / episode_lengths are their rows
+        self.ep_returns = torch.full((n_steps, num_envs), float("nan"), dtype=torch.float64, device=device)
+        self.ep_lengths = z((n_steps, num_envs), torch.int32)
 
     def as_dict(self):
         return OrderedDict(obs=self.obs, actions=self.actions, rewards=self.rewards, dones=self.dones,
@@ -40,9 +47,12 @@ class RolloutCollector:
 
     collect() continues from where the previous call stopped (like a SB runner: the environment is only reset
     once), so consecutive rollouts tile the same trajectories.  With `vec_env.monitor` the finished episodes'
-    returns/lengths accumulate in `episode_returns` / `episode_lengths` (device tensors, no host sync)."""
+    returns/lengths accumulate in `episode_returns` / `episode_lengths` (device tensors, no host sync).
 
-    def __init__(self, vec_env, n_steps):
+    kernel_rows: None = the step writes the small columns of a row itself where the wrapped environment offers it
+    (BatchedPcgrlEnv.bind_rollout_row), True = require that (ValueError otherwise), False = the loop of small copies."""
+
+    def __init__(self, vec_env, n_steps, kernel_rows=None):
         self.env = vec_env
         self.torch = vec_env.env.pcgrl_env._torch
         dev = vec_env.env.pcgrl_env.device
@@ -58,6 +68,38 @@ class RolloutCollector:
         self._start = self.torch.ones(vec_env.num_envs, dtype=self.torch.bool, device=dev)
         self.episode_returns, self.episode_lengths = [], []      # per step, the last `keep_steps` steps (default: one rollout)
         self.keep_steps = int(n_steps)
+        self.kernel_rows = self._setup_kernel_rows(kernel_rows)
+
+    def _setup_kernel_rows(self, kernel_rows):
+        """Whether the step writes the rows; if so, the column pointers of every row (the buffer never moves: binding row t is a
+        tuple handed to the environment, no tensor is touched)."""
+        if kernel_rows is not None and not kernel_rows:
+            return False
+        e, b = self.env.env.pcgrl_env, self.buffer
+        if not hasattr(e, "bind_rollout_row"):
+            if kernel_rows:
+                raise ValueError("kernel_rows=True: the wrapped environment has no bind_rollout_row()")
+            return False
+        T = b.n_steps
+        mon = bool(self.env.monitor)
+        nxt_start = lambda t: b.episode_starts[t + 1] if t + 1 < T else self._start      # the last row's goes to the carry tensor
+        cols = lambda t: dict(actions_out=b.actions[t], reward=b.rewards[t], done=b.dones[t], start_in=b.episode_starts[t], start_out=nxt_start(t),
+                              ep_return=b.ep_returns[t] if mon else None, ep_length=b.ep_lengths[t] if mon else None, took=b.took[t], fresh=b.fresh[t])
+        try:
+            e.bind_rollout_row(**cols(0))            # the checks (dtype, shape, device), once
+        except (ValueError, RuntimeError):
+            if kernel_rows:
+                raise
+            return False
+        finally:
+            e.unbind_rollout_row()
+        from ._lib import ROW_FIELDS
+        self._row_ptrs = []
+        for t in range(T):
+            c = cols(t)
+            self._row_ptrs.append(tuple(c[n].data_ptr() if c[n] is not None else None for n in ROW_FIELDS))
+        self._row_ptrs_noact = [(None,) + p[1:] for p in self._row_ptrs]
+        return True
 
     def collect(self, policy, pop_budget=None):
         """pop_budget: collect with asynchronous ticks (BatchedPcgrlEnv.tick; sokoban / mdungeon / ddave) -- a row of the buffer is then a
@@ -86,9 +128,50 @@ class RolloutCollector:
         else:
             b.obs[0].copy_(b.last_obs)                    # one copy per rollout: where the previous one stopped
             self._obs = b.obs[0]
+        if self.kernel_rows:
+            self.env.env.pcgrl_env.unbind_rollout_row()   # (a rollout that was given up half way left its row bound)
+            b.episode_starts[0].copy_(self._start)        # one copy per rollout too: the steps write the rows below it
+
+    def _step_kernel_rows(self, t, policy, pop_budget):
+        """Row t where the step writes it: bind the row and the next image (host work only), the policy, the step."""
+        b = self.buffer
+        w = self.env.env
+        e = w.pcgrl_env
+        asynchronous = pop_budget is not None
+        # (a tick of the ActionMap wrapper hands the environment the decoded [N, 3] triples: the flat indices are copied as before)
+        own_actions = asynchronous and e._rep.name == "wide"
+        e._set_row((self._row_ptrs_noact if own_actions else self._row_ptrs)[t], (b, self._start))
+        nxt = b.obs[t + 1] if t + 1 < b.n_steps else b.last_obs
+        try:
+            if self.direct:
+                w.set_observation_target(nxt)
+            actions = policy(self._obs)
+            if own_actions:
+                b.actions[t].copy_(actions)
+            if asynchronous:
+                self._obs = w.tick(actions, pop_budget=pop_budget)[0]
+            else:
+                self._obs = w.step(actions)[0]
+        except BaseException:
+            e.unbind_rollout_row()                        # a policy or a step that raised: no later step writes into this row
+            raise
+        if not self.direct:
+            nxt.copy_(self._obs)
+            self._obs = nxt
+        if t + 1 == b.n_steps:
+            e.unbind_rollout_row()                        # a step outside the collector writes into no row
+        if self.env.monitor:
+            # (row views while the window is one rollout: a row is overwritten exactly when its entry falls out of the window)
+            own = self.keep_steps != b.n_steps
+            self.episode_returns.append(b.ep_returns[t].clone() if own else b.ep_returns[t])
+            self.episode_lengths.append(b.ep_lengths[t].clone() if own else b.ep_lengths[t])
+            if len(self.episode_returns) > self.keep_steps:
+                del self.episode_returns[0], self.episode_lengths[0]
 
     def step(self, t, policy, pop_budget=None):
         """Row t of the rollout: the policy's actions for obs[t], one step (or tick) of the environment, its outcome."""
+        if self.kernel_rows:
+            return self._step_kernel_rows(t, policy, pop_budget)
         torch, b = self.torch, self.buffer
         asynchronous = pop_budget is not None
         w = self.env.env
@@ -142,9 +225,9 @@ class DoubleBufferedCollector:
     return value: the sub-batches' RolloutBuffer's ([T, N / K, ...] each; concatenate along axis 1 where one tensor is wanted).
     `policy(obs)` is called per sub-batch, on that sub-batch's stream."""
 
-    def __init__(self, vec_envs, n_steps):
+    def __init__(self, vec_envs, n_steps, kernel_rows=None):
         from .node import side_by_side_streams
-        self.parts = [RolloutCollector(v, n_steps) for v in vec_envs]
+        self.parts = [RolloutCollector(v, n_steps, kernel_rows) for v in vec_envs]
         self.torch = self.parts[0].torch
         self.device = self.parts[0].buffer.obs.device
         for p in self.parts:

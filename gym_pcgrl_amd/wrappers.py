@@ -121,11 +121,11 @@ class ActionMapImagePCGRLWrapper(_ImageWrapper):
     def step(self, actions):
         e = self.pcgrl_env
         torch = e._torch
-        a = actions if torch.is_tensor(actions) else torch.as_tensor(actions)
-        a = a.to(device=e.device, dtype=torch.int32).reshape(self.num_envs).contiguous()
         if self._xyv is None:
             self._xyv = torch.empty((self.num_envs, 3), dtype=torch.int32, device=e.device)
-        _, reward, done, info = e.step_flat(a, self._xyv)          # decode + step: one call, one launch where the step is fused
+        # decode + step: one call, one launch where the step is fused (a contiguous int64 / int32 device tensor goes through as it is,
+        # anything else is converted to int32 [N]: BatchedPcgrlEnv._pass_actions)
+        _, reward, done, info = e.step_flat(actions, self._xyv)
         return self._obs, reward, done, info
 
     def tick(self, actions, pop_budget=64):

@@ -38,7 +38,9 @@ extern "C" {
  * 7: + the smb problem: pcgrl_config grew (min_empty, min_enemies, min_jumps; `reserved_` is gone); pcgrl_status reports
  *    clamped actions.  10: + pcgrl_tuning / pcgrl_set_tuning (the library reads no environment variables any more); pcgrl_config
  *    grew (prob_width, prob_height); maps up to 255 x 255, search levels up to 16 384 bordered cells, solver_power up to 1 000 000.
- * 15: without auto_reset the heat map holds 32-bit counts (an episode goes on past done); max_changes beyond 65 535 there. */
+ * 15: without auto_reset the heat map holds 32-bit counts (an episode goes on past done); max_changes beyond 65 535 there.
+ *     Still 15: + pcgrl_row / pcgrl_bind_row -- purely additive (one struct, one entry point; no existing struct or signature
+ *     changed), so the number stays; a caller detects the feature by the symbol pcgrl_bind_row. */
 #define PCGRL_ABI_VERSION 15
 #define PCGRL_OK 0
 #define PCGRL_EINVAL (-1)   /* bad argument / unsupported configuration */
@@ -220,6 +222,31 @@ int pcgrl_observe(pcgrl_env* env, uint8_t* out, int32_t out_h, int32_t out_w, in
  * another buffer, or incremental = 0, always gives full images. */
 int pcgrl_bind_observation(pcgrl_env* env, uint8_t* out, int32_t out_h, int32_t out_w, int32_t centered,
                            int32_t pad_value, int32_t onehot, int32_t incremental);
+/* The rest of a rollout row written by the step itself (the image goes through pcgrl_bind_observation): what a collector around
+ * the reference's VecEnv (utils.py:60-71) and its Monitor (utils.py:13-29) copies out of every step -- actions, reward, done, the
+ * episode-start flag of the next row, the finished episodes' return / length -- lands in the caller's columns of row t, and the
+ * `actions` argument of the step may be the policy's int64 tensor as it is.  Where the step is one fused kernel (binary, zelda;
+ * maps of at most 16 rows, row masks of 32 bits) that kernel writes the columns: no extra launch; elsewhere one small kernel
+ * follows the step (the tick).  All pointers DEVICE, caller-owned; any pointer may be NULL = column not wanted. */
+typedef struct pcgrl_row {
+    int64_t* actions_out;           /* i64 [N(,k)]  the actions handed to the step, widened (all N, also those a pending environment ignores) */
+    double*  reward;                /* f64 [N]      the step's reward (asynchronous: 0.0 where not fresh) */
+    uint8_t* done;                  /* u8  [N]      0 / 1 (asynchronous: 0 where not fresh) */
+    const uint8_t* start_in;        /* u8  [N]      episode-start flags of this row (read by the asynchronous form only) */
+    uint8_t* start_out;             /* u8  [N]      episode-start flags of the next row: done (asynchronous: start_in where not fresh) */
+    double*  ep_return;             /* f64 [N]      last_return where done, else the quiet NaN 0x7FF8000000000000 */
+    int32_t* ep_length;             /* i32 [N]      last_length where done, else 0  (both need pcgrl_bind_episode_stats) */
+    uint8_t* took;                  /* u8  [N]      asynchronous: pending[e] == 0 before the tick; lockstep: 1 */
+    uint8_t* fresh;                 /* u8  [N]      asynchronous: pending[e] == 0 after the tick; lockstep: 1 */
+    int32_t  actions_i64;           /* 1: the `actions` argument of pcgrl_step / pcgrl_step_flat / pcgrl_step_async points to int64 values
+                                       whose low 32-bit word is the action (what a conversion to int32 keeps) */
+} pcgrl_row;
+/* Only records the pointers (nothing is launched or written by the call); may be repeated before every step with other pointers;
+ * row = NULL switches it off (the default).  From then on pcgrl_step / pcgrl_step_flat / pcgrl_step_async fill the columns; the
+ * handle's own reward / done / info / episode-statistics buffers are written as without a binding.  pcgrl_rollout has its own
+ * outputs and ignores the binding (its tape is int32); pcgrl_reset / pcgrl_set_maps write no row.  PCGRL_ESTATE: ep_return /
+ * ep_length without bound episode statistics. */
+int pcgrl_bind_row(pcgrl_env* env, const pcgrl_row* row);
 /* ActionMap.step for the wide representation (wrappers.py:139-154): flat DEVICE i32 [N] index into
  * (H, W, tiles) -> xyv DEVICE i32 [N,3] = (x, y, tile), the action pcgrl_step takes. */
 int pcgrl_action_map(pcgrl_env* env, const int32_t* flat, int32_t* xyv, void* stream);
