@@ -15,8 +15,9 @@
 //                     cell, np.argmax = first cell of the last frontier; a component of k cells is only swept while k - 1 can
 //                     still raise the maximum (and the second sweep only while 2 * e1 can)
 //   big_bfs_dist      distance from a set to the nearest cell of another set (zelda_prob.py:98-110)
-// No incremental route, no champion cache: every change recomputes.  This is the general path, not the tuned one -- the
-// configurations BASELINE.json names all fit the row-bitboard kernels.
+// Binary maps of up to 256 per side keep the champion component per environment and answer a change that neither touches nor
+// neighbours it from the previous statistics (big_incremental; pcgrl_abi.hip champ_bytes); every other change recomputes.  This is
+// the general path, not the tuned one -- the configurations BASELINE.json names all fit the row-bitboard kernels.
 #pragma once
 
 // developer build only (tools/probe/big_prof.py: -DPCGRL_BIG_PROF): cycles of a full recomputation by phase, summed into g_tl_buf

@@ -257,7 +257,8 @@ static size_t sok_pool_nodes(int power, int prob = -1) {
     return full > small ? full : small;
 }
 static_assert(SS_SMALL_NODES >= 4 * SS_SMALL_POPS + 4, "a small-tier search pushes up to four nodes per pop");
-// rows of the champion component per environment (binary, maps of at most 16 x 32): the incremental statistics path
+// rows of the champion component per environment (binary: the row-bitboard maps, and maps beyond 64 x 64 of up to 256 per side with at
+// most 32 768 environments -- see below): the incremental statistics path
 // (smb: per map column the rows the last play-through read -- uint32 [N][W], kernels_smb.h -- for the representations that change one tile a step)
 static size_t champ_bytes(const pcgrl_config* c) {
     if (c->prob == PCGRL_SMB) return (c->rep <= PCGRL_REP_TURTLE && c->num_envs < SMB_KEEP_PLAY) ? align_up((size_t)c->num_envs * c->width * 4, 256) : 0;

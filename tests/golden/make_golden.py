@@ -930,6 +930,8 @@ TRAJS = [
     ("smb_narrowcast_16x6", "smb", "narrowcast", 4, 120, (dict(width=16, height=6), dict(change_percentage=0.5, probs={"empty": 0.45, "solid": 0.5}))),
     # round 4: maps beyond 64 x 64 (bigmap.h) -- max_changes follows Q9 (the second adjust_param call sets it)
     ("binary_narrow_100x100", "binary", "narrow", 3, 90, (dict(width=100, height=100), dict(change_percentage=0.002))),
+    # three words per row and more than 128 rows at once: the oracle pinned where tests/test_gpu_bigmap_edges.py leans on it
+    ("binary_narrow_129x130", "binary", "narrow", 3, 35, (dict(width=129, height=130), dict(change_percentage=0.0005))),
     ("binary_wide_70x65", "binary", "wide", 3, 60, (dict(width=70, height=65), dict(change_percentage=0.003))),
     ("zelda_turtle_66x20", "zelda", "turtle", 3, 120, (dict(width=66, height=20), dict(change_percentage=0.01))),
     ("binary_turtlecast_30x90", "binary", "turtlecast", 3, 80, (dict(width=30, height=90), dict(change_percentage=0.01))),

@@ -137,65 +137,103 @@ def oracle_noreset(o, actions):
                 info=np.array([[s[3][k] for k in keys] for s in steps], np.int64).reshape(len(steps), len(keys)))
 
 
-def _oracle_rollouts(prob, rep, calls, seeds, acts_by_env, auto_reset=True):
+def _oracle_rollouts(prob, rep, calls, seeds, acts_by_env, auto_reset=True, keep_start=False):
     out = []
     for seed, a in zip(seeds, acts_by_env):
         o = ol.OracleEnv(prob, rep)
         for kw in calls:
             o.adjust_param(**kw)
         o.seed(int(seed))
-        o.reset()
+        map0 = o.reset()["map"]
         out.append(o.rollout(a) if auto_reset else oracle_noreset(o, a))
+        if keep_start:
+            out[-1]["map0"] = map0
     return out
 
 
-def run_config(prob, rep, calls, E, T, seed0, rs, use_rollout, mixed=False, steps_scale=1.0, auto_reset=True, map_every=MAP_EVERY):
+def action_dims(prob, rep, w, h):
+    """The sizes of the action space of a single-cell representation, as the representations define them (narrow_rep.py:37-38,
+    turtle_rep.py:50-51, wide_rep.py:22-23) -- for drawing a tape of actions where there is no device to ask."""
+    nt = len(ol.TILES[prob])
+    return {"narrow": [nt + 1], "turtle": [nt + 4], "wide": [w, h, nt]}[rep]
+
+
+def draw_actions(dims, rs, T, E):
+    """[T, E, len(dims)] int32, drawn from `rs` the way run_config always has."""
+    if len(dims) == 1:
+        return rs.randint(0, int(dims[0]), size=(T, E, 1)).astype(np.int32)
+    return np.stack([rs.randint(0, int(k), size=(T, E)) for k in dims], -1).astype(np.int32)
+
+
+def oracle_tape(prob, rep, calls, E, T, seed0, rs, sample=None):
+    """The host half of run_config on its own: a tape of random actions for E environments and the oracle's rollouts of the
+    environments `sample` (default: all), each with the map it started from as x["map0"].  -> (acts, exp), for run_config(tape=)."""
+    o = ol.OracleEnv(prob, rep)
+    for kw in calls:
+        o.adjust_param(**kw)
+    w, h = o.width, o.height
+    acts = draw_actions(action_dims(prob, rep, w, h), rs, T, E)
+    idx = np.arange(E) if sample is None else np.asarray(sample)
+    return acts, _oracle_rollouts(prob, rep, calls, [seed0 + int(i) for i in idx], [acts[:, i] for i in idx], keep_start=True)
+
+
+def run_config(prob, rep, calls, E, T, seed0, rs, use_rollout, mixed=False, steps_scale=1.0, auto_reset=True, map_every=MAP_EVERY,
+               tuning=None, sample=None, tape=None):
     """One configuration on the GPU against the oracle.  `mixed`: the first part of the tape as one rollout of ODD length,
     the rest as single steps on the same handle (switching between the fused and the work-list pipelines).  auto_reset=False:
-    the environments step on past done, the oracle without reset().  Returns None or a string describing the first mismatch."""
+    the environments step on past done, the oracle without reset().  tuning: the library's developer switches for this handle.
+    sample: indices of the environments compared with the oracle (default: all).  tape: (acts, exp) of oracle_tape -- the actions
+    and the oracle's side made beforehand (`rs` is then not drawn from).  Returns None or a string describing the first mismatch."""
     import torch
     from gym_pcgrl_amd.envs import BatchedPcgrlEnv
     T = max(4, int(T * steps_scale))
-    env = BatchedPcgrlEnv(prob=prob, rep=rep, num_envs=E, seed=seed0, auto_reset=auto_reset)
+    env = BatchedPcgrlEnv(prob=prob, rep=rep, num_envs=E, seed=seed0, auto_reset=auto_reset, tuning=tuning)
     try:
         for kw in calls:
             env.adjust_param(**kw)
         env.reset()
         sp = env.single_action_space
-        if hasattr(sp, "n"):
-            acts = rs.randint(0, sp.n, size=(T, E, 1)).astype(np.int32)
+        dims = [sp.n] if hasattr(sp, "n") else [int(k) for k in sp.nvec]
+        idx = np.arange(E) if sample is None else np.asarray(sample)
+        if tape is None:
+            acts = draw_actions(dims, rs, T, E)
+            exp = _oracle_rollouts(prob, rep, calls, [seed0 + int(i) for i in idx], [acts[:, i] for i in idx], auto_reset)
         else:
-            acts = np.stack([rs.randint(0, int(k), size=(T, E)) for k in sp.nvec], -1).astype(np.int32)
-        exp = _oracle_rollouts(prob, rep, calls, [seed0 + i for i in range(E)], [acts[:, i] for i in range(E)], auto_reset)
+            acts, exp = tape
+            assert acts.shape == (T, E, len(dims)) and len(exp) == len(idx) and dims == action_dims(prob, rep, env._prob._width, env._prob._height), \
+                "the tape was made for another configuration"
+        sel = None if sample is None else torch.as_tensor(idx, device="cuda")
         keys = list(env._prob.info_keys) + ["iterations", "changes"]
         t_roll = 0
         obs = env._obs()
         if use_rollout or mixed:
             t_roll = T if not mixed else (T // 3) | 1
-            tape = torch.as_tensor(acts[:t_roll] if acts.shape[2] > 1 else acts[:t_roll, :, 0], device="cuda")
-            rew_t, done_t, info_t = env.rollout(tape)
-            got_info = np.stack([info_t[k].cpu().numpy() for k in keys], 1).astype(np.int64).reshape(t_roll, E, len(keys))
-            ok = np.array_equal(done_t.cpu().numpy(), np.stack([x["done"][:t_roll] for x in exp], 1)) and \
-                np.array_equal(rew_t.cpu().numpy(), np.stack([x["reward"][:t_roll] for x in exp], 1)) and \
+            tape_d = torch.as_tensor(acts[:t_roll] if acts.shape[2] > 1 else acts[:t_roll, :, 0], device="cuda")
+            rew_t, done_t, info_t = env.rollout(tape_d)
+            col = (lambda x: x) if sel is None else (lambda x: x[:, sel])
+            got_info = np.stack([col(info_t[k].view(t_roll, E)).cpu().numpy() for k in keys], 2).astype(np.int64)
+            ok = np.array_equal(col(done_t).cpu().numpy(), np.stack([x["done"][:t_roll] for x in exp], 1)) and \
+                np.array_equal(col(rew_t).cpu().numpy(), np.stack([x["reward"][:t_roll] for x in exp], 1)) and \
                 np.array_equal(got_info, np.stack([x["info"][:t_roll] for x in exp], 1))
             if not ok:
                 return "ROLLOUT MISMATCH %s %s %s E %d seed %d" % (prob, rep, calls, E, seed0)
+        row = (lambda x: x) if sel is None else (lambda x: x[sel])
         for t in range(t_roll, T):
             obs, rew, done, info = env.step(acts[t] if acts.shape[2] > 1 else acts[t, :, 0])
-            ok = np.array_equal(done.cpu().numpy(), np.array([x["done"][t] for x in exp])) and \
-                np.array_equal(rew.cpu().numpy(), np.array([x["reward"][t] for x in exp])) and \
-                np.array_equal(np.stack([info[k].cpu().numpy() for k in keys], 1).astype(np.int64), np.stack([x["info"][t] for x in exp]))
+            ok = np.array_equal(row(done).cpu().numpy(), np.array([x["done"][t] for x in exp])) and \
+                np.array_equal(row(rew).cpu().numpy(), np.array([x["reward"][t] for x in exp])) and \
+                np.array_equal(np.stack([row(info[k]).cpu().numpy() for k in keys], 1).astype(np.int64), np.stack([x["info"][t] for x in exp]))
             if not ok:
                 return "MISMATCH %s %s %s E %d seed %d step %d" % (prob, rep, calls, E, seed0, t)
-            bad = _obs_mismatch(obs, exp, t, env._rep.has_pos, map_every=map_every)
+            bad = _obs_mismatch(obs, exp, t, env._rep.has_pos, sel, map_every=map_every)
             if bad:
                 return "OBS MISMATCH (%s) %s %s %s E %d seed %d step %d" % (bad, prob, rep, calls, E, seed0, t)
         # the state the tape / the steps end in: map, cursor, heat map
-        if not np.array_equal(obs["map"].cpu().numpy(), np.stack([x["maps"][-1] for x in exp])):
+        if not np.array_equal(row(obs["map"]).cpu().numpy(), np.stack([x["maps"][-1] for x in exp])):
             return "MAP MISMATCH %s %s %s E %d seed %d" % (prob, rep, calls, E, seed0)
-        if env._rep.has_pos and not np.array_equal(obs["pos"].cpu().numpy().astype(np.int64), np.stack([x["pos"][-1] for x in exp])):
+        if env._rep.has_pos and not np.array_equal(row(obs["pos"]).cpu().numpy().astype(np.int64), np.stack([x["pos"][-1] for x in exp])):
             return "POS MISMATCH %s %s %s E %d seed %d" % (prob, rep, calls, E, seed0)
-        if not np.array_equal(obs["heatmap"].cpu().numpy().astype(np.int64), np.stack([x["heatmap"][-1] for x in exp]).astype(np.int64)):
+        if not np.array_equal(row(obs["heatmap"]).cpu().numpy().astype(np.int64), np.stack([x["heatmap"][-1] for x in exp]).astype(np.int64)):
             return "HEATMAP MISMATCH %s %s %s E %d seed %d" % (prob, rep, calls, E, seed0)
         env.check_status()
     finally:

@@ -460,6 +460,11 @@ def _expected_image(m, pos, oh, ow, centered, pad, depth):
     # windows of 65 536 bytes and more per environment (k_obs_huge: 64-bit offsets; the reference's Cropped takes any crop_size):
     # a 228 x 228 x 7 crop of an smb level, a 128 x 128 one-hot crop, a huge id window on a batch that ends mid-piece
     ("smb", "narrow", (), 3, 228, 228, 1, 1), ("zelda", "narrow", (), 5, 128, 128, 1, 1), ("binary", "turtle", (dict(width=20, height=30),), 7, 257, 255, 1, 0),
+    # maps beyond 64 x 64 (k_obs on byte maps): crops centred on cursors with x / y up to 254, and origin windows over a 300-wide map --
+    # exactly the map, smaller, larger (padding on two sides)
+    ("binary", "narrow", (dict(width=200, height=130),), 70, 28, 28, 1, 0), ("binary", "turtle", (dict(width=255, height=255),), 4, 31, 17, 1, 1),
+    ("zelda", "narrow", (dict(width=130, height=70),), 50, 22, 22, 1, 1), ("binary", "wide", (dict(width=300, height=40),), 9, 40, 300, 0, 0),
+    ("binary", "wide", (dict(width=300, height=40),), 9, 16, 64, 0, 0), ("binary", "wide", (dict(width=300, height=40),), 9, 50, 320, 0, 0),
 ], ids=lambda v: str(v) if not isinstance(v, tuple) else "adj%d" % len(v))
 def test_bound_observation_every_step(prob, rep, calls, n, oh, ow, centered, onehot):
     """pcgrl_bind_observation: after reset, after every step (auto-resets included) and after a rollout the bound tensor
@@ -475,9 +480,12 @@ def test_bound_observation_every_step(prob, rep, calls, n, oh, ow, centered, one
     obs = env.reset()
     has_pos = env._rep.has_pos
 
+    far = [0, 0]          # the largest cursor (x, y) an image was compared at
+
     def check(tag):
         m = env._bufs["map"].cpu().numpy()
         pos = env._bufs["pos"].cpu().numpy() if has_pos else np.zeros((n, 2), np.uint8)
+        far[0], far[1] = max(far[0], int(pos[:, 0].max())), max(far[1], int(pos[:, 1].max()))
         exp = _expected_image(m, pos, oh, ow, centered, pad, depth)
         got = img.cpu().numpy()
         bad = np.nonzero((got != exp).reshape(n, -1).any(1))[0]
@@ -509,6 +517,10 @@ def test_bound_observation_every_step(prob, rep, calls, n, oh, ow, centered, one
     assert torch.equal(other, img)
     assert env.check_status() == 0
     env.close()
+    if centered and has_pos:
+        # a centred crop on a map beyond 128 per side proves nothing about the upper columns / rows unless a compared cursor was there
+        W_, H_ = env._prob._width, env._prob._height
+        assert (W_ <= 128 or far[0] >= 128) and (H_ <= 128 or far[1] >= 128), ("no compared cursor in the upper columns / rows", W_, H_, far)
 
 
 @pytest.mark.gpu
