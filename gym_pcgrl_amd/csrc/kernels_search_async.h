@@ -15,7 +15,7 @@
 // environment steps differs.  The tick's length is bounded by pop_budget, the stall of a hard level is its own.
 //
 // The agents of a level run one after the other as in the reference (sokoban_prob.py:104-122, mdungeon_prob.py:110-126,
-// ddave_prob.py): nothing is searched speculatively -- in lockstep idle compute units are free, here every pop is throughput.
+// ddave_prob.py; SearchGame<PROB>::agent_fast and ::next, search_game.h): nothing is searched speculatively -- in lockstep idle compute units are free, here every pop is throughput.
 // A block is the two wavefronts of k_sokoban (search wavefront + heap server); jobs are handed out by tickets (first the
 // suspended slots, then the fresh jobs of the work lists) and no block ever waits for another.
 #pragma once
@@ -78,79 +78,6 @@ __device__ __forceinline__ void async_copy(uint32_t* dst, const uint32_t* src, i
     for (int i = lane; i < n4; i += 64) reinterpret_cast<uint4*>(dst)[i] = reinterpret_cast<const uint4*>(src)[i];
 }
 
-// One agent of a problem's _run_game, or a piece of it (lanes 0..3 of the search wavefront; the compact searches only).
-// res[]: what get_stats takes from the agent (kept from the last agent that ran to its end).
-template <int PROB>
-struct AsyncGame;
-template <>
-struct AsyncGame<PCGRL_PROB_SOKOBAN> {
-    typedef SolverGame<PCGRL_PROB_SOKOBAN>::Shared Shared;
-    // the 64 lanes of the search wavefront (level_build_wave.h); m: the map; scratch: 64 bytes of LDS
-    static __device__ __forceinline__ void build(const PcgrlParams& P, const DevBufs& B, const uint8_t* m, Shared& S, uint8_t* scratch, int lane) {
-        const int ncr = sok_build_level_wave(m, P.width, P.height, S.L, S.root, lane);
-        sok_init_deadlocks_wave(S.L, S.scratch, lane);
-        if (lane == 0) {
-            if (ncr > SOK_MAXC) atomicOr(B.status, 1);
-            S.root.h = (uint16_t)sok_heuristic(S.L, S.root.crate);
-            S.fast = (S.L.nc <= B.sok_fast_maxc) ? 1 : 0;
-        }
-    }
-    static __device__ __forceinline__ bool agent(Shared& S, int a, void* pool, uint32_t* lds, int toff, int tsize, SokDuoBox* duo, int power, const SokResumeArg& ra,
-                                                 int lane, int* res, bool& exhausted) {
-        const int KS[4] = {-1, 2, 1, 0};                                            // BFS, A*(1), A*(0.5), A*(0): sokoban_prob.py:104-122
-        const SokKidsLanes kids = {lane, sokf_dir(lane & 3, S.L.w)};
-        uint64_t* tab = reinterpret_cast<uint64_t*>(lds + toff);
-        int hh = 0, dd = 0, it = 0;
-        bool w;
-        if (S.L.cells <= 64) w = sok_search_fast<1>(S.L, reinterpret_cast<SokFastNode*>(pool), lds, tab, tsize - 1, S.cache, S.root, KS[a], power, hh, dd, it, exhausted, SokNoHook(), kids, duo, ra);
-        else w = sok_search_fast<4>(S.L, reinterpret_cast<SokFastNode*>(pool), lds, tab, tsize - 1, S.cache, S.root, KS[a], power, hh, dd, it, exhausted, SokNoHook(), kids, duo, ra);
-        res[0] = w ? 0 : hh; res[1] = w ? dd : 0;
-        return w;
-    }
-    static __device__ __forceinline__ int next(int a, bool win, bool exhausted) { return (win || (a == 0 && exhausted) || a == 3) ? 4 : a + 1; }   // (the exact exhausted-BFS shortcut)
-    static __device__ __forceinline__ void pack(int32_t* s, const int* res) { s[4] = res[0]; s[5] = res[1]; }
-};
-template <>
-struct AsyncGame<PCGRL_PROB_MDUNGEON> {
-    typedef SolverGame<PCGRL_PROB_MDUNGEON>::Shared Shared;
-    static __device__ __forceinline__ void build(const PcgrlParams& P, const DevBufs& B, const uint8_t* m, Shared& S, uint8_t*, int lane) {
-        const int n = md_build_level_wave(m, P.width, P.height, S.L, S.root, S.F, lane);
-        if (lane == 0) S.fast = (n <= MDF_MAXI && B.sok_fast_maxc >= 0) ? 1 : 0;
-    }
-    static __device__ __forceinline__ bool agent(Shared& S, int a, void* pool, uint32_t* lds, int toff, int tsize, SokDuoBox* duo, int power, const SokResumeArg& ra,
-                                                 int lane, int* res, bool& exhausted) {
-        const int KS[4] = {2, 1, 0, -1};                                            // mdungeon_prob.py:110-126
-        const MdKidsLanes kids = {lane};
-        uint64_t key = 0; int hh = 0, dd = 0, it = 0;
-        const bool w = md_search_fast(S.L, S.F, reinterpret_cast<MdFastNode*>(pool), lds, reinterpret_cast<uint64_t*>(lds + toff), tsize - 1, S.cache,
-                                      S.root, KS[a], power, key, hh, dd, it, exhausted, SokNoHook(), kids, duo, ra);
-        mdf_result(S.F, key, hh, dd, w, res);
-        return w;
-    }
-    static __device__ __forceinline__ int next(int a, bool win, bool exhausted) { return (win || a == 3) ? 4 : ((a < 3 && exhausted) ? 3 : a + 1); }   // md_run_game: straight to BFS
-    static __device__ __forceinline__ void pack(int32_t* s, const int* res) { md_pack(s, res); }
-};
-template <>
-struct AsyncGame<PCGRL_PROB_DDAVE> {
-    typedef SolverGame<PCGRL_PROB_DDAVE>::Shared Shared;
-    static __device__ __forceinline__ void build(const PcgrlParams& P, const DevBufs& B, const uint8_t* m, Shared& S, uint8_t*, int lane) {
-        const int n = dd_build_level_wave(m, P.width, P.height, S.L, S.root, S.F, lane);
-        if (lane == 0) S.fast = (n <= DDF_MAXD && B.sok_fast_maxc >= 0) ? 1 : 0;
-    }
-    static __device__ __forceinline__ bool agent(Shared& S, int a, void* pool, uint32_t* lds, int toff, int tsize, SokDuoBox* duo, int power, const SokResumeArg& ra,
-                                                 int lane, int* res, bool& exhausted) {
-        const int KS[4] = {2, 1, 0, -1};
-        const DdKidsLanes kids = {lane};
-        uint64_t key = 0; int hh = 0, dd = 0, jj = 0, it = 0;
-        const bool w = dd_search_fast(S.L, S.F, reinterpret_cast<DdFastNode*>(pool), lds, reinterpret_cast<uint64_t*>(lds + toff), tsize - 1, S.cache,
-                                      S.root, KS[a], power, key, hh, dd, jj, it, exhausted, SokNoHook(), kids, duo, ra);
-        ddf_result(S.F, key, hh, dd, jj, w, res);
-        return w;
-    }
-    static __device__ __forceinline__ int next(int a, bool win, bool) { return (win || a == 3) ? 4 : a + 1; }
-    static __device__ __forceinline__ void pack(int32_t* s, const int* res) { dd_pack(s, res); }
-};
-
 // developer build (tools/probe/async_prof.py, -DPCGRL_ASYNC_PROF): where the search wavefront's time goes, 10 ns ticks summed over all blocks
 #if defined(PCGRL_ASYNC_PROF)
 #define AP_DECL unsigned long long ap_t = wall_clock64()
@@ -172,14 +99,13 @@ struct AsyncGame<PCGRL_PROB_DDAVE> {
 template <int PROB>
 __global__ __launch_bounds__(128) void k_search_async(PcgrlParams P, DevBufs B, AsyncCtl A, int list_a, int mode_a, int list_b, int mode_b, int parity,
                                                      int rst_list, int32_t* tickets, int clear_parity, int budget, int resume, int toff, int tsize, int small) {
-    typedef AsyncGame<PROB> Game;
+    typedef SearchGame<PROB> Game;
     extern __shared__ __attribute__((aligned(16))) uint32_t as_lds[];       // heap | visited table, as in k_sokoban
     __shared__ int s_pref_a[WL_NSHARD + 1], s_pref_b[WL_NSHARD + 1];
     __shared__ SokDuoBox s_box;
     __shared__ typename Game::Shared s_game;
     __shared__ SokResume s_rs;
     __shared__ int s_slot;
-    __shared__ uint8_t s_scratch[64];
     if (clear_parity >= 0 && blockIdx.x == 0) wl_clear(B, clear_parity);
     const int lane = threadIdx.x & 63;
     const int n_a = list_a >= 0 ? wl_load_prefix(B, parity, list_a, s_pref_a) : 0;
@@ -235,7 +161,7 @@ __global__ __launch_bounds__(128) void k_search_async(PcgrlParams P, DevBufs B, 
             e = hd->env; mode = hd->mode; a0 = hd->agent; tsm = hd->tsaved;
             if (lane == 0) s_rs = hd->rs;
         }
-        Game::build(P, B, B.map + (size_t)e * P.width * P.height, s_game, s_scratch, lane);
+        Game::build(P, B, B.map + (size_t)e * P.width * P.height, s_game, lane);
         __threadfence_block();
         AP(2);
         if (!s_game.fast) {
@@ -246,12 +172,10 @@ __global__ __launch_bounds__(128) void k_search_async(PcgrlParams P, DevBufs B, 
                 __threadfence_block();
                 continue;
             }
-            int32_t s[PCGRL_MAX_STATS];
-            const int32_t* park = (mode == MODE_STEP) ? B.info + (size_t)e * 10 : B.stats + (size_t)e * 8;
-            if (lane == 0) for (int k = 0; k < 8; k++) s[k] = park[k];
-            SolverGame<PROB>::run(P, B, e, s_game, as_lds, toff, tsize, P.solver_power, reinterpret_cast<SokNode*>(block_pool), lane, s);
+            int gres[Game::NRES] = {};
+            search_game_run<PROB>(P, B, e, s_game, as_lds, toff, tsize, P.solver_power, block_pool, lane, gres);
             if (lane == 0) {
-                const bool ended = finalize_item<PROB>(P, B, e, s, mode, parity, e & (WL_NSHARD - 1), rst_list >= 0, rst_list);
+                const bool ended = finish_search_item<PROB>(P, B, e, gres, mode, parity, rst_list >= 0, rst_list);
                 A.pending[e] = (ended && rst_list < 0) ? ASYNC_PEND_RESET : 0;
                 if (slot >= 0) { async_hdr(A, slot)->state = 0; atomicAdd(A.stats + ASYNC_ST_LATE, 1ull); }
             }
@@ -262,7 +186,7 @@ __global__ __launch_bounds__(128) void k_search_async(PcgrlParams P, DevBufs B, 
         void* pool = slot >= 0 ? (void*)async_pool(A, slot) : (void*)block_pool;
         int a = a0, remaining = unbounded ? 0x3FFFFFFF : budget, done = 0, handed = 0;
         int how = (slot >= 0 && s_rs.iterations > 0) ? 1 : 0;          // 0: the agent starts (clear the table), 1: restore from the slot, 2: go on in place
-        int res[5] = {0, 0, 0, 0, 0};
+        int res[Game::NRES] = {};                                      // what get_stats takes from the agent (kept from the last agent that ran to its end)
         int tcur = tsize;                                              // slots of the table this piece works on (async_table_need)
         for (;;) {
             for (;;) {
@@ -298,8 +222,9 @@ __global__ __launch_bounds__(128) void k_search_async(PcgrlParams P, DevBufs B, 
                 int win = 0, exh = 0;
                 if (lane < 4) {
                     bool ex = false;
+                    int it = 0;
                     const SokResumeArg ra = {&s_rs, before + remaining};
-                    win = Game::agent(s_game, a, pool, as_lds, toff, tcur, &s_box, P.solver_power, ra, lane, res, ex) ? 1 : 0;
+                    win = Game::agent_fast(s_game, a, pool, as_lds, toff, tcur, P.solver_power, lane, res, it, ex, SokNoHook(), &s_box, ra) ? 1 : 0;
                     exh = ex ? 1 : 0;
                 }
                 __threadfence_block();
@@ -359,12 +284,8 @@ __global__ __launch_bounds__(128) void k_search_async(PcgrlParams P, DevBufs B, 
             __threadfence_block();
         } else if (done) {
             if (lane == 0) {
-                int32_t s[PCGRL_MAX_STATS];
-                const int32_t* park = (mode == MODE_STEP) ? B.info + (size_t)e * 10 : B.stats + (size_t)e * 8;
-                for (int k = 0; k < 8; k++) s[k] = park[k];
-                Game::pack(s, res);
                 // an episode this result ends: with a reset list the caller resets it in this tick (flush), else the next tick does
-                const bool ended = finalize_item<PROB>(P, B, e, s, mode, parity, e & (WL_NSHARD - 1), rst_list >= 0, rst_list);
+                const bool ended = finish_search_item<PROB>(P, B, e, res, mode, parity, rst_list >= 0, rst_list);
                 A.pending[e] = (ended && rst_list < 0) ? ASYNC_PEND_RESET : 0;
                 if (slot >= 0) { __threadfence(); async_hdr(A, slot)->state = 0; atomicAdd(A.stats + ASYNC_ST_LATE, 1ull); }
             }

@@ -17,13 +17,14 @@
 // waits on work that may never come.  A block leaves when every BFS has finished (the hard list is then
 // final) and every A* ticket has been taken.  Blocks only ever wait for blocks that hold a ticket, i.e.
 // that are resident and running: no forward-progress assumption between unscheduled blocks.
+//
+// The game itself -- level build, agent order, the searches, the stop rule, the packing of the result -- is
+// SearchGame<PCGRL_PROB_SOKOBAN> (search_game.h); this file is the scheduling and the selection.
 #pragma once
 
 enum { SOK_SY_TICKET_A = 0, SOK_SY_TICKET_B = 1, SOK_SY_HARD = 2, SOK_SY_BFS_DONE = 3, SOK_SY_WORDS = 16 };
 #define SOK_HARD_CAP 4096          /* published levels per launch; beyond it a BFS block runs its A* agents itself */
 #define SOK_SPAWN_ITERS 128
-
-__device__ __forceinline__ int sok_ld(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 struct SokSpawnHook {     // BFS: publish the level once the search has proven to be a long one
     int32_t* sync; int32_t* hard; int spawn_at; int tag; int* spawned; int lane; int cap;
@@ -35,86 +36,31 @@ struct SokSpawnHook {     // BFS: publish the level once the search has proven t
         return false;
     }
 };
-struct SokPollHook {      // A*: stop when the result cannot be selected any more
-    const int32_t* stop; int need;
-    __device__ __forceinline__ bool operator()(int it) const { return (it & SOK_POLL_MASK) == 0 && sok_ld(stop) >= need; }
-};
-
-// The four children of a pop, one per lane (lanes 0..3 run the search in lockstep; everything else in it is
-// uniform across them).  The results come back through v_readlane, i.e. as scalars.
-struct SokKidsLanes {
-    int lane, dir;      // dir: this lane's move as a cell offset (sokf_dir(lane & 3, level width)), made once per search
-    // this lane's child only (two-wavefront searches: each lane files its own child)
-    template <int NW>
-    __device__ __forceinline__ SokChild mine(const SokFastLevel<NW>& F, uint64_t cr, const uint64_t* cb, int player, int h) const {
-        return sokf_child_dir<NW>(F, cr, cb, player, h, dir);
-    }
-    template <int NW>
-    __device__ __forceinline__ void operator()(const SokFastLevel<NW>& F, uint64_t cr, const uint64_t* cb, int player, int h, SokChild* out) const {
-        const SokChild mine = sokf_child_dir<NW>(F, cr, cb, player, h, dir);
-#pragma unroll
-        for (int d = 0; d < 4; d++) {
-            const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)mine.cr, d);
-            const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(mine.cr >> 32), d);
-            out[d].cr = ((uint64_t)hi << 32) | lo;
-            out[d].np = __builtin_amdgcn_readlane(mine.np, d);
-            out[d].h = __builtin_amdgcn_readlane(mine.h, d);
-            out[d].ok = __builtin_amdgcn_readlane(mine.ok, d);
-        }
-    }
-};
-
-// One agent of environment e is done.  The fourth report selects the result and finishes the item.
-__device__ __forceinline__ void sok_report(const PcgrlParams& P, const DevBufs& B, int e, int a, bool win, int hh, int dd, bool exhausted,
+// One agent of environment e is done (res: SearchGame::agent_*).  The fourth report selects the result and finishes the item.
+__device__ __forceinline__ void sok_report(const PcgrlParams& P, const DevBufs& B, int e, int a, bool win, bool exhausted, const int* res,
                                            int mode, int parity, int rst_list) {
     int32_t* r = B.sok_res + ((size_t)e * 4 + a) * 4;
     __hip_atomic_store(r + 0, win ? 1 : 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(r + 1, hh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(r + 2, dd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(r + 1, res[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(r + 2, res[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_store(r + 3, exhausted ? 1 : 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    // agents after `a` are not needed once a wins (or BFS has expanded every reachable state): stop level 3 - a
-    if (win || (a == 0 && exhausted)) atomicMax(B.sok_stop + e, 3 - a);
+    SearchGame<PCGRL_PROB_SOKOBAN>::stop_update(B.sok_stop + e, a, win, exhausted);
     __threadfence();
     if (atomicAdd(B.sok_cnt + e, 1) != 3) return;
     __threadfence();
-    int dist = 0, sol = 0;
+    int sel[2] = {0, 0};   // dist-win, sol-length
     bool chosen = false;
     for (int k = 0; k < 4 && !chosen; k++) {
         const int32_t* q = B.sok_res + ((size_t)e * 4 + k) * 4;
-        if (sok_ld(q + 0)) { dist = 0; sol = sok_ld(q + 2); chosen = true; }
+        if (sok_ld(q + 0)) { sel[1] = sok_ld(q + 2); chosen = true; }
     }
     if (!chosen) {
         const int32_t* q0 = B.sok_res + (size_t)e * 16;
-        dist = sok_ld(q0 + 3) ? sok_ld(q0 + 1) : sok_ld(q0 + 12 + 1);   // exhausted BFS, else the last agent's best node
+        sel[0] = sok_ld(q0 + 3) ? sok_ld(q0 + 1) : sok_ld(q0 + 12 + 1);   // exhausted BFS, else the last agent's best node
     }
     B.sok_cnt[e] = 0;      // ready for the next job of this environment (a later launch)
     B.sok_stop[e] = 0;
-    int32_t s[PCGRL_MAX_STATS];
-    const int32_t* park = (mode == MODE_STEP) ? B.info + (size_t)e * 10 : B.stats + (size_t)e * 8;
-    for (int k = 0; k < 8; k++) s[k] = park[k];
-    s[4] = dist; s[5] = sol;
-    finalize_item<PCGRL_PROB_SOKOBAN>(P, B, e, s, mode, parity, e & (WL_NSHARD - 1), true, rst_list);
-}
-
-// One agent on the level in L: the register-resident search (sokoban_fast.h; LDS heap + 64-bit-key table) when the
-// level qualifies, else the generic one (LDS or global-arena heap/table).  Called by lanes 0..3 for the former (the
-// four children of a pop are made side by side), by lane 0 for the latter.
-template <class Hook>
-__device__ __forceinline__ bool sok_run_agent(const DevBufs& B, int power, const SokLevel& L, SokNode& work, const SokNode& root, SokNode* pool,
-                                              uint32_t* lds, SokFastNode* cache, uint32_t* g_heap, uint32_t* g_table, int tsize, int fast, int k,
-                                              int& hh, int& dd, int& it, bool& exhausted, Hook hook, int lane, int table_off = SOK_LDS_HEAP,
-                                              SokDuoBox* duo = nullptr) {
-    if (fast) {
-        const SokKidsLanes kids = {lane, sokf_dir(lane & 3, L.w)};
-        uint64_t* tab = reinterpret_cast<uint64_t*>(lds + table_off);
-        SokFastNode* fp = reinterpret_cast<SokFastNode*>(pool);
-        if (L.cells <= 64) return sok_search_fast<1>(L, fp, lds, tab, tsize - 1, cache, root, k, power, hh, dd, it, exhausted, hook, kids, duo);
-        return sok_search_fast<4>(L, fp, lds, tab, tsize - 1, cache, root, k, power, hh, dd, it, exhausted, hook, kids, duo);
-    }
-    if (lane != 0) return false;
-    if (B.sok_use_lds)   // two instantiations: LDS pointers compile to ds_* instructions
-        return sok_search(L, pool, lds, lds + table_off, tsize - 1, work, root, k, power, hh, dd, it, exhausted, hook);
-    return sok_search(L, pool, g_heap, g_table, tsize - 1, work, root, k, power, hh, dd, it, exhausted, hook);
+    finish_search_item<PCGRL_PROB_SOKOBAN>(P, B, e, sel, mode, parity, true, rst_list);
 }
 
 // pcgrl_selftest_heap: the heap server's two primitives (sok_duo_append / sok_duo_repair) driven by a tape of operations, so that
@@ -163,17 +109,13 @@ __global__ __launch_bounds__(128) void k_sokoban(PcgrlParams P, DevBufs B, int l
     __shared__ SokDuoBox s_box;
     if (threadIdx.x >= 64) { sok_duo_server(sok_lds, &s_box, lane); return; }
     SokDuoBox* const duo = B.sok_use_lds ? &s_box : nullptr;       // (the heap has to be the LDS one)
-    __shared__ SokLevel s_L;             // level + node workspace in LDS: they are indexed dynamically
-    __shared__ SokNode s_root, s_work;
-    __shared__ int s_spawned, s_fast;
-    __shared__ uint8_t s_scr[64];
-    __shared__ SokFastNode s_cache[4];
+    typedef SearchGame<PCGRL_PROB_SOKOBAN> G;
+    __shared__ G::Shared s_game;         // level + node workspace in LDS: they are indexed dynamically
+    __shared__ int s_spawned;
     SokNode* pool = B.sok_pool + (size_t)blockIdx.x * B.sok_pool_stride;
     uint32_t* g_heap = B.sok_use_lds ? nullptr : B.sok_heap + (size_t)blockIdx.x * B.sok_heap_stride;
     uint32_t* g_table = B.sok_use_lds ? nullptr : B.sok_table + (size_t)blockIdx.x * B.sok_table_size;
     const int tsize = B.sok_use_lds ? SOK_LDS_TABLE : B.sok_table_size;
-    const int W = P.width, H = P.height;
-    const int KS[4] = {-1, 2, 1, 0};
     for (;;) {
         int kind = 0, t = 0;   // 0: nothing to do right now, 1: BFS job t, 2: A* ticket t, 3: leave
         if (lane == 0) {
@@ -213,63 +155,44 @@ __global__ __launch_bounds__(128) void k_sokoban(PcgrlParams P, DevBufs B, int l
             mode = (tag >> 28) & 3;
             first = last = 1 + t % 3;
         }
-        {   // the level by all 64 lanes (level_build_wave.h: ~40 us on one lane, a few on the wavefront)
-            const int ncr = sok_build_level_wave(B.map + (size_t)e * W * H, W, H, s_L, s_root, lane);
-            sok_init_deadlocks_wave(s_L, s_scr, lane);
-            if (lane == 0) {
-                if (ncr > SOK_MAXC) atomicOr(B.status, 1);
-                s_root.h = (uint16_t)sok_heuristic(s_L, s_root.crate);
-                s_spawned = 0;
-                s_fast = (B.sok_use_lds && s_L.nc <= B.sok_fast_maxc) ? 1 : 0;
-            }
-        }
+        // the level by all 64 lanes (level_build_wave.h: ~40 us on one lane, a few on the wavefront)
+        G::build(P, B, B.map + (size_t)e * P.width * P.height, s_game, lane);
+        if (lane == 0) s_spawned = 0;
         __threadfence_block();
-        const int fast = s_fast;
+        const int fast = s_game.fast;
         // BFS job: agent 0 and -- only if the level could not be published -- the other agents after it, with the
         // exact exhausted-BFS shortcut.  A* ticket: that one agent.  The search runs on lanes 0..3 (register-resident
         // path: uniform except for the four children of a pop) or on lane 0 (generic path); every lane helps to clear
         // the visited table.
-        int dist = 0, sol = 0, go = 1, reported = 0;
+        int res[2] = {0, 0}, go = 1, reported = 0;
         for (int a = first; a <= last && go; a++) {
-            if (fast) { for (int i = lane; i < 2 * tsize; i += 64) sok_lds[SOK_LDS_HEAP + i] = 0; }   // 64-bit keys
-            else if (B.sok_use_lds) { for (int i = lane; i < tsize; i += 64) sok_lds[SOK_LDS_HEAP + i] = 0; }
-            else { for (int i = lane; i < tsize; i += 64) g_table[i] = 0; }
+            search_clear_table(B, sok_lds, g_table, tsize, fast, lane);
             __threadfence_block();
             if (lane < (fast ? 4 : 1)) {
-                int hh = 0, dd = 0, it = 0;
+                int it = 0;
                 bool exhausted = false, win = false;
                 if (kind == 1 && a == 0) {
                     int sp = P.solver_power < B.sok_spawn_iters ? P.solver_power : B.sok_spawn_iters;
                     SokSpawnHook hook = {sync, hard, sp, (e + 1) | (mode << 28), &s_spawned, lane, B.sok_hard_cap};
-                    win = sok_run_agent(B, P.solver_power, s_L, s_work, s_root, pool, sok_lds, s_cache, g_heap, g_table, tsize, fast, -1, hh, dd, it, exhausted, hook, lane);
+                    win = search_agent<PCGRL_PROB_SOKOBAN>(B, s_game, 0, pool, sok_lds, g_heap, g_table, tsize, fast, P.solver_power, lane, res, it, exhausted, hook, (SokDuoBox*)nullptr);
                     __threadfence_block();
-                    if (s_spawned) { if (lane == 0) sok_report(P, B, e, 0, win, hh, dd, exhausted, mode, parity, rst_list); reported = 1; go = 0; }
+                    if (s_spawned) { if (lane == 0) sok_report(P, B, e, 0, win, exhausted, res, mode, parity, rst_list); reported = 1; go = 0; }
                     else go = !(win || exhausted);
                 } else if (kind == 1) {
-                    win = sok_run_agent(B, P.solver_power, s_L, s_work, s_root, pool, sok_lds, s_cache, g_heap, g_table, tsize, fast, KS[a], hh, dd, it, exhausted, SokNoHook(), lane, SOK_LDS_HEAP, duo);
+                    win = search_agent<PCGRL_PROB_SOKOBAN>(B, s_game, a, pool, sok_lds, g_heap, g_table, tsize, fast, P.solver_power, lane, res, it, exhausted, SokNoHook(), duo);
                     go = !win;
                 } else {
-                    SokPollHook hook = {B.sok_stop + e, 4 - a};
-                    if (sok_ld(B.sok_stop + e) < 4 - a) {
-                        win = sok_run_agent(B, P.solver_power, s_L, s_work, s_root, pool, sok_lds, s_cache, g_heap, g_table, tsize, fast, KS[a], hh, dd, it, exhausted, hook, lane, SOK_LDS_HEAP, duo);
-                    }
-                    if (lane == 0) sok_report(P, B, e, a, win, hh, dd, false, mode, parity, rst_list);
+                    const SearchPollHook<PCGRL_PROB_SOKOBAN> hook = {B.sok_stop + e, a};   // A*: stop when the result cannot be selected any more
+                    if (!hook(0)) win = search_agent<PCGRL_PROB_SOKOBAN>(B, s_game, a, pool, sok_lds, g_heap, g_table, tsize, fast, P.solver_power, lane, res, it, exhausted, hook, duo);
+                    if (lane == 0) sok_report(P, B, e, a, win, false, res, mode, parity, rst_list);
                     reported = 1;
                 }
-                dist = win ? 0 : hh;
-                sol = win ? dd : 0;
             }
             go = __shfl(go, 0, 64);
             __threadfence_block();
         }
         if (lane == 0 && kind == 1) {
-            if (!reported) {
-                int32_t s[PCGRL_MAX_STATS];
-                const int32_t* park = (mode == MODE_STEP) ? B.info + (size_t)e * 10 : B.stats + (size_t)e * 8;
-                for (int k = 0; k < 8; k++) s[k] = park[k];
-                s[4] = dist; s[5] = sol;
-                finalize_item<PCGRL_PROB_SOKOBAN>(P, B, e, s, mode, parity, e & (WL_NSHARD - 1), true, rst_list);
-            }
+            if (!reported) finish_search_item<PCGRL_PROB_SOKOBAN>(P, B, e, res, mode, parity, true, rst_list);
             __threadfence();
             atomicAdd(sync + SOK_SY_BFS_DONE, 1);
         }

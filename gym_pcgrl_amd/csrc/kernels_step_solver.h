@@ -17,11 +17,8 @@
 // list ids reuse the global ones: WL_CHG changed, WL_RST reset before the searches, WL_SOL / WL_SOL2 search jobs of changed /
 // regenerated maps, WL_RST2 reset after the searches, WL_SOL3 their jobs
 //
-// SolverGame<PROB>::run: _run_game of one level by one wavefront with the agents in sequence, inside a given search region
-// (`heap`, `table` of `tsize` slots at `heap + table_off` words) and with at most `power` pops per agent.  Returns (on every
-// lane) whether the result is final: with power < solver_power an agent that is stopped by the limit makes the whole job
-// "not final" -- it is then run again with the full region and the full power.  A search that ends by winning or by running
-// out of states before the limit gives what the full search gives (the table size only changes the probe sequences).
+// The searches are search_game_run (search_game.h): the agents in sequence inside a given search region, with a pop limit; a job
+// that the small region's limit stops is "not final" and is run again with the full region and the full power.
 #define SS_SMALL_POPS 256
 #define SS_SMALL_TABLE 1024
 #define SS_SMALL_HEAP 1028                                /* 1 + 4 * SS_SMALL_POPS entries, padded */
@@ -30,137 +27,13 @@
 #define SS_THREADS 512                                   /* one block per compute unit: eight wavefronts share the phases of a step */
 #define SS_SEARCH_WAVES 8                                 /* wavefronts that take search jobs (a small region each) */
 
-template <int PROB>
-struct SolverGame;
-
-template <>
-struct SolverGame<PCGRL_PROB_SOKOBAN> {
-    struct Shared { SokLevel L; SokNode root, work; SokFastNode cache[4]; int fast; uint8_t scratch[64]; };
-    static __device__ __forceinline__ bool run(const PcgrlParams& P, const DevBufs& B, int e, Shared& S, uint32_t* heap, int table_off, int tsize, int power,
-                                               SokNode* pool, int lane, int32_t* s) {
-        {   // the level by all 64 lanes (level_build_wave.h)
-            const int ncr = sok_build_level_wave(B.map + (size_t)e * P.width * P.height, P.width, P.height, S.L, S.root, lane);
-            sok_init_deadlocks_wave(S.L, S.scratch, lane);
-            if (lane == 0) {
-                if (ncr > SOK_MAXC) atomicOr(B.status, 1);
-                S.root.h = (uint16_t)sok_heuristic(S.L, S.root.crate);
-                S.fast = (S.L.nc <= B.sok_fast_maxc) ? 1 : 0;
-            }
-        }
-        __threadfence_block();
-        const int fast = S.fast;
-        const int KS[4] = {-1, 2, 1, 0};
-        int hh = 0, dd = 0, win = 0, final = 1;
-        for (int a = 0; a < 4; a++) {
-            for (int i = lane; i < (fast ? 2 : 1) * tsize; i += 64) heap[table_off + i] = 0;      // 64-bit keys on the fast path
-            __threadfence_block();
-            int stop = 0;
-            if (lane < (fast ? 4 : 1)) {
-                int it = 0; bool exhausted = false;
-                const bool w = sok_run_agent(B, power, S.L, S.work, S.root, pool, heap, S.cache, (uint32_t*)nullptr, (uint32_t*)nullptr, tsize, fast,
-                                             KS[a], hh, dd, it, exhausted, SokNoHook(), lane, table_off);
-                win = w ? 1 : 0;
-                if (!w && !exhausted && power < P.solver_power) { final = 0; stop = 1; }        // stopped by the reduced limit
-                else stop = (w || (a == 0 && exhausted)) ? 1 : 0;   // sok_run_game: first winner, or the exact exhausted-BFS shortcut
-            }
-            stop = __shfl(stop, 0, 64);
-            __threadfence_block();
-            if (stop) break;
-        }
-        if (lane == 0) { s[4] = win ? 0 : hh; s[5] = win ? dd : 0; }
-        return __shfl(final, 0, 64) != 0;
-    }
-};
-template <>
-struct SolverGame<PCGRL_PROB_MDUNGEON> {
-    struct Shared { MdLevel L; MdNode root, work; MdFastLevel F; MdFastNode cache[4]; int fast; };
-    static __device__ __forceinline__ bool run(const PcgrlParams& P, const DevBufs& B, int e, Shared& S, uint32_t* heap, int table_off, int tsize, int power,
-                                               SokNode* pool, int lane, int32_t* s) {
-        {
-            const int nthings = md_build_level_wave(B.map + (size_t)e * P.width * P.height, P.width, P.height, S.L, S.root, S.F, lane);
-            if (lane == 0) S.fast = (nthings <= MDF_MAXI && B.sok_fast_maxc >= 0) ? 1 : 0;
-        }
-        __threadfence_block();
-        const int fast = S.fast;
-        const int KS[4] = {2, 1, 0, -1};
-        int out5[5] = {0, 0, 0, 0, 0}, final = 1;
-        for (int a = 0; a < 4; a++) {
-            for (int i = lane; i < (fast ? 2 : 1) * tsize; i += 64) heap[table_off + i] = 0;
-            __threadfence_block();
-            int next = a + 1;
-            if (lane < (fast ? 4 : 1)) {
-                int it = 0; bool exhausted = false, w;
-                if (fast) {
-                    uint64_t key = 0; int hh = 0, dd = 0;
-                    const MdKidsLanes kids = {lane};
-                    w = md_search_fast(S.L, S.F, reinterpret_cast<MdFastNode*>(pool), heap, reinterpret_cast<uint64_t*>(heap + table_off), tsize - 1,
-                                       S.cache, S.root, KS[a], power, key, hh, dd, it, exhausted, SokNoHook(), kids);
-                    mdf_result(S.F, key, hh, dd, w, out5);
-                } else {
-                    w = md_search(S.L, reinterpret_cast<MdNode*>(pool), heap, heap + table_off, tsize - 1, S.work, S.root, KS[a], power, it, exhausted);
-                    md_result(S.L, S.root, S.work, w, out5);
-                }
-                if (!w && !exhausted && power < P.solver_power) { final = 0; next = 4; }
-                else if (w) next = 4;
-                else if (a < 3 && exhausted) next = 3;            // md_run_game: straight to BFS
-            }
-            next = __shfl(next, 0, 64);
-            __threadfence_block();
-            a = next - 1;
-        }
-        if (lane == 0) md_pack(s, out5);
-        return __shfl(final, 0, 64) != 0;
-    }
-};
-template <>
-struct SolverGame<PCGRL_PROB_DDAVE> {
-    struct Shared { DdLevel L; DdNode root, work; DdFastLevel F; DdFastNode cache[4]; int fast; };
-    static __device__ __forceinline__ bool run(const PcgrlParams& P, const DevBufs& B, int e, Shared& S, uint32_t* heap, int table_off, int tsize, int power,
-                                               SokNode* pool, int lane, int32_t* s) {
-        {
-            const int nd = dd_build_level_wave(B.map + (size_t)e * P.width * P.height, P.width, P.height, S.L, S.root, S.F, lane);
-            if (lane == 0) S.fast = (nd <= DDF_MAXD && B.sok_fast_maxc >= 0) ? 1 : 0;
-        }
-        __threadfence_block();
-        const int fast = S.fast;
-        const int KS[4] = {2, 1, 0, -1};
-        int out4[4] = {0, 0, 0, 0}, final = 1;
-        for (int a = 0; a < 4; a++) {
-            for (int i = lane; i < (fast ? 2 : 1) * tsize; i += 64) heap[table_off + i] = 0;
-            __threadfence_block();
-            int stop = 0;
-            if (lane < (fast ? 4 : 1)) {
-                int it = 0; bool exhausted = false, w;
-                if (fast) {
-                    uint64_t key = 0; int hh = 0, dd = 0, jj = 0;
-                    const DdKidsLanes kids = {lane};
-                    w = dd_search_fast(S.L, S.F, reinterpret_cast<DdFastNode*>(pool), heap, reinterpret_cast<uint64_t*>(heap + table_off), tsize - 1, S.cache,
-                                       S.root, KS[a], power, key, hh, dd, jj, it, exhausted, SokNoHook(), kids);
-                    ddf_result(S.F, key, hh, dd, jj, w, out4);
-                } else {
-                    w = dd_search(S.L, reinterpret_cast<DdNode*>(pool), heap, heap + table_off, tsize - 1, S.work, S.root, KS[a], power, it, exhausted,
-                                  SokNoHook());
-                    dd_result(S.L, S.work, w, out4);
-                }
-                if (!w && !exhausted && power < P.solver_power) { final = 0; stop = 1; }
-                else stop = w ? 1 : 0;
-            }
-            stop = __shfl(stop, 0, 64);
-            __threadfence_block();
-            if (stop) break;
-        }
-        if (lane == 0) dd_pack(s, out4);
-        return __shfl(final, 0, 64) != 0;
-    }
-};
-
 template <int PROB, int REP, class MaskT>
 __global__ __launch_bounds__(SS_THREADS) void k_step_solver(PcgrlParams P, DevBufs Bg, const int32_t* __restrict__ actions, int gen_map, int steps,
                                                              size_t action_stride, int envs_per_block, double* reward_out, uint8_t* done_out,
                                                              int32_t* info_out) {
     extern __shared__ __attribute__((aligned(16))) uint32_t ss_lds[];     // heap + visited table of the block's one search at a time
     __shared__ LocalLists s_lists;
-    __shared__ typename SolverGame<PROB>::Shared s_game0;      // the full-region search; the small ones keep theirs in the region itself
+    __shared__ typename SearchGame<PROB>::Shared s_game0;      // the full-region search; the small ones keep theirs in the region itself
     __shared__ uint16_t s_big[2 * WL_LOCAL_CAP];    // search jobs that need the full region (at most every WL_SOL + park-list entry)
     __shared__ int s_nbig;
     // the resets (MT ring + tile bytes per wavefront) borrow the search region: resets and searches are separate phases
@@ -238,18 +111,16 @@ __global__ __launch_bounds__(SS_THREADS) void k_step_solver(PcgrlParams P, DevBu
             if (tid == 0) s_nbig = 0;
             __syncthreads();
             const int small_power = P.solver_power < SS_SMALL_POPS ? P.solver_power : SS_SMALL_POPS;
-            typedef typename SolverGame<PROB>::Shared GameShared;
+            typedef typename SearchGame<PROB>::Shared GameShared;
             GameShared* small_games = reinterpret_cast<GameShared*>(ss_lds + SS_SEARCH_WAVES * SS_SMALL_WORDS);
             for (int j = wv; j < na + nb && wv < SS_SEARCH_WAVES; j += SS_SEARCH_WAVES) {
                 const int mode = j < na ? MODE_STEP : MODE_START;
                 const int e = e0 + (int)(j < na ? s_lists.items[WL_SOL][j] : s_lists.items[park_list][j - na]);
-                int32_t s[PCGRL_MAX_STATS];
-                const int32_t* park = (mode == MODE_STEP) ? B.info + (size_t)e * 10 : B.stats + (size_t)e * 8;
-                if (lane64 == 0) for (int k = 0; k < 8; k++) s[k] = park[k];
-                const bool final = SolverGame<PROB>::run(P, B, e, small_games[wv], ss_lds + wv * SS_SMALL_WORDS, SS_SMALL_HEAP, SS_SMALL_TABLE, small_power,
-                                                         pool + (size_t)wv * SS_SMALL_NODES, lane64, s);
+                int res[SearchGame<PROB>::NRES] = {};
+                const bool final = search_game_run<PROB>(P, B, e, small_games[wv], ss_lds + wv * SS_SMALL_WORDS, SS_SMALL_HEAP, SS_SMALL_TABLE, small_power,
+                                                         pool + (size_t)wv * SS_SMALL_NODES, lane64, res);
                 if (lane64 == 0) {
-                    if (final) finalize_item<PROB>(P, B, e, s, mode, 0, 0, true, WL_RST2);
+                    if (final) finish_search_item<PROB>(P, B, e, res, mode, 0, true, WL_RST2);
                     else s_big[atomicAdd(&s_nbig, 1)] = (uint16_t)j;
                 }
                 __builtin_amdgcn_wave_barrier();
@@ -261,11 +132,9 @@ __global__ __launch_bounds__(SS_THREADS) void k_step_solver(PcgrlParams P, DevBu
                     const int j = s_big[q];
                     const int mode = j < na ? MODE_STEP : MODE_START;
                     const int e = e0 + (int)(j < na ? s_lists.items[WL_SOL][j] : s_lists.items[park_list][j - na]);
-                    int32_t s[PCGRL_MAX_STATS];
-                    const int32_t* park = (mode == MODE_STEP) ? B.info + (size_t)e * 10 : B.stats + (size_t)e * 8;
-                    if (lane64 == 0) for (int k = 0; k < 8; k++) s[k] = park[k];
-                    SolverGame<PROB>::run(P, B, e, s_game0, ss_lds, SOK_LDS_HEAP, SOK_LDS_TABLE, P.solver_power, pool, lane64, s);
-                    if (lane64 == 0) finalize_item<PROB>(P, B, e, s, mode, 0, 0, true, WL_RST2);
+                    int res[SearchGame<PROB>::NRES] = {};
+                    search_game_run<PROB>(P, B, e, s_game0, ss_lds, SOK_LDS_HEAP, SOK_LDS_TABLE, P.solver_power, pool, lane64, res);
+                    if (lane64 == 0) finish_search_item<PROB>(P, B, e, res, mode, 0, true, WL_RST2);
                     __builtin_amdgcn_wave_barrier();
                 }
             }

@@ -76,9 +76,9 @@
 #include "bigmap_team.h"
 #include "kernels_big.h"
 #include "kernels_step.h"
+#include "search_game.h"
 #include "kernels_sokoban.h"
-#include "kernels_mdungeon.h"
-#include "kernels_ddave.h"
+#include "kernels_agents4.h"
 #include "kernels_smb.h"
 #include "kernels_step_solver.h"
 #include "kernels_search_async.h"
@@ -863,14 +863,19 @@ PCGRL_LOCAL int launch_smb(pcgrl_env* h, int32_t* sync, int list_a, int mode_a, 
 }
 #endif  // PART_SMB
 #if PCGRL_IN_PART(PART_SEARCH)
+// the handle's instantiation of k_search_async, and of the four-agent kernels that share a signature (k_sokoban has its hard list on top)
+typedef void (*AsyncKernel)(PcgrlParams, DevBufs, AsyncCtl, int, int, int, int, int, int, int32_t*, int, int, int, int, int, int);
+typedef void (*Agents4Kernel)(PcgrlParams, DevBufs, int, int, int, int, int, int, int32_t*, int);
+static AsyncKernel async_kernel(int prob) {
+    return prob == PCGRL_PROB_DDAVE ? k_search_async<PCGRL_PROB_DDAVE> : prob == PCGRL_PROB_MDUNGEON ? k_search_async<PCGRL_PROB_MDUNGEON> : k_search_async<PCGRL_PROB_SOKOBAN>;
+}
+static Agents4Kernel agents4_kernel(int prob) { return prob == PCGRL_PROB_DDAVE ? k_ddave<0> : k_mdungeon<0>; }
 PCGRL_LOCAL int search_device_setup(pcgrl_env* h) {   // the search kernels use most of a compute unit's LDS (heap + 64-bit-key table)
     const int lds = (int)((SOK_LDS_HEAP + 2 * SOK_LDS_TABLE) * 4);
-    const void* f = h->cfg.prob == PCGRL_SOKOBAN ? reinterpret_cast<const void*>(k_sokoban<0>)
-                  : h->cfg.prob == PCGRL_MDUNGEON ? reinterpret_cast<const void*>(k_mdungeon<0>) : reinterpret_cast<const void*>(k_ddave<0>);
+    const int prob = h->cfg.prob;                      // (PCGRL_SOKOBAN ... of the ABI are the kernels' PCGRL_PROB_* values)
+    const void* f = prob == PCGRL_PROB_SOKOBAN ? reinterpret_cast<const void*>(k_sokoban<0>) : reinterpret_cast<const void*>(agents4_kernel(prob));
     HIPCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    const void* fa = h->cfg.prob == PCGRL_SOKOBAN ? reinterpret_cast<const void*>(k_search_async<PCGRL_PROB_SOKOBAN>)
-                   : h->cfg.prob == PCGRL_MDUNGEON ? reinterpret_cast<const void*>(k_search_async<PCGRL_PROB_MDUNGEON>) : reinterpret_cast<const void*>(k_search_async<PCGRL_PROB_DDAVE>);
-    HIPCHK(hipFuncSetAttribute(fa, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(async_kernel(prob)), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     return PCGRL_OK;
 }
 // one launch of a tick of pcgrl_step_async (kernels_search_async.h).  small: the launch for the fresh jobs -- a few KB of LDS per
@@ -879,12 +884,7 @@ PCGRL_LOCAL int launch_search_async(pcgrl_env* h, int32_t* tickets, int list_a, 
     const int toff = small ? ASYNC_SMALL_HEAP : SOK_LDS_HEAP, tsize = small ? ASYNC_SMALL_TABLE : SOK_LDS_TABLE;
     const size_t lds = (size_t)(toff + 2 * tsize) * 4;
     const int grid = small ? ASYNC_SMALL_BLOCKS : SOK_BLOCKS;
-    if (h->P.prob == PCGRL_PROB_DDAVE)
-        hipLaunchKernelGGL(k_search_async<PCGRL_PROB_DDAVE>, dim3(grid), dim3(128), lds, st, h->P, h->B, h->async, list_a, mode_a, list_b, mode_b, parity, rst_list, tickets, clr, budget, resume, toff, tsize, small);
-    else if (h->P.prob == PCGRL_PROB_MDUNGEON)
-        hipLaunchKernelGGL(k_search_async<PCGRL_PROB_MDUNGEON>, dim3(grid), dim3(128), lds, st, h->P, h->B, h->async, list_a, mode_a, list_b, mode_b, parity, rst_list, tickets, clr, budget, resume, toff, tsize, small);
-    else
-        hipLaunchKernelGGL(k_search_async<PCGRL_PROB_SOKOBAN>, dim3(grid), dim3(128), lds, st, h->P, h->B, h->async, list_a, mode_a, list_b, mode_b, parity, rst_list, tickets, clr, budget, resume, toff, tsize, small);
+    hipLaunchKernelGGL(async_kernel(h->P.prob), dim3(grid), dim3(128), lds, st, h->P, h->B, h->async, list_a, mode_a, list_b, mode_b, parity, rst_list, tickets, clr, budget, resume, toff, tsize, small);
     HIPCHK(hipGetLastError());
     return PCGRL_OK;
 }
@@ -906,10 +906,8 @@ PCGRL_LOCAL int launch_search(pcgrl_env* h, int32_t* sync, int list_a, int mode_
         return launch_search_big_p<PCGRL_PROB_SOKOBAN>(h, sync, list_a, mode_a, list_b, mode_b, parity, rst_list, clr, st);
     }
     const size_t lds = h->B.sok_use_lds ? (size_t)(SOK_LDS_HEAP + 2 * SOK_LDS_TABLE) * 4 : 0;   // heap + 64-bit-key table
-    if (h->P.prob == PCGRL_PROB_DDAVE)
-        hipLaunchKernelGGL(k_ddave<0>, dim3(SOK_BLOCKS), dim3(128), lds, st, h->P, h->B, list_a, mode_a, list_b, mode_b, parity, rst_list, sync, clr);
-    else if (h->P.prob == PCGRL_PROB_MDUNGEON)
-        hipLaunchKernelGGL(k_mdungeon<0>, dim3(SOK_BLOCKS), dim3(128), lds, st, h->P, h->B, list_a, mode_a, list_b, mode_b, parity, rst_list, sync, clr);
+    if (h->P.prob != PCGRL_PROB_SOKOBAN)
+        hipLaunchKernelGGL(agents4_kernel(h->P.prob), dim3(SOK_BLOCKS), dim3(128), lds, st, h->P, h->B, list_a, mode_a, list_b, mode_b, parity, rst_list, sync, clr);
     else
         hipLaunchKernelGGL(k_sokoban<0>, dim3(SOK_BLOCKS), dim3(128), lds, st, h->P, h->B, list_a, mode_a, list_b, mode_b, parity, rst_list,
                            sync, sync + SOK_SY_WORDS, clr);

@@ -798,6 +798,29 @@ def test_ddave_generic_search_path(path, monkeypatch):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("prob,fixture,solver_cols", [("sokoban", "stats_sokoban_6x6.npz", slice(4, 6)),
+                                                      ("mdungeon", "stats_mdungeon_7x11_p5000.npz", slice(6, 11)),
+                                                      ("ddave", "stats_ddave_11x7_p5000.npz", slice(7, 11))], ids=["sokoban", "mdungeon", "ddave"])
+def test_search_global_arena_path(prob, fixture, solver_cols):
+    """A solver_power between 5001 and 16383 is beyond the LDS heap: heap and visited table live in the global arena and
+    k_sokoban / k_mdungeon / k_ddave run the generic search on lane 0.  The first 64 fixture levels with solver_power = 5001
+    against the oracle at that power (the fixtures' stored rows are for 5000)."""
+    _torch()
+    power = 5001
+    maps = np.load(os.path.join(G, fixture))["maps"][:64]
+    n, h, w = maps.shape
+    exp = np.array([ol.get_stats(prob, m, solver_power=power) for m in maps])
+    for k in range(solver_cols.start, solver_cols.stop):
+        assert len(np.unique(exp[:, k])) >= 2, k          # the searches ran and found different things
+    env = _make(prob, "wide", n, [dict(width=w, height=h), dict(solver_power=power)])
+    env.reset()
+    env.set_maps(maps)
+    got = env.stats.cpu().numpy().astype(np.int64)
+    assert env.check_status() == 0
+    assert np.array_equal(got, exp), np.nonzero((got != exp).any(1))[0]
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("path", sorted(glob.glob(os.path.join(G, "stats_smb_*.npz"))), ids=os.path.basename)
 def test_smb_search_fallback_path(path, monkeypatch):
     """k_smb runs the balance-1 play-through on a two-label heap of at most 4 095 slots in LDS and repeats a search whose
