@@ -76,14 +76,21 @@ class Row(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ROW_FIELDS] + [("actions_i64", C.c_int32)]
 
 
-ABI_VERSION = 15         # include/pcgrl_hip.h PCGRL_ABI_VERSION (pcgrl_bind_row is an addition within 15: found by its symbol)
+# include/pcgrl_hip.h pcgrl_render_desc: what pcgrl_render draws (device pointers; indices None = 0 .. count-1)
+class RenderDesc(C.Structure):
+    _fields_ = [("indices", C.c_void_p), ("count", C.c_int32), ("tiles", C.c_void_p), ("tile_size", C.c_int32),
+                ("border_x", C.c_int32), ("border_y", C.c_int32), ("border_tile", C.c_int32), ("cursor", C.c_int32),
+                ("grid_rows", C.c_int32), ("grid_cols", C.c_int32), ("out", C.c_void_p)]
+
+
+ABI_VERSION = 15         # include/pcgrl_hip.h PCGRL_ABI_VERSION (pcgrl_bind_row, pcgrl_render are additions within 15: found by their symbols)
 EXPORTS = ("pcgrl_abi_version", "pcgrl_error_string", "pcgrl_last_hip_error", "pcgrl_query_layout", "pcgrl_create",
            "pcgrl_destroy", "pcgrl_bind", "pcgrl_configure", "pcgrl_seed", "pcgrl_set_tile_probs", "pcgrl_reset",
            "pcgrl_step", "pcgrl_set_maps", "pcgrl_observe", "pcgrl_action_map", "pcgrl_status", "pcgrl_profile",
            "pcgrl_profile_read", "pcgrl_bind_episode_stats", "pcgrl_seed_words", "pcgrl_rollout", "pcgrl_bind_observation", "pcgrl_selftest_heap",
            "pcgrl_tuning_defaults", "pcgrl_set_tuning", "pcgrl_clear_status", "pcgrl_step_flat",
            "pcgrl_async_bytes", "pcgrl_bind_async", "pcgrl_step_async", "pcgrl_async_flush", "pcgrl_step_multi", "pcgrl_selftest_step_pool", "pcgrl_step_threads", "pcgrl_selftest_range_reward",
-           "pcgrl_bind_row")
+           "pcgrl_bind_row", "pcgrl_render")
 NPHASE = 6
 # the six intervals between the seven event marks of a step; sokoban: update, stats, reset, solver, reset2, solver2;
 # other problems: update, stats(+resets), -, reset (only with PCGRL_INLINE_RESET=0), -, -
@@ -193,6 +200,7 @@ def load():
     L.pcgrl_observe.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
     L.pcgrl_bind_observation.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     L.pcgrl_bind_row.argtypes = [C.c_void_p, C.POINTER(Row)]
+    L.pcgrl_render.argtypes = [C.c_void_p, C.POINTER(RenderDesc), C.c_void_p]
     L.pcgrl_action_map.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pcgrl_step_flat.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pcgrl_selftest_heap.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

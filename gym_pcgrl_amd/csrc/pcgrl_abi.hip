@@ -86,6 +86,7 @@
 #include "kernels_search_big.h"
 #if PCGRL_IN_PART(PART_CORE)
 #include "kernels_misc.h"
+#include "kernels_render.h"      // (beside k_obs's launcher: the core part holds both picture writers)
 #endif
 
 // ------------------------------------------------------------------------------------------
@@ -1511,6 +1512,46 @@ int pcgrl_observe(pcgrl_env* h, uint8_t* out, int32_t out_h, int32_t out_w, int3
     int rc = obs_spec(h, out, out_h, out_w, centered, pad_value, onehot, &S);
     if (rc) return rc;
     return launch_obs(h, S, (hipStream_t)stream);
+}
+
+int pcgrl_render(pcgrl_env* h, const pcgrl_render_desc* d, void* stream) {
+    if (!h || !h->bound || !h->was_reset) return PCGRL_ESTATE;
+    if (!d || !d->tiles || !d->out || d->count < 1) return PCGRL_EINVAL;
+    const PcgrlParams& P = h->P;
+    if (d->tile_size < 1 || d->tile_size > 64 || d->border_tile < 0 || d->border_tile >= P.ntiles) return PCGRL_EINVAL;
+    if (d->border_x < 0 || d->border_x > 255 || d->border_y < 0 || d->border_y > 255) return PCGRL_EINVAL;
+    if (d->cursor != 0 && d->cursor != 1) return PCGRL_EINVAL;
+    if (d->cursor && P.rep == PCGRL_REP_WIDE) return PCGRL_EINVAL;        // no cursor to frame (wide_rep.py:42-45)
+    if (d->grid_rows < 0 || d->grid_cols < 0 || (d->grid_rows == 0) != (d->grid_cols == 0)) return PCGRL_EINVAL;
+    const bool grid = d->grid_rows > 0;
+    if (grid && (long long)d->grid_rows * d->grid_cols < (long long)d->count) return PCGRL_EINVAL;
+    if (((uintptr_t)d->out & 15) != 0) return PCGRL_EINVAL;
+    DeviceGuard guard(h->device);
+    RenderArgs A;
+    A.map = h->B.map; A.pos = d->cursor ? h->B.pos : nullptr; A.indices = d->indices; A.tiles = d->tiles; A.out = d->out;
+    A.cells = grid ? (long long)d->grid_rows * d->grid_cols : (long long)d->count;
+    A.N = P.num_envs; A.W = P.width; A.H = P.height; A.ntiles = P.ntiles; A.ts = d->tile_size;
+    A.bx = d->border_x; A.by = d->border_y; A.border_tile = d->border_tile;
+    A.count = d->count; A.gcols = grid ? d->grid_cols : 1;
+    const int ts = d->tile_size, Wp = P.width + 2 * d->border_x, Hp = P.height + 2 * d->border_y;
+    // a unit: whole tile rows of one image, RENDER_BAND_BYTES where the image has them, their tile ids within RENDER_IDS_MAX
+    const size_t tile_row_bytes = (size_t)ts * Wp * ts * 3;
+    size_t band = RENDER_BAND_BYTES / tile_row_bytes;
+    if (band > (size_t)(RENDER_IDS_MAX / Wp)) band = RENDER_IDS_MAX / Wp;      // (Wp <= 4096 + 2 * 255)
+    band = band < 1 ? 1 : (band > (size_t)Hp ? (size_t)Hp : band);
+    A.band = (int)band; A.nbands = (Hp + A.band - 1) / A.band;
+    const bool fast = (ts * 3) % 16 == 0;
+    A.pal_bytes = fast ? P.ntiles * ts * ts * 3 : 0;
+    const size_t lds = (size_t)A.pal_bytes + align_up((size_t)A.band * Wp, 16);
+    const long long units = A.cells * A.nbands;
+    const unsigned blocks = (unsigned)(units < 8192 ? units : 8192);           // (more units than that: a block takes several, the palette staged once)
+    hipStream_t st = (hipStream_t)stream;
+    if (fast) {
+        { const int rc = lds_cap<k_render<1>>(h->device, lds); if (rc) return rc; }      // (64-pixel tiles: a palette beyond 64 KB)
+        hipLaunchKernelGGL(k_render<1>, dim3(blocks), dim3(256), lds, st, A);
+    } else hipLaunchKernelGGL(k_render<0>, dim3(blocks), dim3(256), lds, st, A);
+    HIPCHK(hipGetLastError());
+    return PCGRL_OK;
 }
 
 int pcgrl_bind_observation(pcgrl_env* h, uint8_t* out, int32_t out_h, int32_t out_w, int32_t centered, int32_t pad_value, int32_t onehot,

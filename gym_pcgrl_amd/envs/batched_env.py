@@ -709,6 +709,7 @@ class BatchedPcgrlEnv:
     def set_graphics(self, graphics):
         """Tile pictures for render(): None = the reference's grey fallback (the default), "drawn" = the package's own
         pictures (envs/tile_art.py), or a dict {tile name: tile_size x tile_size x 3 image} -- the reference's `_graphics`."""
+        self._palette = None               # (render_batch's device copy of the pictures: built again at the next call)
         if graphics is None:
             self._graphics = None
             return
@@ -756,6 +757,81 @@ class BatchedPcgrlEnv:
             return Image.fromarray(img, "RGB")
         except ImportError:
             return img
+
+    def _render_palette(self):
+        """The tile pictures render() draws with -- the grey fallback or the `_graphics` dict, at the problem's tile size -- as a
+        device tensor uint8 [tiles, ts, ts, 3]; built once, dropped by set_graphics() and by a change of the tile size."""
+        ts = int(self._prob._tile_size)
+        cached = getattr(self, "_palette", None)
+        if cached is not None and cached[0] == ts:
+            return cached[1]
+        tiles = self._prob.tiles
+        gfx = getattr(self, "_graphics", None)
+        if gfx is None:
+            grey = np.array([int(i * 255 / len(tiles)) for i in range(len(tiles))], dtype=np.uint8)
+            pal = np.broadcast_to(grey[:, None, None, None], (len(tiles), ts, ts, 3))
+        else:
+            pal = np.stack([np.asarray(gfx[t], dtype=np.uint8)[:ts, :ts, :3] for t in tiles])
+            if pal.shape != (len(tiles), ts, ts, 3):
+                raise ValueError("tile pictures of %s for a tile size of %d" % (pal.shape[1:], ts))
+        dev = self._torch.as_tensor(np.ascontiguousarray(pal)).to(self.device)
+        self._palette = (ts, dev)
+        return dev
+
+    def render_batch(self, indices=None, out=None, grid=None):
+        """The pictures render("rgb_array", i) draws, for many environments in one kernel launch on the device (pcgrl_render): a
+        uint8 device tensor [K, Hp, Wp, 3], or with `grid` one picture [rows * Hp, cols * Wp, 3] with picture k in cell
+        (k // cols, k % cols) and black cells behind the last one.
+        indices: None = every environment; a sequence / numpy array, checked here (IndexError outside [0, num_envs)); or an int32 /
+        int64 device tensor, used as it is without a look at its values -- an entry outside the range gives a black picture.  Any
+        order, repeats, more entries than environments.
+        grid: None = stacked; True = stable-baselines' tile_images rule (rendering.grid_shape); or (rows, cols).
+        out: a contiguous, 16-byte aligned uint8 tensor of exactly the result's shape on this device (ValueError otherwise); every
+        byte of it is written.  The call reads the state as it is and does not wait for the device."""
+        from .. import rendering
+        torch = self._torch
+        if self._handle is None or self._needs_reset:
+            raise RuntimeError("reset() must be called before render_batch()")
+        keep = None
+        if indices is None:
+            count = self.num_envs
+        elif torch.is_tensor(indices) and indices.device == self.device:
+            if indices.dim() != 1 or indices.dtype not in (torch.int32, torch.int64):
+                raise ValueError("indices: a one-dimensional int32 or int64 tensor")
+            if indices.dtype == torch.int64:       # (a value beyond 32 bits must not wrap into the range)
+                indices = indices.clamp(-1, self.num_envs)
+            keep = indices.to(torch.int32).contiguous()
+            count = int(keep.shape[0])
+        else:
+            idx = np.asarray(indices.cpu() if torch.is_tensor(indices) else indices)
+            if idx.ndim != 1 or (idx.size and idx.dtype.kind not in "iu"):
+                raise ValueError("indices: a one-dimensional sequence of integers")
+            if idx.size and (int(idx.min()) < 0 or int(idx.max()) >= self.num_envs):
+                raise IndexError("render_batch: environment index outside [0, %d)" % self.num_envs)
+            keep = torch.as_tensor(np.ascontiguousarray(idx, dtype=np.int32)).to(self.device)
+            count = int(idx.size)
+        if count < 1:
+            raise ValueError("render_batch: no environment chosen")
+        cells = rendering.resolve_grid(grid, count)
+        ts = int(self._prob._tile_size)
+        bx, by = (int(v) for v in self._prob._border_size)
+        h, w = (int(v) for v in self._bufs["map"].shape[1:])
+        shape = rendering.picture_shape(h, w, (bx, by), ts, count, cells)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=self.device)
+        elif (not torch.is_tensor(out) or out.dtype != torch.uint8 or tuple(out.shape) != tuple(shape) or not out.is_contiguous()
+              or out.device != self.device or out.data_ptr() % 16):
+            raise ValueError("render_batch: out must be a contiguous, 16-byte aligned uint8 tensor of shape %s on %s" % (tuple(shape), self.device))
+        pal = self._render_palette()
+        d = _lib.RenderDesc()
+        d.indices, d.count = (keep.data_ptr() if keep is not None else None), count
+        d.tiles, d.tile_size = pal.data_ptr(), ts
+        d.border_x, d.border_y = bx, by
+        d.border_tile, d.cursor = self._prob.tiles.index(self._prob._border_tile), int(bool(self._rep.has_pos))
+        d.grid_rows, d.grid_cols = cells if cells is not None else (0, 0)
+        d.out = out.data_ptr()
+        _lib.check(self._lib.pcgrl_render(self._handle, C.byref(d), self._stream()), "pcgrl_render")
+        return out
 
     def close(self):
         self._free()

@@ -10,7 +10,8 @@ The reference wraps every worker in RenderMonitor (a stable-baselines Monitor, u
 sums per environment (`BatchedPcgrlEnv.enable_episode_stats`); `monitor=True` (the default when `log_dir` is given,
 as in the reference) adds the same `episode` entry to the infos of finished environments and `episode_stats()`
 returns them as device tensors without any host round trip.  `render` and `max_step` are accepted and ignored
-(rendering is outside the accelerated path; `max_step` is unused by the reference wrapper too, utils.py:21-29).
+(nothing is drawn per step -- `get_images()` / `render()` draw the levels on the device when asked; `max_step` is unused by the
+reference wrapper too, utils.py:21-29).
 """
 import numpy as np
 
@@ -71,6 +72,19 @@ class BatchedVecEnv:
     def episode_stats(self):
         """Device tensors of the in-kernel episode statistics (see BatchedPcgrlEnv.episode_stats)."""
         return self.env.pcgrl_env.episode_stats()
+
+    def get_images(self, indices=None):
+        """The environments' level pictures as one uint8 device tensor [K, Hp, Wp, 3] (VecEnv.get_images; BatchedPcgrlEnv.render_batch)."""
+        return self.env.pcgrl_env.render_batch(indices)
+
+    def render(self, mode="rgb_array", indices=None):
+        """VecEnv.render: the pictures tiled into one image (stable-baselines' tile_images), drawn on the device -- by default of the
+        first 16 environments.  "human" returns the same tensor: this package opens no window."""
+        if mode not in ("rgb_array", "human"):
+            raise ValueError("unsupported render mode %r" % (mode,))
+        if indices is None:
+            indices = list(range(min(self.num_envs, 16)))
+        return self.env.pcgrl_env.render_batch(indices, grid=True)
 
     def step_async(self, actions):
         self._pending = self.step(actions)

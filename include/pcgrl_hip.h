@@ -40,7 +40,8 @@ extern "C" {
  *    grew (prob_width, prob_height); maps up to 255 x 255, search levels up to 16 384 bordered cells, solver_power up to 1 000 000.
  * 15: without auto_reset the heat map holds 32-bit counts (an episode goes on past done); max_changes beyond 65 535 there.
  *     Still 15: + pcgrl_row / pcgrl_bind_row -- purely additive (one struct, one entry point; no existing struct or signature
- *     changed), so the number stays; a caller detects the feature by the symbol pcgrl_bind_row. */
+ *     changed), so the number stays; a caller detects the feature by the symbol pcgrl_bind_row.
+ *     Still 15: + pcgrl_render_desc / pcgrl_render -- additive in the same way; a caller detects it by the symbol pcgrl_render. */
 #define PCGRL_ABI_VERSION 15
 #define PCGRL_OK 0
 #define PCGRL_EINVAL (-1)   /* bad argument / unsupported configuration */
@@ -247,6 +248,30 @@ typedef struct pcgrl_row {
  * outputs and ignores the binding (its tape is int32); pcgrl_reset / pcgrl_set_maps write no row.  PCGRL_ESTATE: ep_return /
  * ep_length without bound episode statistics. */
 int pcgrl_bind_row(pcgrl_env* env, const pcgrl_row* row);
+/* Pictures of levels, drawn on the device: PcgrlEnv.render (pcgrl_env.py:161-175) = Problem.render (problem.py:134-156: a frame of
+ * the border tile, then every cell the picture of its tile) + the representation's cursor frame (narrow_rep.py:128-142,
+ * turtle_rep.py:142) for `count` chosen environments in one launch.  The reference draws one environment per call on the host.
+ * The picture of an environment is u8 [(H + 2 border_y) * ts][(W + 2 border_x) * ts][3], ts = tile_size: the border tile on a frame
+ * of border_y rows and border_x columns of cells, the map's tiles inside; cursor = 1 (a representation with `pos` only): the two
+ * outermost pixel rows and columns of the cursor's cell are (255, 0, 0).
+ * out, grid_rows == grid_cols == 0: the pictures one after the other, u8 [count][Hp * ts][Wp * ts][3]; else ONE picture
+ * u8 [grid_rows * Hp * ts][grid_cols * Wp * ts][3] with picture k in cell (k / grid_cols, k % grid_cols).  Every byte of `out` is
+ * written (it may be uninitialised): cells beyond `count` are zero, and so is the picture of an index outside [0, N).
+ * Asynchronous on the stream; reads the state as it is (pending asynchronous searches are not flushed) and writes nothing but `out`.
+ * PCGRL_ESTATE before the first pcgrl_reset.  PCGRL_EINVAL: tiles or out NULL, count < 1, tile_size outside 1..64, border_tile not a
+ * tile, a border outside 0..255, a grid with fewer cells than count (or only one of its sides 0), out not 16-byte aligned, cursor = 1
+ * on a representation without `pos`.  Where tile_size * 3 is a multiple of 16 (the reference's 16-pixel tiles) the pictures leave as
+ * 16-byte stores (csrc/kernels_render.h); any other size is drawn byte by byte. */
+typedef struct pcgrl_render_desc {
+    const int32_t* indices;         /* DEVICE i32 [count]: the environments, in any order, repeats allowed; NULL = 0 .. count-1 */
+    int32_t count;
+    const uint8_t* tiles;           /* DEVICE u8 [number of tiles][tile_size][tile_size][3]: the tile pictures */
+    int32_t tile_size;
+    int32_t border_x, border_y, border_tile, cursor;
+    int32_t grid_rows, grid_cols;
+    uint8_t* out;                   /* DEVICE, 16-byte aligned */
+} pcgrl_render_desc;
+int pcgrl_render(pcgrl_env* env, const pcgrl_render_desc* d, void* stream);
 /* ActionMap.step for the wide representation (wrappers.py:139-154): flat DEVICE i32 [N] index into
  * (H, W, tiles) -> xyv DEVICE i32 [N,3] = (x, y, tile), the action pcgrl_step takes. */
 int pcgrl_action_map(pcgrl_env* env, const int32_t* flat, int32_t* xyv, void* stream);
