@@ -199,6 +199,14 @@ class OracleEnv:
         lib(self._big).orc_reset(self._h)
         return self.obs()
 
+    def set_map(self, m):
+        """Replace the map and recompute the current stats (what BatchedPcgrlEnv.set_maps does to one environment): the episode's
+        counters, heat map and start stats stay."""
+        L = lib(self._big)
+        m = np.ascontiguousarray(m, dtype=np.uint8)
+        assert m.shape == (L.orc_map_height(self._h), L.orc_map_width(self._h)), m.shape
+        L.orc_set_map(self._h, _p(m))
+
     def step(self, action):
         a = np.zeros(MAX_ACTION, np.int32)
         a[:np.size(action)] = np.asarray(action).ravel()

@@ -6,6 +6,8 @@ fuzz_case(rs, ...)      one random (problem, representation, map size, parameter
 fullsize_case(...)      a benchmark configuration at its real batch size (the paths only large batches take: paired certain
                         resets, every bucket in use, 512 environments per persistent block); a sample of environments
                         compared with the oracle at every step
+search_game_case(...)   chosen levels of a search problem through one stepping route (steps, one rollout, asynchronous ticks): four
+                        scripted writes per environment that compute the level, its neighbour and both again
 """
 import numpy as np
 
@@ -408,6 +410,122 @@ def _async_rows(env, ti, keys):
     return (b["reward"][ti].cpu().numpy(), b["done"][ti].cpu().numpy(), inf, b["pos"][ti].cpu().numpy().astype(np.int64),
             b["heatmap"][ti].cpu().numpy().astype(np.int64), b["map"][ti].cpu().numpy())
 
+
+def flip_tape(maps, cells):
+    """For levels `maps` [N, H, W] and one cell (x, y) per level that is empty or solid in it: the neighbours M' (that cell flipped
+    between empty and solid) and the wide actions [4, N, 3] that write the cell back to its value in M, to M' again, and both once
+    more -- the level itself is what steps 1 and 3 compute, its neighbour steps 2 and 4."""
+    maps = np.ascontiguousarray(maps, dtype=np.uint8)
+    n = len(maps)
+    x, y = np.asarray(cells)[:, 0], np.asarray(cells)[:, 1]
+    v = maps[np.arange(n), y, x]
+    assert (v <= 1).all()
+    start = maps.copy()
+    start[np.arange(n), y, x] = 1 - v
+    acts = np.stack([np.stack([x, y, v if t % 2 == 0 else 1 - v], 1) for t in range(4)]).astype(np.int32)
+    return start, acts
+
+
+def search_game_case(prob, w, h, power, maps, cells, route, seed0=7000, tuning=None, pop_budget=4, nslots=8, labels=None):
+    """Chosen levels through one stepping route of a search problem against the oracle (tests/test_gpu_search_games.py).  One handle
+    of N wide environments with change_percentage 1.0; set_maps() puts every environment one write away from its level (flip_tape)
+    and four actions compute the level, its neighbour, and both again.  route: "step" -- step() four times; "rollout" -- the four
+    actions as one rollout(); "async" -- enable_async(nslots) and tick(pop_budget) until every environment has completed the four
+    steps and nothing is pending.  Reward, done and every info column of every step, and the map, must equal the oracle's
+    (OracleEnv seeded seed0 + i, reset(), set_map(), the four steps with auto-reset); check_status() must be 0.  labels: a name per
+    level for the message of a mismatch.  Returns the asynchronous counters (route "async") or None."""
+    import torch
+    from gym_pcgrl_amd.envs import BatchedPcgrlEnv
+    n = len(maps)
+    calls = [dict(width=w, height=h), dict(change_percentage=1.0, solver_power=power)]
+    start, acts = flip_tape(maps, cells)
+    exp = []
+    for i in range(n):
+        o = ol.OracleEnv(prob, "wide")
+        for kw in calls:
+            o.adjust_param(**kw)
+        o.seed(seed0 + i)
+        o.reset()
+        o.set_map(start[i])
+        exp.append(o.rollout(acts[:, i]))
+    e_rew = np.stack([x["reward"] for x in exp], 1)           # [4, N]
+    e_done = np.stack([x["done"] for x in exp], 1)
+    e_info = np.stack([x["info"] for x in exp], 1)            # [4, N, keys]
+    e_maps = np.stack([x["maps"] for x in exp], 1)            # [4, N, H, W]
+
+    def check(what, got, want, t):
+        got, want = np.asarray(got), np.asarray(want)
+        bad = np.nonzero((got != want).reshape(n, -1).any(1))[0]
+        if bad.size:
+            i = int(bad[0])
+            raise AssertionError("%s differs at step %d (route %s, %s %dx%d power %d) for %d levels: %s; level %d: got %s, the oracle %s"
+                                 % (what, t, route, prob, w, h, power, bad.size, [(int(j), labels[j] if labels else "") for j in bad[:8]],
+                                    i, got[i].tolist(), want[i].tolist()))
+
+    env = BatchedPcgrlEnv(prob=prob, rep="wide", num_envs=n, seed=seed0, tuning=tuning)
+    try:
+        for kw in calls:
+            env.adjust_param(**kw)
+        env.reset()
+        keys = list(env._prob.info_keys) + ["iterations", "changes"]
+        cnt = None
+        if route == "async":
+            assert env.enable_async(nslots), "no asynchronous form for this configuration"
+        env.set_maps(start)
+        if route == "step":
+            for t in range(4):
+                obs, rew, done, info = env.step(acts[t])
+                check("done", done.cpu().numpy(), e_done[t], t)
+                check("reward", rew.cpu().numpy(), e_rew[t], t)
+                check("info", np.stack([info[k].cpu().numpy() for k in keys], 1).astype(np.int64), e_info[t], t)
+                check("map", obs["map"].cpu().numpy(), e_maps[t], t)
+        elif route == "rollout":
+            rew, done, info = env.rollout(torch.as_tensor(acts, device=env.device))
+            got_info = np.stack([info[k].view(4, n).cpu().numpy() for k in keys], 2).astype(np.int64)
+            for t in range(4):
+                check("done", done[t].cpu().numpy(), e_done[t], t)
+                check("reward", rew[t].cpu().numpy(), e_rew[t], t)
+                check("info", got_info[t], e_info[t], t)
+            check("map", env._bufs["map"].cpu().numpy(), e_maps[3], 3)
+        elif route == "async":
+            ti = torch.arange(n, device=env.device)
+            ar = np.arange(n)
+            ntaken, ngot = np.zeros(n, np.int64), np.zeros(n, np.int64)
+            pending = np.zeros(n, bool)
+            got = [[np.zeros_like(e[t]) for t in range(4)] for e in (e_rew, e_done, e_info, e_maps)]
+            # every search ends within 4 * power pops; a tick gives a suspended one pop_budget of them (and the end of an episode takes one more)
+            max_ticks = 4 * (4 * power // pop_budget + 4) + 64
+            for tick in range(max_ticks):
+                a = acts[np.minimum(ntaken, 3), ar]              # past its four steps an environment repeats the last write
+                _obs, _rew, _done, _info, pend = env.tick(a, pop_budget=pop_budget)
+                after = pend.cpu().numpy() != 0
+                ntaken += ~pending
+                fresh = ~after & (ngot < 4)
+                if fresh.any():
+                    rew_k, done_k, info_k, _pos, _heat, map_k = _async_rows(env, ti, keys)
+                    for j in np.nonzero(fresh)[0]:
+                        for dst, src in zip(got, (rew_k, done_k, info_k, map_k)):
+                            dst[ngot[j]][j] = src[j]
+                ngot += ~after
+                pending = after
+                if not after.any() and (ngot >= 4).all():
+                    break
+            else:
+                raise AssertionError("still pending after %d ticks: %s" % (max_ticks, np.nonzero(pending | (ngot < 4))[0][:8]))
+            assert (ntaken >= ngot).all()
+            for t in range(4):
+                check("done", got[1][t] != 0, e_done[t], t)
+                check("reward", got[0][t], e_rew[t], t)
+                check("info", got[2][t], e_info[t], t)
+                check("map", got[3][t], e_maps[t], t)
+            cnt = env.async_counters()
+            cnt["ticks"] = tick + 1
+        else:
+            raise ValueError(route)
+        assert env.check_status() == 0
+        return cnt
+    finally:
+        env.close()
 
 
 def expected_image(m, pos, oh, ow, centered, pad, depth):
