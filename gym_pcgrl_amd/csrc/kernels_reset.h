@@ -10,8 +10,7 @@ __global__ __launch_bounds__(PCGRL_BLOCK) void k_reset(PcgrlParams P, DevBufs B,
     if (clear_parity >= 0 && blockIdx.x == 0) wl_clear(B, clear_parity);
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int W = P.width, H = P.height, cells = W * H;
-    const int tiles_bytes = (cells + 15) & ~15;
-    uint32_t* mt = reinterpret_cast<uint32_t*>(smem + (size_t)wv * (PCGRL_MT_N * 4 + tiles_bytes));
+    uint32_t* mt = reinterpret_cast<uint32_t*>(smem + (size_t)wv * reset_stage_bytes(cells));
     uint8_t* tiles = reinterpret_cast<uint8_t*>(mt + PCGRL_MT_N);
     __shared__ int s_pref[WL_NSHARD + 1];
     const int n = wl_load_prefix(B, parity, list, s_pref);
@@ -40,7 +39,7 @@ __global__ __launch_bounds__(PCGRL_BLOCK) void k_planes_from_map(PcgrlParams P, 
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int cells = P.width * P.height;
-    uint8_t* tiles = smem + (size_t)wv * ((cells + 15) & ~15);
+    uint8_t* tiles = smem + (size_t)wv * reset_tile_bytes(cells);
     for (int e = blockIdx.x * 4 + wv; e < P.num_envs; e += gridDim.x * 4) {
         for (int c = lane; c < cells; c += 64) {
             uint8_t t = src[(size_t)e * cells + c];

@@ -350,8 +350,7 @@ __global__ __launch_bounds__(PCGRL_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 
     const int lane64 = threadIdx.x & 63, wv = threadIdx.x >> 6, gw = lane64 / G;
     const int NPL = (PROB == PCGRL_PROB_BINARY) ? 1 : 3;
     const int W = P.width, H = P.height;
-    const int tiles_bytes = (W * H + 15) & ~15;
-    uint32_t* mt = reinterpret_cast<uint32_t*>(smem + (size_t)wv * (PCGRL_MT_N * 4 + tiles_bytes));
+    uint32_t* mt = reinterpret_cast<uint32_t*>(smem + (size_t)wv * reset_stage_bytes(W * H));
     uint8_t* tiles = reinterpret_cast<uint8_t*>(mt + PCGRL_MT_N);
     const MaskT rowmask = row_valid<MaskT>(g.lane, W, H);
     for (int wid = blockIdx.x * (PCGRL_BLOCK / 64) + wv; wid < w_total; wid += gridDim.x * (PCGRL_BLOCK / 64)) {
@@ -506,7 +505,7 @@ __global__ __launch_bounds__(NWAVES * 64) void k_stats_wide(PcgrlParams P, DevBu
     const int n = n_rst + n_chg;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int W = P.width, H = P.height;
-    const int wave_lds = PCGRL_MT_N * 4 + ((W * H + 15) & ~15);
+    const int wave_lds = reset_stage_bytes(W * H);
     uint32_t* mt = reinterpret_cast<uint32_t*>(smem);
     uint8_t* tiles = reinterpret_cast<uint8_t*>(mt + PCGRL_MT_N);
     // the block-wide reset's buffers (raw MT19937 words, the map's bit string): in the scratch sets of wavefronts 1 .. NWAVES-1,

@@ -116,7 +116,7 @@ struct pcgrl_env {
     int alloc_solver_power;
     // developer switches (pcgrl_set_tuning; A/B measurements and tests), resolved at pcgrl_bind
     pcgrl_tuning tun;
-    int no_wide, wide_waves, wide_grid, wide_pairs, fused_zelda, no_fused, step_epb, smb_heap, obs_at_end;
+    int no_wide, wide_waves, wide_grid, wide_pairs, fused_zelda, no_fused, step_epb, smb_heap, obs_at_end, no_inc;
     int profiling;
     int obs_incremental;       // pcgrl_bind_observation(incremental): the bound target is the library's to update in place
     const uint8_t* obs_synced; // the buffer that holds the image of the current state (written by the last step / reset), or NULL
@@ -132,6 +132,8 @@ struct pcgrl_env {
     size_t ev_used;
     int prof_steps;
 };
+// gen_map of the reset kernels: draw a new map (1) or start again from the kept one (representation.py:41)
+static int gen_flag(const pcgrl_env* h) { return (h->P.random_start || !h->has_old) ? 1 : 0; }
 #define PCGRL_NPHASE 6   /* intervals between the 7 event marks of step_one (names: _lib.PHASES) */
 static int prof_mark(pcgrl_env* h, hipStream_t st) {
     if (!h->profiling) return PCGRL_OK;
@@ -239,23 +241,22 @@ static int wl_capacity(int num_envs, int list) {
 }
 static size_t wl_list_bytes(int num_envs, int list) { return align_up((size_t)WL_NSHARD * wl_capacity(num_envs, list) * 4, 256); }
 #define SOK_BLOCKS 256   /* resident solver blocks (one per CU: heap + table fill most of its LDS) */
-static size_t wl_bytes(const pcgrl_config* c) {
-    size_t b = WL_CNT_BYTES + 256;
-    for (int k = 0; k < WL_NLIST; k++) b += wl_list_bytes(c->num_envs, k);
-    return b;
-}
-// per-environment agent results + counters, and the scheduling words of the two solver launches of a step
-static size_t sok_sync_bytes() { return align_up(2 * (size_t)(SOK_SY_WORDS + SOK_HARD_CAP) * 4, 256); }
-static size_t sok_sched_bytes(int num_envs) { return align_up((size_t)num_envs * 18 * 4, 256) + sok_sync_bytes(); }
+// scheduling words of the search problems.  Per environment (DevBufs::sok_res / sok_cnt / sok_stop): 4 agents x [win, h, depth, exhausted],
+// how many agents have reported, the stop level.  Per step: the sync words of its two solver launches.
+enum { SOK_RES_WORDS = 16, SOK_CNT_WORDS = 1, SOK_STOP_WORDS = 1 };
 static int sok_table_size(int power) { int t = 1024; while (t < 2 * power) t <<= 1; return t; }
+// heap + table of a compact search: in LDS up to SOK_LDS_POWER (smb has its own heap split, kernels_smb.h), else per resident block in scratch
+static bool sok_in_lds(const pcgrl_config* c) { return c->solver_power <= SOK_LDS_POWER || c->prob == PCGRL_SMB; }
+static size_t sok_heap_bytes(int power) { return align_up((4 * (size_t)power + 4) * 4, 256); }
 // Node pool of one resident solver block: 4 children per pop of the full search -- and never less than the private
 // small-tier pools of k_step_solver (SS_SEARCH_WAVES wavefronts x SS_SMALL_NODES at pool + wv * SS_SMALL_NODES), so that a
 // small solver_power cannot make them spill into the next block's pool.
-static size_t sok_pool_nodes(int power, int prob = -1) {
-    if (prob == PCGRL_SMB)     // k_smb: up to SMB_MAX_WAVES searches per block, each with its own arena (kernels_smb.h)
-        return (SMB_MAX_WAVES * smb_wave_arena_bytes(power) + sizeof(SokNode) - 1) / sizeof(SokNode);
-    const size_t full = 4 * (size_t)power + 4, small = (size_t)SS_SEARCH_WAVES * SS_SMALL_NODES;
-    return full > small ? full : small;
+static size_t sok_pool_bytes(const pcgrl_config* c) {           // (rounded to whole nodes and to 256 bytes; an MdNode is as large as a SokNode)
+    const size_t full = 4 * (size_t)c->solver_power + 4, small = (size_t)SS_SEARCH_WAVES * SS_SMALL_NODES;
+    size_t nodes = full > small ? full : small;
+    if (c->prob == PCGRL_SMB)     // k_smb: up to SMB_MAX_WAVES searches per block, each with its own arena (kernels_smb.h)
+        nodes = (SMB_MAX_WAVES * smb_wave_arena_bytes(c->solver_power) + sizeof(SokNode) - 1) / sizeof(SokNode);
+    return align_up(nodes * sizeof(SokNode), 256);
 }
 static_assert(SS_SMALL_NODES >= 4 * SS_SMALL_POPS + 4, "a small-tier search pushes up to four nodes per pop");
 // rows of the champion component per environment (binary: the row-bitboard maps, and maps beyond 64 x 64 of up to 256 per side with at
@@ -270,20 +271,13 @@ static size_t champ_bytes(const pcgrl_config* c) {
     if (c->height <= 16) return (c->width <= 32 && c->num_envs <= WL_INC_ENV_MASK) ? align_up((size_t)c->num_envs * 64, 256) : 0;
     return c->num_envs <= WL_INC64_ENV_MASK ? align_up((size_t)c->num_envs * 64 * (c->width > 32 ? 8 : 4), 256) : 0;
 }
-// draw cache of the narrow representation (DevBufs::fifo, fifo_tag)
-static size_t fifo_words_bytes(const pcgrl_config* c) { return c->rep == PCGRL_NARROW ? align_up((size_t)c->num_envs * PCGRL_FIFO_N * 4, 256) : 0; }
-static size_t fifo_bytes(const pcgrl_config* c) { return c->rep == PCGRL_NARROW ? fifo_words_bytes(c) + align_up((size_t)c->num_envs * 4, 256) : 0; }
-static size_t scratch_bytes_base(const pcgrl_config* c);
-static size_t wide_sync_bytes(const pcgrl_config* c) { return (c->prob == PCGRL_BINARY && c->height > 16 && !big_map(c)) ? align_up((size_t)c->num_envs * 16, 256) : 0; }
-static size_t scratch_bytes(const pcgrl_config* c) { return scratch_bytes_base(c) + champ_bytes(c) + fifo_bytes(c) + wide_sync_bytes(c); }
 // The arena of the general searches (search_big.h): per resident block a node pool (4 children per pop), a 64-bit heap and a
 // visited table of 32-bit node indices.  As many blocks as fit a 6 GB budget (at most SOK_BLOCKS, at least 4).
 static BigArenaDims big_arena_of(const pcgrl_config* c) {
     BigArenaDims A;
     const int cells = (c->width + 2) * (c->height + 2), nwb = (cells + 63) / 64, inner = c->width * c->height;
     A.nodes_cap = 4 * c->solver_power + 4;
-    A.tsize = 1024;
-    while (A.tsize < 2 * c->solver_power) A.tsize <<= 1;
+    A.tsize = sok_table_size(c->solver_power);
     // sokb_init_deadlocks keeps its corner list (16-bit cells, fewer than `cells` of them) in the block's heap before the search
     // starts: heap + visited table must hold it even for a tiny solver_power, so that it never reaches the next block's node pool
     while (align_up((size_t)A.nodes_cap * 8, 256) + (size_t)A.tsize * 4 < (size_t)2 * cells) A.tsize <<= 1;
@@ -298,20 +292,46 @@ static BigArenaDims big_arena_of(const pcgrl_config* c) {
     A.nblocks = (int)nb;
     return A;
 }
-static size_t scratch_bytes_base(const pcgrl_config* c) {
-    size_t b = wl_bytes(c);
-    if (big_search(c)) {
-        const BigArenaDims A = big_arena_of(c);
-        return b + (size_t)A.nblocks * A.block_bytes + sok_sched_bytes(c->num_envs);
+// A caller-sized buffer is cut by a bump cursor: a region is what take() returned and nothing else, so regions cannot overlap and
+// the cursor's end is the size to ask the caller for.  The size rules above round to 256 bytes, which keeps every region aligned.
+struct Region { size_t off, bytes; };
+struct Bump { size_t off; Region take(size_t bytes) { const Region r = {off, bytes}; off += bytes; return r; } };
+template <class T> static T* at(uint8_t* base, Region r) { return r.bytes ? reinterpret_cast<T*>(base + r.off) : nullptr; }     // (an empty region: no pointer)
+// The caller's `scratch` (pcgrl_layout::scratch), its regions in the order they lie: pcgrl_query_layout reports `total`, pcgrl_bind
+// points DevBufs at `scratch + off` and clears by `bytes`.  A region that the configuration does not have is empty.
+struct ScratchPlan {
+    Region wl_cnt, status, wl_items[WL_NLIST];     // work-list counters, the status word's 256 bytes, the lists
+    Region arena;                                  // the general searches' arena (cut as `big` says), or the compact searches' node pools
+    Region sok_env, sok_sync;                      // scheduling words: per environment, then the launches' sync words
+    Region sok_heap, sok_table;                    // heap + table of the compact searches beyond SOK_LDS_POWER
+    Region champ, fifo, fifo_tag, wide_sync;
+    size_t total;
+    BigArenaDims big;
+};
+static ScratchPlan scratch_plan(const pcgrl_config* c) {
+    ScratchPlan S = {};
+    Bump b = {0};
+    S.wl_cnt = b.take(WL_CNT_BYTES);
+    S.status = b.take(256);
+    for (int k = 0; k < WL_NLIST; k++) S.wl_items[k] = b.take(wl_list_bytes(c->num_envs, k));
+    if (solver_prob(c->prob)) {
+        const bool big = big_search(c);
+        if (big) S.big = big_arena_of(c);
+        S.arena = b.take(big ? (size_t)S.big.nblocks * S.big.block_bytes : SOK_BLOCKS * sok_pool_bytes(c));
+        S.sok_env = b.take(align_up((size_t)c->num_envs * (SOK_RES_WORDS + SOK_CNT_WORDS + SOK_STOP_WORDS) * 4, 256));
+        S.sok_sync = b.take(align_up(2 * (size_t)(SOK_SY_WORDS + SOK_HARD_CAP) * 4, 256));
+        if (!big && !sok_in_lds(c)) {
+            S.sok_heap = b.take(SOK_BLOCKS * sok_heap_bytes(c->solver_power));
+            S.sok_table = b.take(SOK_BLOCKS * (size_t)sok_table_size(c->solver_power) * 4);
+        }
     }
-    if (solver_prob(c->prob)) {           // (an MdNode is as large as a SokNode)
-        const size_t nodes = sok_pool_nodes(c->solver_power, c->prob);
-        b += SOK_BLOCKS * align_up(nodes * sizeof(SokNode), 256);
-        b += sok_sched_bytes(c->num_envs);
-        const size_t hnodes = 4 * (size_t)c->solver_power + 4;
-        if (c->solver_power > SOK_LDS_POWER && c->prob != PCGRL_SMB) b += SOK_BLOCKS * (align_up(hnodes * 4, 256) + (size_t)sok_table_size(c->solver_power) * 4);
-    }
-    return b;
+    S.champ = b.take(champ_bytes(c));
+    const size_t n = (size_t)c->num_envs;
+    S.fifo = b.take(c->rep == PCGRL_NARROW ? align_up(n * PCGRL_FIFO_N * 4, 256) : 0);        // draw cache of the narrow representation (DevBufs::fifo, fifo_tag)
+    S.fifo_tag = b.take(c->rep == PCGRL_NARROW ? align_up(n * 4, 256) : 0);
+    S.wide_sync = b.take((c->prob == PCGRL_BINARY && c->height > 16 && !big_map(c)) ? align_up(n * 16, 256) : 0);
+    S.total = b.off;
+    return S;
 }
 
 // Per-DEVICE state the kernels need, (re)established at every pcgrl_bind -- never behind a process-wide flag: a process may
@@ -328,6 +348,107 @@ static int device_setup(pcgrl_env* h) {
     }
     if (h->cfg.prob == PCGRL_SMB) return smb_device_setup(h);
     if (solver_prob(h->cfg.prob) && !big_search(&h->cfg)) return search_device_setup(h);
+    return PCGRL_OK;
+}
+
+// developer switches (pcgrl_set_tuning): resolved at pcgrl_bind, once -- nothing on the step path reads them, and the library reads no
+// environment variables
+static void resolve_tuning(pcgrl_env* h) {
+    const pcgrl_tuning& T = h->tun;
+    DevBufs& B = h->B;
+    h->no_wide = tun_or(T.no_wide, 0) ? 1 : 0;
+    h->wide_waves = tun_or(T.wide_waves, 8);
+    h->wide_pairs = tun_or(T.wide_pairs, 1);           // 0 = every full item of a tall map a block of its own
+    h->wide_grid = tun_or(T.wide_grid, 2048);           // blocks of k_stats_wide (they loop over the items; C5 steady: 768 .. 4096 -> 59.5 us/step, 8192 -> 63.5: a block costs ~4 us of prefix sums before its first item)
+    if (h->wide_grid < 1) h->wide_grid = 2048;
+    h->fused_zelda = tun_or(T.fused_zelda, 1) ? 1 : 0;  // 0: zelda steps as k_update + k_stats
+    h->no_fused = tun_or(T.no_fused, 0) ? 1 : 0;
+    h->obs_at_end = tun_or(T.obs_at_end, 0) ? 1 : 0;
+    // pcgrl_step_async: the fresh jobs of a tick in a launch of their own with small search regions.  Pays where a tick has many of them
+    // (C4: 1 300 fresh jobs of ~30 pops a tick, 240 -> 275 M env-steps/s); MiniDungeons / Dave have under a hundred and the extra
+    // launch -- whose length is one job's chain of pops, like the other's -- costs more than it saves (M1 277 -> 207 M)
+    h->async_split = tun_or(T.async_split, h->cfg.prob == PCGRL_SOKOBAN ? 1 : 0) ? 1 : 0;
+    // k_step: environments per block (see launch_step_pm).  The largest block that still gives (about) every compute unit one and
+    // is resident in one round: 256 environments -> one block per CU (LDS), 128 -> two, 64 -> four.
+    const int n_ = h->cfg.num_envs;
+    h->step_epb = T.step_epb > 0 ? T.step_epb : ((n_ >= 192 * 256 && n_ <= 256 * 256) ? 256 : (n_ >= 192 * 128 ? 128 : 64));
+    if (h->step_epb != 128 && h->step_epb != 256) h->step_epb = 64;
+    h->smb_heap = T.smb_lds_heap > 0 ? T.smb_lds_heap : SMB_LDS_HEAP;        // heap words a k_smb search keeps in LDS
+    if (h->smb_heap < 256 || h->smb_heap > 4096) h->smb_heap = SMB_LDS_HEAP;
+    const int f = tun_or(T.full_per_wave, 4), i = tun_or(T.inc_per_wave, 4);
+    B.step_fpw = (f == 1 || f == 2) ? f : 4;
+    // wavefront priorities in k_step: certain resets and full recomputations of the binary problem at level 3, its incremental
+    // updates at 0 (C2: 30.4 -> 28.9 us first window, 29.4 -> 28.7 steady).  Zelda's tasks are all of one kind and about one
+    // length; every setting measured there was 0.3-0.7 us slower than none.
+    // (round 6: with the narrow representation the update wavefronts -- cursor draws, ring refills -- at level 3 as well: C2 steady 29.05 ->
+    //  28.6 us, first window unchanged; zelda loses 0.4 us with it, the wrapped steps do not care: profiles/r6_round6/probe/ab_step_prio_update.txt)
+    B.step_prio = tun_or(T.step_prio, h->cfg.prob == PCGRL_BINARY ? (h->cfg.rep == PCGRL_NARROW ? (15 | (3 << 6)) : 15) : 0) & 0xFFF;
+    B.step_ipw = (i == 1 || i == 2) ? i : 4;
+    B.step_touch = tun_or(T.no_touch, 0) ? 0 : 1;
+    B.step_pair = tun_or(T.step_pair, 6);        // (C3: fifteen certain resets a block and step; 32.2 -> 29.8 us.  C2 has two or three: unaffected)
+    B.step_tight = B.step_touch ? tun_or(T.touch_tight, 1) : 0;
+    h->no_inc = tun_or(T.no_inc, 0) != 0;       // every change takes the full statistics (A/B, tests)
+    B.zelda_inc = (h->cfg.prob == PCGRL_ZELDA && h->cfg.rep <= PCGRL_REP_TURTLE && h->cfg.height <= 16 && h->cfg.width <= 32 &&
+                   h->cfg.num_envs <= WL_INC_ENV_MASK && !h->no_inc) ? 1 : 0;
+    B.pair_min = tun_or(T.pair_min, 2048);
+    B.big_team = tun_or(T.big_team, 1) ? 1 : 0;
+    h->big_team_waves = tun_or(T.big_team, 1) >= 2 ? (tun_or(T.big_team, 1) > BIG_TEAM_MAX_WAVES ? BIG_TEAM_MAX_WAVES : tun_or(T.big_team, 1)) : 4;
+    B.wide_few = tun_or(T.wide_few, WL_WIDE_FEW_REGIONS);
+    B.wide_spin = T.wide_spin > 0 ? T.wide_spin : WIDE_SPIN_LIMIT;
+    // inline_reset = 0 routes resets through the reset list + k_reset instead (A/B measurements)
+    B.inline_reset = (!solver_prob(h->cfg.prob) && tun_or(T.inline_reset, 1) != 0) ? 1 : 0;
+    if (big_search(&h->cfg)) {             // the general searches (search_big.h) take none of the compact searches' switches
+        B.sok_fast_maxc = -1; B.md_only_agent = -1; B.sok_hard_cap = 0; B.sok_spawn_iters = SOK_SPAWN_ITERS;
+    } else if (solver_prob(h->cfg.prob)) {
+        B.sok_fast_maxc = tun_or(T.sok_generic, 0) ? -1 : SOKF_MAXC;       // sok_generic: every level takes the generic search (tests)
+        B.md_only_agent = T.md_only_agent;                                  // (-1: all four agents)
+        B.sok_hard_cap = tun_or(T.sok_hard_cap, SOK_HARD_CAP);
+        B.sok_spawn_iters = T.sok_spawn > 0 ? T.sok_spawn : SOK_SPAWN_ITERS;
+        if (B.sok_hard_cap > SOK_HARD_CAP) B.sok_hard_cap = SOK_HARD_CAP;
+    }
+}
+// DevBufs from the caller's buffers: the state arrays as they are, `scratch` cut by its plan; what the kernels expect cleared is cleared
+static int bind_buffers(pcgrl_env* h, const pcgrl_buffers* b, hipStream_t st) {
+    const pcgrl_config& c = h->cfg;
+    DevBufs& B = h->B;
+    B.map = (uint8_t*)b->map; B.old_map = (uint8_t*)b->old_map; B.heat = (uint16_t*)b->heatmap; B.pos = (uint8_t*)b->pos;
+    B.heat_end = B.heat + (size_t)c.num_envs * c.width * c.height;
+    B.heat32 = c.auto_reset ? 0 : 1;
+    B.ep_return = nullptr; B.ep_length = nullptr; B.last_return = nullptr; B.last_length = nullptr;
+    B.planes = b->planes; B.counters = (int32_t*)b->counters; B.stats = (int32_t*)b->stats;
+    B.start_stats = (int32_t*)b->start_stats; B.info = (int32_t*)b->info; B.reward = (double*)b->reward;
+    B.done = (uint8_t*)b->done; B.tile_p = (double*)b->tile_p; B.rng_rep = (uint32_t*)b->rng_rep;
+    B.rng_prob = (uint32_t*)b->rng_prob; B.rng_cur = (int32_t*)b->rng_cursor;
+    B.obs = ObsSpec{nullptr, 0, 0, 0, 0, 0, 0, 0};
+    B.local = nullptr; B.flat = nullptr;
+    const ScratchPlan S = scratch_plan(&c);
+    uint8_t* s = (uint8_t*)b->scratch;
+    B.wl_cnt = at<int32_t>(s, S.wl_cnt); B.status = at<int32_t>(s, S.status);
+    for (int k = 0; k < WL_NLIST; k++) { B.wl_cap[k] = wl_capacity(c.num_envs, k); B.wl_items[k] = at<int32_t>(s, S.wl_items[k]); }
+    HIPCHK(hipMemsetAsync(B.wl_cnt, 0, S.wl_cnt.bytes + S.status.bytes, st));
+    B.champ = h->no_inc ? nullptr : at<uint8_t>(s, S.champ);
+    if (B.champ) HIPCHK(hipMemsetAsync(B.champ, c.prob == PCGRL_SMB ? 0xFF : 0, S.champ.bytes, st));   // (smb: "every cell read")
+    B.fifo = at<uint32_t>(s, S.fifo); B.fifo_tag = at<int32_t>(s, S.fifo_tag);
+    if (B.fifo_tag) HIPCHK(hipMemsetAsync(B.fifo_tag, 0xFF, S.fifo_tag.bytes, st));     // -1: nothing cached yet
+    B.wide_sync = at<int32_t>(s, S.wide_sync); B.wide_epoch = 0;
+    if (B.wide_sync) HIPCHK(hipMemsetAsync(B.wide_sync, 0, S.wide_sync.bytes, st));
+    const bool big = big_search(&c);       // levels / solver_power beyond the compact searches: the arena is the general searches'
+    B.big_arena = big ? at<uint8_t>(s, S.arena) : nullptr;
+    B.sok_pool = big ? nullptr : at<SokNode>(s, S.arena);
+    B.sok_heap = at<uint32_t>(s, S.sok_heap); B.sok_table = at<uint32_t>(s, S.sok_table);
+    if (solver_prob(c.prob)) {
+        const int power = h->alloc_solver_power = c.solver_power;      // the arena is sized for the solver_power the buffers were allocated with
+        h->big_dims = S.big;                   // (the launches keep using the dimensions the arena was cut with)
+        B.sok_res = at<int32_t>(s, S.sok_env);
+        B.sok_cnt = B.sok_res + (size_t)c.num_envs * SOK_RES_WORDS;
+        B.sok_stop = B.sok_cnt + (size_t)c.num_envs * SOK_CNT_WORDS;
+        B.sok_sync = at<int32_t>(s, S.sok_sync);
+        HIPCHK(hipMemsetAsync(B.sok_res, 0, S.sok_env.bytes + S.sok_sync.bytes, st));
+        B.sok_use_lds = !big && sok_in_lds(&c);
+        B.sok_table_size = big ? S.big.tsize : sok_table_size(power);
+        B.sok_pool_stride = big ? 0 : (int32_t)(sok_pool_bytes(&c) / sizeof(SokNode));
+        B.sok_heap_stride = big ? 0 : (int32_t)(sok_heap_bytes(power) / 4);
+    }
     return PCGRL_OK;
 }
 
@@ -360,7 +481,7 @@ int pcgrl_query_layout(const pcgrl_config* c, pcgrl_layout* L) {
     L->reward = n * 8; L->done = n; L->tile_p = n * 16;
     L->rng_rep = n * PCGRL_MT_N * 4; L->rng_prob = c->prob == PCGRL_BINARY ? n * PCGRL_MT_N * 4 : 0;
     L->rng_cursor = n * 8;
-    L->scratch = scratch_bytes(c);
+    L->scratch = scratch_plan(c).total;
     return PCGRL_OK;
 }
 
@@ -414,140 +535,10 @@ int pcgrl_bind(pcgrl_env* h, const pcgrl_buffers* b, void* stream) {
         else { (void)hipGetLastError(); HIPCHK(hipGetDevice(&h->device)); }
     }
     DeviceGuard guard(h->device);
-    int rc0 = device_setup(h);
-    if (rc0) return rc0;
-    // developer switches (pcgrl_set_tuning): resolved here, once -- nothing on the step path reads them, and the library reads no
-    // environment variables
-    const pcgrl_tuning& T = h->tun;
-    h->no_wide = tun_or(T.no_wide, 0) ? 1 : 0;
-    h->wide_waves = tun_or(T.wide_waves, 8);
-    h->wide_pairs = tun_or(T.wide_pairs, 1);           // 0 = every full item of a tall map a block of its own
-    h->wide_grid = tun_or(T.wide_grid, 2048);           // blocks of k_stats_wide (they loop over the items; C5 steady: 768 .. 4096 -> 59.5 us/step, 8192 -> 63.5: a block costs ~4 us of prefix sums before its first item)
-    if (h->wide_grid < 1) h->wide_grid = 2048;
-    h->fused_zelda = tun_or(T.fused_zelda, 1) ? 1 : 0;  // 0: zelda steps as k_update + k_stats
-    h->no_fused = tun_or(T.no_fused, 0) ? 1 : 0;
-    h->obs_at_end = tun_or(T.obs_at_end, 0) ? 1 : 0;
-    // pcgrl_step_async: the fresh jobs of a tick in a launch of their own with small search regions.  Pays where a tick has many of them
-    // (C4: 1 300 fresh jobs of ~30 pops a tick, 240 -> 275 M env-steps/s); MiniDungeons / Dave have under a hundred and the extra
-    // launch -- whose length is one job's chain of pops, like the other's -- costs more than it saves (M1 277 -> 207 M)
-    h->async_split = tun_or(T.async_split, h->cfg.prob == PCGRL_SOKOBAN ? 1 : 0) ? 1 : 0;
-    {   // k_step: environments per block (see launch_step_pm).  The largest block that still gives (about) every compute unit one and
-        // is resident in one round: 256 environments -> one block per CU (LDS), 128 -> two, 64 -> four.
-        const int n_ = h->cfg.num_envs;
-        h->step_epb = T.step_epb > 0 ? T.step_epb : ((n_ >= 192 * 256 && n_ <= 256 * 256) ? 256 : (n_ >= 192 * 128 ? 128 : 64));
-        if (h->step_epb != 128 && h->step_epb != 256) h->step_epb = 64;
-        h->smb_heap = T.smb_lds_heap > 0 ? T.smb_lds_heap : SMB_LDS_HEAP;        // heap words a k_smb search keeps in LDS
-        if (h->smb_heap < 256 || h->smb_heap > 4096) h->smb_heap = SMB_LDS_HEAP;
-    }
-    {
-        const int f = tun_or(T.full_per_wave, 4), i = tun_or(T.inc_per_wave, 4);
-        h->B.step_fpw = (f == 1 || f == 2) ? f : 4;
-        // wavefront priorities in k_step: certain resets and full recomputations of the binary problem at level 3, its incremental
-        // updates at 0 (C2: 30.4 -> 28.9 us first window, 29.4 -> 28.7 steady).  Zelda's tasks are all of one kind and about one
-        // length; every setting measured there was 0.3-0.7 us slower than none.
-        // (round 6: with the narrow representation the update wavefronts -- cursor draws, ring refills -- at level 3 as well: C2 steady 29.05 ->
-        //  28.6 us, first window unchanged; zelda loses 0.4 us with it, the wrapped steps do not care: profiles/r6_round6/probe/ab_step_prio_update.txt)
-        h->B.step_prio = tun_or(T.step_prio, h->cfg.prob == PCGRL_BINARY ? (h->cfg.rep == PCGRL_NARROW ? (15 | (3 << 6)) : 15) : 0) & 0xFFF;
-        h->B.step_ipw = (i == 1 || i == 2) ? i : 4;
-        h->B.step_touch = tun_or(T.no_touch, 0) ? 0 : 1;
-        h->B.step_pair = tun_or(T.step_pair, 6);        // (C3: fifteen certain resets a block and step; 32.2 -> 29.8 us.  C2 has two or three: unaffected)
-        h->B.step_tight = h->B.step_touch ? tun_or(T.touch_tight, 1) : 0;
-    }
-    const bool no_inc = tun_or(T.no_inc, 0) != 0;       // every change takes the full statistics (A/B, tests)
-    DevBufs& B = h->B;
-    B.map = (uint8_t*)b->map; B.old_map = (uint8_t*)b->old_map; B.heat = (uint16_t*)b->heatmap; B.pos = (uint8_t*)b->pos;
-    B.heat_end = B.heat + (size_t)h->cfg.num_envs * h->cfg.width * h->cfg.height;
-    B.heat32 = h->cfg.auto_reset ? 0 : 1;
-    B.ep_return = nullptr; B.ep_length = nullptr; B.last_return = nullptr; B.last_length = nullptr;
-    B.local = nullptr;
-    B.planes = b->planes; B.counters = (int32_t*)b->counters; B.stats = (int32_t*)b->stats;
-    B.start_stats = (int32_t*)b->start_stats; B.info = (int32_t*)b->info; B.reward = (double*)b->reward;
-    B.done = (uint8_t*)b->done; B.tile_p = (double*)b->tile_p; B.rng_rep = (uint32_t*)b->rng_rep;
-    B.rng_prob = (uint32_t*)b->rng_prob; B.rng_cur = (int32_t*)b->rng_cursor;
-    uint8_t* s = (uint8_t*)b->scratch;
-    B.wl_cnt = (int32_t*)s;
-    B.status = (int32_t*)(s + WL_CNT_BYTES);
-    {
-        uint8_t* q = s + WL_CNT_BYTES + 256;
-        for (int k = 0; k < WL_NLIST; k++) {
-            B.wl_cap[k] = wl_capacity(h->cfg.num_envs, k);
-            B.wl_items[k] = (int32_t*)q;
-            q += wl_list_bytes(h->cfg.num_envs, k);
-        }
-    }
-    HIPCHK(hipMemsetAsync(B.wl_cnt, 0, WL_CNT_BYTES + 256, (hipStream_t)stream));
-    B.sok_pool = nullptr; B.sok_heap = nullptr; B.sok_table = nullptr;
-    B.zelda_inc = (h->cfg.prob == PCGRL_ZELDA && h->cfg.rep <= PCGRL_REP_TURTLE && h->cfg.height <= 16 && h->cfg.width <= 32 &&
-                   h->cfg.num_envs <= WL_INC_ENV_MASK && !no_inc) ? 1 : 0;
-    B.pair_min = tun_or(T.pair_min, 2048);
-    B.big_team = tun_or(T.big_team, 1) ? 1 : 0;
-    h->big_team_waves = tun_or(T.big_team, 1) >= 2 ? (tun_or(T.big_team, 1) > BIG_TEAM_MAX_WAVES ? BIG_TEAM_MAX_WAVES : tun_or(T.big_team, 1)) : 4;
-    B.champ = nullptr;
-    if (champ_bytes(&h->cfg) && !no_inc) {
-        B.champ = s + scratch_bytes_base(&h->cfg);
-        HIPCHK(hipMemsetAsync(B.champ, h->cfg.prob == PCGRL_SMB ? 0xFF : 0, champ_bytes(&h->cfg), (hipStream_t)stream));   // (smb: "every cell read")
-    }
-    B.obs = ObsSpec{nullptr, 0, 0, 0, 0, 0, 0, 0};
-    B.fifo = nullptr; B.fifo_tag = nullptr;
-    if (fifo_bytes(&h->cfg)) {
-        uint8_t* f = s + scratch_bytes_base(&h->cfg) + champ_bytes(&h->cfg);     // (wide_sync follows the draw cache: below)
-        B.fifo = (uint32_t*)f;
-        B.fifo_tag = (int32_t*)(f + fifo_words_bytes(&h->cfg));
-        HIPCHK(hipMemsetAsync(B.fifo_tag, 0xFF, (size_t)h->cfg.num_envs * 4, (hipStream_t)stream));     // -1: nothing cached yet
-    }
-    B.wide_sync = nullptr; B.wide_epoch = 0;
-    B.wide_few = tun_or(T.wide_few, WL_WIDE_FEW_REGIONS);
-    B.wide_spin = T.wide_spin > 0 ? T.wide_spin : WIDE_SPIN_LIMIT;
-    if (wide_sync_bytes(&h->cfg)) {
-        B.wide_sync = (int32_t*)(s + scratch_bytes_base(&h->cfg) + champ_bytes(&h->cfg) + fifo_bytes(&h->cfg));
-        HIPCHK(hipMemsetAsync(B.wide_sync, 0, wide_sync_bytes(&h->cfg), (hipStream_t)stream));
-    }
-    // inline_reset = 0 routes resets through the reset list + k_reset instead (A/B measurements)
-    B.inline_reset = (!solver_prob(h->cfg.prob) && tun_or(T.inline_reset, 1) != 0) ? 1 : 0;
-    B.flat = nullptr;
-    B.big_arena = nullptr;
-    if (big_search(&h->cfg)) {
-        // levels / solver_power beyond the compact searches: the general searches' arena, then the scheduling words
-        h->alloc_solver_power = h->cfg.solver_power;
-        const BigArenaDims A = h->big_dims = big_arena_of(&h->cfg);        // (the launches keep using the dimensions the arena was cut with)
-        uint8_t* a = s + wl_bytes(&h->cfg);
-        B.big_arena = a;
-        a += (size_t)A.nblocks * A.block_bytes;
-        B.sok_res = (int32_t*)a;
-        B.sok_cnt = B.sok_res + (size_t)h->cfg.num_envs * 16;
-        B.sok_stop = B.sok_cnt + h->cfg.num_envs;
-        B.sok_sync = (int32_t*)(a + align_up((size_t)h->cfg.num_envs * 18 * 4, 256));
-        HIPCHK(hipMemsetAsync(a, 0, sok_sched_bytes(h->cfg.num_envs), (hipStream_t)stream));
-        B.sok_use_lds = 0; B.sok_fast_maxc = -1; B.md_only_agent = -1; B.sok_hard_cap = 0; B.sok_spawn_iters = SOK_SPAWN_ITERS;
-        B.sok_table_size = A.tsize; B.sok_pool_stride = 0; B.sok_heap_stride = 0;
-    } else if (solver_prob(h->cfg.prob)) {
-        // the arena is sized for the solver_power the buffers were allocated with
-        const int power = h->alloc_solver_power = h->cfg.solver_power;
-        const size_t nodes = sok_pool_nodes(power, h->cfg.prob), hnodes = 4 * (size_t)power + 4;
-        uint8_t* a = s + wl_bytes(&h->cfg);
-        B.sok_pool = (SokNode*)a;
-        B.sok_pool_stride = (int32_t)(align_up(nodes * sizeof(SokNode), 256) / sizeof(SokNode));
-        a += SOK_BLOCKS * align_up(nodes * sizeof(SokNode), 256);
-        B.sok_res = (int32_t*)a;
-        B.sok_cnt = B.sok_res + (size_t)h->cfg.num_envs * 16;
-        B.sok_stop = B.sok_cnt + h->cfg.num_envs;
-        B.sok_sync = (int32_t*)(a + align_up((size_t)h->cfg.num_envs * 18 * 4, 256));
-        HIPCHK(hipMemsetAsync(a, 0, sok_sched_bytes(h->cfg.num_envs), (hipStream_t)stream));
-        a += sok_sched_bytes(h->cfg.num_envs);
-        B.sok_use_lds = power <= SOK_LDS_POWER || h->cfg.prob == PCGRL_SMB;     // (smb has its own heap split, kernels_smb.h)
-        B.sok_fast_maxc = tun_or(T.sok_generic, 0) ? -1 : SOKF_MAXC;       // sok_generic: every level takes the generic search (tests)
-        B.md_only_agent = T.md_only_agent;                                  // (-1: all four agents)
-        B.sok_hard_cap = tun_or(T.sok_hard_cap, SOK_HARD_CAP);
-        B.sok_spawn_iters = T.sok_spawn > 0 ? T.sok_spawn : SOK_SPAWN_ITERS;
-        if (B.sok_hard_cap > SOK_HARD_CAP) B.sok_hard_cap = SOK_HARD_CAP;
-        B.sok_table_size = sok_table_size(power);
-        B.sok_heap_stride = (int32_t)(align_up(hnodes * 4, 256) / 4);
-        if (!B.sok_use_lds) {
-            B.sok_heap = (uint32_t*)a;
-            a += SOK_BLOCKS * align_up(hnodes * 4, 256);
-            B.sok_table = (uint32_t*)a;
-        }
-    }
+    int rc = device_setup(h);
+    if (rc) return rc;
+    resolve_tuning(h);
+    if ((rc = bind_buffers(h, b, (hipStream_t)stream))) return rc;
     h->bound = 1; h->has_old = 0; h->was_reset = 0; h->parity = 0;
     h->async_on = h->async_dirty = 0;      // (pcgrl_bind_async follows a bind)
     return PCGRL_OK;   // tile_p is caller state: call pcgrl_set_tile_probs once after the first bind
@@ -653,8 +644,8 @@ static int launch_stats_p(pcgrl_env* h, int list, int parity, int mode, int clr,
     const int gpb = PCGRL_BLOCK / P.group;
     const int grid = grid_for(P.num_envs, gpb, 8192);
     // in-kernel reset: one MT ring + tile-byte staging area per wavefront
-    const size_t lds = inline_reset ? 4 * (size_t)(PCGRL_MT_N * 4 + ((P.width * P.height + 15) & ~15)) : 0;
-    const int gen = (P.random_start || !h->has_old) ? 1 : 0;
+    const size_t lds = inline_reset ? 4 * (size_t)reset_stage_bytes(P.width * P.height) : 0;
+    const int gen = gen_flag(h);
     // where k_update put the environments that are certain to be reset in this launch
     // (1: shard 0 of the bucketed changed list -- single-cell representations of the binary problem on 16-row maps;
     //  2: the list WL_RST -- everything else that resets in k_stats)
@@ -663,7 +654,7 @@ static int launch_stats_p(pcgrl_env* h, int list, int parity, int mode, int clr,
         const int nw = h->wide_waves;
         // per wavefront an MT19937 ring + the tile bytes of a map; the block-wide reset keeps its raw words (8 bytes a cell) and the
         // map's bit string in the sets of wavefronts 1.. (kernels_stats.h): at least that much
-        const size_t set1 = PCGRL_MT_N * 4 + ((P.width * P.height + 15) & ~15);
+        const size_t set1 = reset_stage_bytes(P.width * P.height);
         const size_t need1 = set1 + (size_t)8 * P.width * P.height + 8 * ((size_t)(P.width * P.height + 63) / 64 + 2);
         const size_t sets1 = (size_t)(nw == 8 ? 8 : 4) * set1;
         const size_t lds1 = inline_reset ? (sets1 > need1 ? sets1 : need1) : 0;
@@ -706,8 +697,7 @@ static int launch_big_p(pcgrl_env* h, int list, int parity, int mode, int clr, i
     const size_t lds = (size_t)nw * per_wave;
     { const int rc = lds_cap<k_big<PROB>>(h->device, lds); if (rc) return rc; }
     const int grid = grid_for(P.num_envs, nw, 2048);
-    const int gen = (P.random_start || !h->has_old) ? 1 : 0;
-    hipLaunchKernelGGL((k_big<PROB>), dim3(grid), dim3(nw * 64), lds, st, P, h->B, list, parity, mode, clr, inline_reset, gen, park_list);
+    hipLaunchKernelGGL((k_big<PROB>), dim3(grid), dim3(nw * 64), lds, st, P, h->B, list, parity, mode, clr, inline_reset, gen_flag(h), park_list);
     HIPCHK(hipGetLastError());
     return PCGRL_OK;
 }
@@ -783,13 +773,12 @@ static int launch_step_pme(pcgrl_env* h, const int32_t* actions, int parity, hip
     // the block's state copy (kernels_step.h) + per wavefront an MT19937 ring and the tile bytes of a map (in-kernel resets)
     const StepLds SL = step_lds_layout(16 * P.nplanes * (int)sizeof(MaskT), PROB == PCGRL_PROB_BINARY ? 16 * (int)sizeof(MaskT) : 0,
                                        P.rep == PCGRL_REP_NARROW, P.rep == PCGRL_REP_WIDE ? 3 : 1, EPB);
-    const size_t lds = (size_t)SL.total + (EPB / 16) * (size_t)(PCGRL_MT_N * 4 + ((P.width * P.height + 15) & ~15));
+    const size_t lds = (size_t)SL.total + (EPB / 16) * (size_t)reset_stage_bytes(P.width * P.height);
     const int grid = (P.num_envs + EPB - 1) / EPB;
-    const int gen = (P.random_start || !h->has_old) ? 1 : 0;
 #define PCGRL_LAUNCH_STEP(REPV, MULTI, OBSV, ROWV) do { \
         { const int rca = lds_cap<k_step<PROB, REPV, MaskT, MULTI, EPB, OBSV, ROWV>>(h->device, lds); if (rca) return rca; } \
         hipLaunchKernelGGL((k_step<PROB, REPV, MaskT, MULTI, EPB, OBSV, ROWV>), dim3(grid), dim3(EPB * 4), lds, st, P, h->B, actions, \
-                           parity, gen, R.steps, R.action_stride, R.reward_out, R.done_out, R.info_out); } while (0)
+                           parity, gen_flag(h), R.steps, R.action_stride, R.reward_out, R.done_out, R.info_out); } while (0)
     const bool multi = R.steps > 1 || R.reward_out || R.done_out || R.info_out;
     // a single step with a bound observation of a lean shape: the instantiation that writes the images while it runs (32-bit row masks)
     constexpr bool kObsKernel = sizeof(MaskT) == 4;
@@ -848,17 +837,16 @@ PCGRL_LOCAL int launch_smb(pcgrl_env* h, int32_t* sync, int list_a, int mode_a, 
     // per wavefront: the heap (smb_search: its first levels; a deeper heap continues in the arena) + the visited bitmap;
     // as many wavefronts per block (one block per compute unit) as the LDS budget holds, SMB_MAX_WAVES at most
     int heap_n = 4 * h->P.solver_power + 4 < h->smb_heap ? ((4 * h->P.solver_power + 4 + 3) & ~3) : h->smb_heap;
-    const int reset_words = PCGRL_MT_N + ((h->P.width * h->P.height + 15) & ~15) / 4;       // the in-kernel reset stages its ring and tiles there
+    const int reset_words = reset_stage_bytes(h->P.width * h->P.height) / 4;       // the in-kernel reset stages its ring and tiles there
     if (heap_n < reset_words) heap_n = (reset_words + 3) & ~3;
     const size_t vis_words = ((size_t)((h->P.width + 6) * (h->P.height + SMB_YOFF + 1) * 5 + 31) / 32 + 3) & ~(size_t)3;
     const size_t per_wave = ((size_t)heap_n + vis_words) * 4;
     int nw = (int)(SMB_LDS_BUDGET / per_wave);
     nw = nw > SMB_MAX_WAVES ? SMB_MAX_WAVES : (nw < 1 ? 1 : nw);
     if ((size_t)nw * per_wave > SMB_LDS_BUDGET) return PCGRL_EINVAL;      // one search does not fit a compute unit's LDS
-    const int gen = (h->P.random_start || !h->has_old) ? 1 : 0;
     // (a step's changed levels come on two lists: WL_INC = the ones expected to take long, first; see k_update)
     hipLaunchKernelGGL(k_smb<0>, dim3(SOK_BLOCKS), dim3(nw * 64), nw * per_wave, st, h->P, h->B, (list_a == WL_CHG && mode_a == MODE_STEP) ? (int)WL_INC : -1,
-                       list_a, mode_a, list_b, mode_b, parity, rst_list, sync, clr, heap_n, inline_reset, gen);
+                       list_a, mode_a, list_b, mode_b, parity, rst_list, sync, clr, heap_n, inline_reset, gen_flag(h));
     HIPCHK(hipGetLastError());
     return PCGRL_OK;
 }
@@ -872,7 +860,7 @@ static AsyncKernel async_kernel(int prob) {
 }
 static Agents4Kernel agents4_kernel(int prob) { return prob == PCGRL_PROB_DDAVE ? k_ddave<0> : k_mdungeon<0>; }
 PCGRL_LOCAL int search_device_setup(pcgrl_env* h) {   // the search kernels use most of a compute unit's LDS (heap + 64-bit-key table)
-    const int lds = (int)((SOK_LDS_HEAP + 2 * SOK_LDS_TABLE) * 4);
+    const int lds = (int)sok_lds_bytes();
     const int prob = h->cfg.prob;                      // (PCGRL_SOKOBAN ... of the ABI are the kernels' PCGRL_PROB_* values)
     const void* f = prob == PCGRL_PROB_SOKOBAN ? reinterpret_cast<const void*>(k_sokoban<0>) : reinterpret_cast<const void*>(agents4_kernel(prob));
     HIPCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
@@ -906,7 +894,7 @@ PCGRL_LOCAL int launch_search(pcgrl_env* h, int32_t* sync, int list_a, int mode_
         if (h->P.prob == PCGRL_PROB_MDUNGEON) return launch_search_big_p<PCGRL_PROB_MDUNGEON>(h, sync, list_a, mode_a, list_b, mode_b, parity, rst_list, clr, st);
         return launch_search_big_p<PCGRL_PROB_SOKOBAN>(h, sync, list_a, mode_a, list_b, mode_b, parity, rst_list, clr, st);
     }
-    const size_t lds = h->B.sok_use_lds ? (size_t)(SOK_LDS_HEAP + 2 * SOK_LDS_TABLE) * 4 : 0;   // heap + 64-bit-key table
+    const size_t lds = h->B.sok_use_lds ? sok_lds_bytes() : 0;   // heap + 64-bit-key table
     if (h->P.prob != PCGRL_PROB_SOKOBAN)
         hipLaunchKernelGGL(agents4_kernel(h->P.prob), dim3(SOK_BLOCKS), dim3(128), lds, st, h->P, h->B, list_a, mode_a, list_b, mode_b, parity, rst_list, sync, clr);
     else
@@ -937,9 +925,9 @@ template <int PROB>
 static int launch_reset_p(pcgrl_env* h, int list, int park_list, int parity, int clr, hipStream_t st) {
     const PcgrlParams& P = h->P;
     const int cells = P.width * P.height;
-    const size_t lds = 4 * (size_t)(PCGRL_MT_N * 4 + ((cells + 15) & ~15));
+    const size_t lds = 4 * (size_t)reset_stage_bytes(cells);
     const int grid = grid_for(P.num_envs, 4, h->was_reset ? 512 : 4096);
-    const int gen = (P.random_start || !h->has_old) ? 1 : 0;
+    const int gen = gen_flag(h);
     if (P.group == 16 && P.mask_bytes == 4)
         hipLaunchKernelGGL((k_reset<PROB, 16, uint32_t>), dim3(grid), dim3(PCGRL_BLOCK), lds, st, P, h->B, list, park_list, parity, gen, clr);
     else if (P.group == 16)
@@ -973,7 +961,7 @@ PCGRL_LOCAL int launch_planes_from_map(pcgrl_env* h, const uint8_t* maps, hipStr
         HIPCHK(hipGetLastError());
         return PCGRL_OK;
     }
-    const size_t lds = 4 * (size_t)((P.width * P.height + 15) & ~15);
+    const size_t lds = 4 * (size_t)reset_tile_bytes(P.width * P.height);
     const int grid = grid_for(P.num_envs, 4, 4096);
     if (P.mask_bytes == 4)
         hipLaunchKernelGGL((k_planes_from_map<uint32_t>), dim3(grid), dim3(PCGRL_BLOCK), lds, st, P, h->B, maps);
@@ -999,11 +987,10 @@ static bool solver_rollout_applies(const pcgrl_env* h, int* envs_per_block) {
 #if PCGRL_IN_PART(PART_STEP_SOLVER)
 template <int PROB, int REP, class MaskT>
 static int launch_step_solver_t(pcgrl_env* h, const int32_t* actions, hipStream_t st, const RolloutArgs& R, int epb) {
-    const size_t lds = (size_t)(SOK_LDS_HEAP + 2 * SOK_LDS_TABLE) * 4;
+    const size_t lds = sok_lds_bytes();
     { const int rca = lds_cap<k_step_solver<PROB, REP, MaskT>>(h->device, lds); if (rca) return rca; }
     const int grid = (h->P.num_envs + epb - 1) / epb;
-    const int gen = (h->P.random_start || !h->has_old) ? 1 : 0;
-    hipLaunchKernelGGL((k_step_solver<PROB, REP, MaskT>), dim3(grid), dim3(SS_THREADS), lds, st, h->P, h->B, actions, gen, R.steps, R.action_stride, epb,
+    hipLaunchKernelGGL((k_step_solver<PROB, REP, MaskT>), dim3(grid), dim3(SS_THREADS), lds, st, h->P, h->B, actions, gen_flag(h), R.steps, R.action_stride, epb,
                        R.reward_out, R.done_out, R.info_out);
     HIPCHK(hipGetLastError());
     return PCGRL_OK;
@@ -1169,18 +1156,25 @@ static int launch_row(pcgrl_env* h, const uint8_t* pending, const RowCall& rc_, 
 static bool async_applies(const pcgrl_config* c) {
     return solver_prob(c->prob) && c->prob != PCGRL_SMB && !big_search(c) && !big_map(c) && c->solver_power <= SOK_LDS_POWER;
 }
-// head of the arena: pending [N] | counters + the shards of the first one | the tick's list of runnable slots
-static size_t async_stats_bytes() { return 64 + ASYNC_NSHARD * 64; }
-static size_t async_small_pool_bytes() { return align_up((size_t)ASYNC_SMALL_BLOCKS * ASYNC_SMALL_NODES * 16, 256); }
-static size_t async_head_bytes(const pcgrl_config* c, int nslots) {       // ... | node pools of the small launch | its hand-over list
-    return align_up((size_t)c->num_envs, 256) + async_stats_bytes() + align_up((size_t)nslots * 4, 256) + async_small_pool_bytes() + align_up((size_t)c->num_envs * 4, 256);
-}
-static size_t async_slot_bytes(const pcgrl_config* c) {
-    return align_up((size_t)ASYNC_SLOT_HDR + (size_t)(4 * c->solver_power + 4) * 16 + (size_t)(SOK_LDS_HEAP + 2 * SOK_LDS_TABLE) * 4, 256);
+// The caller's arena of pcgrl_step_async, cut like `scratch` (ScratchPlan): pcgrl_async_bytes reports `total`, pcgrl_bind_async points
+// AsyncCtl at the regions and clears everything before `slots`
+struct AsyncPlan { Region pending, stats, runlist, small_pool, overflow, slots; size_t slot_bytes, total; };
+static AsyncPlan async_plan(const pcgrl_config* c, int nslots) {
+    AsyncPlan A = {};
+    Bump b = {0};
+    A.pending = b.take(align_up((size_t)c->num_envs, 256));                // pending [N]
+    A.stats = b.take(64 + ASYNC_NSHARD * 64);                             // counters + the shards of the first one
+    A.runlist = b.take(align_up((size_t)nslots * 4, 256));                // the tick's list of runnable slots
+    A.small_pool = b.take(align_up((size_t)ASYNC_SMALL_BLOCKS * ASYNC_SMALL_NODES * 16, 256));      // node pools of the small launch
+    A.overflow = b.take(align_up((size_t)c->num_envs * 4, 256));          // its hand-over list
+    A.slot_bytes = align_up((size_t)ASYNC_SLOT_HDR + (size_t)(4 * c->solver_power + 4) * 16 + sok_lds_bytes(), 256);
+    A.slots = b.take((size_t)nslots * A.slot_bytes);
+    A.total = b.off;
+    return A;
 }
 size_t pcgrl_async_bytes(const pcgrl_config* c, int32_t nslots) {
     if (validate_config(c) != PCGRL_OK || nslots < 1 || !async_applies(c)) return 0;
-    return async_head_bytes(c, nslots) + (size_t)nslots * async_slot_bytes(c);
+    return async_plan(c, nslots).total;
 }
 int pcgrl_bind_async(pcgrl_env* h, void* arena, size_t bytes, int32_t nslots, void* stream) {
     if (!h || !h->bound) return PCGRL_ESTATE;
@@ -1188,17 +1182,14 @@ int pcgrl_bind_async(pcgrl_env* h, void* arena, size_t bytes, int32_t nslots, vo
     if (!async_applies(&h->cfg) || nslots < 1 || ((uintptr_t)arena & 255) != 0 || bytes < pcgrl_async_bytes(&h->cfg, nslots)) return PCGRL_EINVAL;
     if (h->alloc_solver_power != h->cfg.solver_power) return PCGRL_EINVAL;         // (the slots are cut for the bound solver_power)
     DeviceGuard guard(h->device);
+    const AsyncPlan Q = async_plan(&h->cfg, nslots);
     uint8_t* a = (uint8_t*)arena;
     AsyncCtl& A = h->async;
-    A.pending = a;
-    A.stats = (unsigned long long*)(a + align_up((size_t)h->cfg.num_envs, 256));
-    A.runlist = (int32_t*)(a + align_up((size_t)h->cfg.num_envs, 256) + async_stats_bytes());
-    A.small_pool = (uint8_t*)A.runlist + align_up((size_t)nslots * 4, 256);
-    A.overflow = (int32_t*)(A.small_pool + async_small_pool_bytes());
-    A.slots = a + async_head_bytes(&h->cfg, nslots);
-    A.slot_bytes = async_slot_bytes(&h->cfg);
+    A.pending = at<uint8_t>(a, Q.pending); A.stats = at<unsigned long long>(a, Q.stats); A.runlist = at<int32_t>(a, Q.runlist);
+    A.small_pool = at<uint8_t>(a, Q.small_pool); A.overflow = at<int32_t>(a, Q.overflow);
+    A.slots = at<uint8_t>(a, Q.slots); A.slot_bytes = Q.slot_bytes;
     A.nslots = nslots; A.nodes_cap = 4 * h->cfg.solver_power + 4; A.tick = 0; A.pad = 0;
-    HIPCHK(hipMemsetAsync(a, 0, async_head_bytes(&h->cfg, nslots), (hipStream_t)stream));
+    HIPCHK(hipMemsetAsync(a, 0, Q.slots.off, (hipStream_t)stream));
     HIPCHK(hipMemset2DAsync(A.slots, A.slot_bytes, 0, ASYNC_SLOT_HDR, (size_t)nslots, (hipStream_t)stream));
     h->async_on = 1; h->async_dirty = 0;
     return PCGRL_OK;

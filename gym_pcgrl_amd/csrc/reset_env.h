@@ -1,6 +1,10 @@
 // Device functions of PcgrlEnv.reset shared by k_reset (kernels_reset.h) and the in-kernel reset of k_stats.
 // Part of the single translation unit pcgrl_abi.hip.
 #pragma once
+// LDS a wavefront stages a reset in: the MT19937 ring, then the map's tile bytes (a multiple of 16).  The launchers size the
+// allocation and the kernels find their wavefront's share with the same two functions.
+__host__ __device__ constexpr int reset_tile_bytes(int cells) { return (cells + 15) & ~15; }
+__host__ __device__ constexpr int reset_stage_bytes(int cells) { return PCGRL_MT_N * 4 + reset_tile_bytes(cells); }
 // ------------------------------------------------------------------------------------------
 // Row bit planes from a tile byte map staged in LDS; lanes [0,G) of the wave each take one row.
 // `row` is the map row this lane owns (0 .. G-1) or -1 for a lane that does not take part.

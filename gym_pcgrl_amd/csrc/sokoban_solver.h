@@ -31,6 +31,8 @@
 #define SOK_LDS_POWER 5000                         /* solver_power up to this keeps heap+table in LDS */
 #define SOK_LDS_HEAP (4 * SOK_LDS_POWER + 4)       /* entries (u32) */
 #define SOK_LDS_TABLE 8192                         /* slots (u32), power of two */
+// dynamic LDS of a search block: the heap + the table with 64-bit keys (two words a slot)
+PCGRL_HD constexpr size_t sok_lds_bytes() { return (size_t)(SOK_LDS_HEAP + 2 * SOK_LDS_TABLE) * 4; }
 
 struct alignas(8) SokNode {  // 40 bytes, moved around as five 64-bit words
     uint8_t crate[SOK_MAXC];
