@@ -167,7 +167,8 @@ __device__ __forceinline__ UpdateOut update_env(const PcgrlParams& P, const DevB
                 // that keeps the cell's kind, or a cell no search read, leaves jumps / jumps-dist / dist-win what they were.
                 const bool so = (0x5Au >> old) & 1u, sn = (0x5Au >> tile) & 1u;
                 const uint32_t seen = reinterpret_cast<const uint32_t*>(B.champ)[(size_t)e * W + wx];
-                cheap = so == sn || ((seen >> wy) & 1u) == 0u;
+                // (not while the previous statistics hold a play-through under another solver_power: SMB_REPLAY, worklist.h)
+                cheap = (so == sn || ((seen >> wy) & 1u) == 0u) && B.sok_cnt[e] != SMB_REPLAY;
                 inc_item = e | SMB_KEEP_PLAY;
             }
             if (B.zelda_inc) {

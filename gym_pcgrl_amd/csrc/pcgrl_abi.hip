@@ -114,6 +114,7 @@ struct pcgrl_env {
     int device;
     // optional per-phase timing with HIP events on the caller's stream (pcgrl_profile)
     int alloc_solver_power;
+    int smb_replay;   // smb: solver_power changed under statistics that were played through with the old one (pcgrl_configure); the next step marks every environment SMB_REPLAY
     // developer switches (pcgrl_set_tuning; A/B measurements and tests), resolved at pcgrl_bind
     pcgrl_tuning tun;
     int no_wide, wide_waves, wide_grid, wide_pairs, fused_zelda, no_fused, step_epb, smb_heap, obs_at_end, no_inc;
@@ -491,6 +492,7 @@ int pcgrl_create(const pcgrl_config* c, pcgrl_env** out) {
     if (!out) return PCGRL_EINVAL;
     pcgrl_env* h = new pcgrl_env();
     h->bound = h->has_old = h->was_reset = h->parity = h->device = 0;
+    h->smb_replay = 0;
     h->profiling = 0; h->ev_used = 0; h->prof_steps = 0; h->obs_hold = 0; h->obs_incremental = 0; h->obs_synced = nullptr;
     memset(&h->row, 0, sizeof(h->row)); h->row_on = h->row_i64 = h->row_live = 0;
     memset(&h->async, 0, sizeof(h->async)); h->async_on = h->async_dirty = 0;
@@ -556,6 +558,9 @@ int pcgrl_configure(pcgrl_env* h, const pcgrl_config* c) {
     // the other direction needs that arena: re-create
     const bool was_big = h->bound && h->P.big_search;
     if (h->bound && big_search(c) && !was_big) return PCGRL_EINVAL;
+    // smb keeps jumps / jumps-dist / dist-win of the last play-through across changes that cannot alter it (SMB_KEEP_PLAY): they were
+    // made with the old solver_power, and the reference plays every changed level with the current one
+    if (h->bound && c->prob == PCGRL_SMB && c->solver_power != h->cfg.solver_power) h->smb_replay = 1;
     h->cfg = *c;
     fill_params(c, &h->P);
     if (was_big) h->P.big_search = 1;
@@ -1081,6 +1086,10 @@ static int step_one(pcgrl_env* h, const int32_t* actions, void* stream, bool* us
         if ((rc = launch_step(h, actions, par, st))) return rc;
         for (int k = 0; k < 6; k++) if ((rc = prof_mark(h, st))) return rc;
         return PCGRL_OK;
+    }
+    if (h->smb_replay) {       // (see pcgrl_configure: every environment's next change is played through)
+        if (h->B.champ) HIPCHK(hipMemsetAsync(h->B.sok_cnt, SMB_REPLAY & 0xFF, (size_t)h->P.num_envs * sizeof(int32_t), st));
+        h->smb_replay = 0;
     }
     if ((rc = launch_update(h, actions, par, st))) return rc;
     if ((rc = prof_mark(h, st))) return rc;

@@ -46,6 +46,10 @@ template <int G> __device__ __forceinline__ unsigned wl_inc_code(int raw) { retu
 // k_stats resets it without recomputing anything.
 #define WL_RESET_ONLY (1 << 30)
 #define SMB_KEEP_PLAY (1 << 29)    /* smb, changed list: the change cannot alter the play-through (k_update), k_smb keeps the previous one */
+// smb, DevBufs::sok_cnt[e] (the pops of the environment's last play-through, at most solver_power): the statistics row holds a play-through
+// made under another solver_power (pcgrl_configure on a stepped handle) -- the environment's next change is played through whatever
+// it touches.  k_smb overwrites the mark with the pops of that play-through.  (Four equal bytes: the host sets it with one memset.)
+#define SMB_REPLAY 0x7F7F7F7F
 
 // Optional in-kernel timeline (tools/timeline.py builds a copy of the library with -DPCGRL_TIMELINE; the product is
 // compiled without it and TL() is nothing): wavefront-private slots, 100 MHz wall clock << 8 | tag.

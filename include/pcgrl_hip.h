@@ -165,7 +165,17 @@ int pcgrl_destroy(pcgrl_env* env);
 void pcgrl_tuning_defaults(pcgrl_tuning* t);
 int pcgrl_set_tuning(pcgrl_env* env, const pcgrl_tuning* t);   /* between pcgrl_create and pcgrl_bind (PCGRL_ESTATE afterwards) */
 int pcgrl_bind(pcgrl_env* env, const pcgrl_buffers* bufs, void* stream);
-/* Change parameters that do not alter buffer sizes (anything but prob/rep/num_envs/width/height). */
+/* Change parameters that do not alter buffer sizes (anything but prob/rep/num_envs/width/height).  A host call: nothing is launched
+ * and no buffer is touched.  On a handle that has been stepped the next step / rollout / tick runs under the new parameters, like
+ * PcgrlEnv.adjust_param between two steps: limits, targets and reward weights apply to the steps that follow (the counters, heat maps,
+ * current and start statistics of the running episodes stay), tile probabilities to the resets that follow (binary: after
+ * pcgrl_set_tile_probs), and a solver_power that is not larger than the one the handle was bound with to every search that follows.
+ * The current statistics are never recomputed here: an unchanged environment keeps the row of its last change, as in the reference.
+ * smb: the rows hold play-through results (jumps, jumps-dist, dist-win) that the step kernels carry over a change the play-through
+ * cannot see; after a call that changes solver_power every environment's next change is played through again with the new value,
+ * whatever it touches, so no row is ever derived from a play-through under another solver_power than the one in force at that change.
+ * PCGRL_EINVAL, and nothing changed: a solver_power beyond the bound one, or one that moves the searches to the general kernels --
+ * create and bind a new handle.  A caller that steps asynchronously (pcgrl_step_async) calls pcgrl_async_flush first. */
 int pcgrl_configure(pcgrl_env* env, const pcgrl_config* cfg);
 /* keys: HOST pointer, [count,624] u32 = MT19937 init_by_array state of environment first..first+count-1;
  * seeds both streams identically (pcgrl_env.py:54-57). */

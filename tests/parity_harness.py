@@ -8,6 +8,8 @@ fullsize_case(...)      a benchmark configuration at its real batch size (the pa
                         compared with the oracle at every step
 search_game_case(...)   chosen levels of a search problem through one stepping route (steps, one rollout, asynchronous ticks): four
                         scripted writes per environment that compute the level, its neighbour and both again
+live_case(...)          a script of steps, rollouts and events -- adjust_param, seed, set_maps ... in the middle of running episodes --
+                        on one handle; every step and the state after every phase against the oracle put through the same script
 """
 import numpy as np
 
@@ -154,10 +156,11 @@ def _oracle_rollouts(prob, rep, calls, seeds, acts_by_env, auto_reset=True, keep
 
 
 def action_dims(prob, rep, w, h):
-    """The sizes of the action space of a single-cell representation, as the representations define them (narrow_rep.py:37-38,
-    turtle_rep.py:50-51, wide_rep.py:22-23) -- for drawing a tape of actions where there is no device to ask."""
+    """The sizes of a representation's action space, as the representations define them (narrow_rep.py:37-38, turtle_rep.py:50-51,
+    wide_rep.py:22-23, narrow_cast_rep.py:24-25, narrow_multi_rep.py:25-26, turtle_cast_rep.py:26-27) -- for drawing a tape of actions
+    where there is no device to ask."""
     nt = len(ol.TILES[prob])
-    return {"narrow": [nt + 1], "turtle": [nt + 4], "wide": [w, h, nt]}[rep]
+    return {"narrow": [nt + 1], "turtle": [nt + 4], "wide": [w, h, nt], "narrowcast": [3, nt], "narrowmulti": [nt + 1] * 9, "turtlecast": [6, nt]}[rep]
 
 
 def draw_actions(dims, rs, T, E):
@@ -526,6 +529,133 @@ def search_game_case(prob, w, h, power, maps, cells, route, seed0=7000, tuning=N
         return cnt
     finally:
         env.close()
+
+
+def live_steps(script):
+    """Number of steps in a live_case script."""
+    return sum(int(arg) for kind, arg in script if kind in ("step", "rollout"))
+
+
+def live_oracle(prob, rep, calls, E, script, seed0, acts):
+    """The oracle's side of live_case, without a device: E OracleEnvs (environment i seeded seed0 + i, `calls`, reset()) put through
+    `script` with the actions acts [T, E, k], auto-reset at done.  -> dict: reward [T, E], done [T, E], info [T, E, keys + iterations +
+    changes], limits [T, 2] (max_changes, max_iterations in force at the step), phase [T] (the script entry a step belongs to),
+    start / states[p] (map, pos, heatmap after reset() / after script entry p), first[p] (the first step after entry p)."""
+    orc = []
+    for i in range(E):
+        o = ol.OracleEnv(prob, rep)
+        for kw in calls:
+            o.adjust_param(**kw)
+        o.seed(seed0 + i)
+        o.reset()
+        orc.append(o)
+
+    def state():
+        obs = [o.obs() for o in orc]
+        return dict(map=np.stack([x["map"] for x in obs]), heatmap=np.stack([x["heatmap"] for x in obs]).astype(np.int64),
+                    pos=np.stack([x.get("pos", np.zeros(2, np.uint8)) for x in obs]).astype(np.int64))
+
+    rec = dict(reward=[], done=[], info=[], limits=[], phase=[], start=state(), states=[], first=[])
+    t = 0
+    for p, (kind, arg) in enumerate(script):
+        rec["first"].append(t)
+        if kind == "event":
+            for i, o in enumerate(orc):
+                arg(o, i)
+        elif kind in ("step", "rollout"):
+            for _ in range(int(arg)):
+                rows = [o.rollout(acts[t, i][None], want_maps=False, want_heat=False) for i, o in enumerate(orc)]
+                rec["reward"].append(np.array([x["reward"][0] for x in rows]))
+                rec["done"].append(np.array([x["done"][0] for x in rows]))
+                rec["info"].append(np.stack([x["info"][0] for x in rows]))
+                lim = {(o.max_changes, o.max_iterations) for o in orc}
+                assert len(lim) == 1, lim
+                rec["limits"].append(lim.pop())
+                rec["phase"].append(p)
+                t += 1
+        else:
+            raise ValueError(kind)
+        rec["states"].append(state())
+    assert t == len(acts), (t, len(acts))
+    for k in ("reward", "done", "info", "limits", "phase"):
+        rec[k] = np.array(rec[k])
+    return rec
+
+
+def live_case(prob, rep, calls, E, script, seed0, acts, tuning=None, setup=None, rec=None):
+    """Reconfiguring a handle that is being stepped (tests/test_gpu_live_handle.py).  One handle of E environments (seed0, `calls`,
+    setup(env) if given, reset()) goes through `script`, a list of
+      ("step", n)      n calls of step()
+      ("rollout", n)   n steps as one rollout()
+      ("event", fn)    fn(env, None) on the batch and fn(oracle i, i) on every OracleEnv -- adjust_param, seed, set_maps / set_map ...
+    with the actions acts [T, E, k] (draw_actions).  Every environment is compared with the oracle (live_oracle; `rec`: its result,
+    when the caller made it already): reward, done, every info column, iterations, changes, max_changes and max_iterations of every
+    step, map, cursor and heat map after reset() and after every script entry, and check_status() == 0 there.  All exact.  Returns
+    the oracle's record, for what a test has to ask of its own case; raises AssertionError on the first difference."""
+    import torch
+    from gym_pcgrl_amd.envs import BatchedPcgrlEnv
+    if rec is None:
+        rec = live_oracle(prob, rep, calls, E, script, seed0, acts)
+    what = "%s %s %s E %d seed %d" % (prob, rep, calls, E, seed0)
+
+    def same(name, got, want, where):
+        got, want = np.asarray(got), np.asarray(want)
+        assert got.shape == want.shape, (name, where, got.shape, want.shape)
+        bad = np.nonzero((got != want).reshape(E, -1).any(1))[0]
+        if bad.size:
+            i = int(bad[0])
+            raise AssertionError("%s differs %s (%s) in %d environments %s; environment %d: got %s, the oracle %s"
+                                 % (name, where, what, bad.size, bad[:8].tolist(), i, got[i].tolist(), want[i].tolist()))
+
+    env = BatchedPcgrlEnv(prob=prob, rep=rep, num_envs=E, seed=seed0, tuning=tuning)
+    try:
+        for kw in calls:
+            env.adjust_param(**kw)
+        if setup is not None:
+            setup(env)
+        env.reset()
+        keys = list(env._prob.info_keys) + ["iterations", "changes"]
+        wide_act = acts.shape[2] > 1
+
+        def same_state(want, where):
+            obs = env._obs()
+            same("map", obs["map"].cpu().numpy(), want["map"], where)
+            if env._rep.has_pos:
+                same("pos", obs["pos"].cpu().numpy().astype(np.int64), want["pos"], where)
+            same("heatmap", obs["heatmap"].cpu().numpy().astype(np.int64), want["heatmap"], where)
+            assert env.check_status() == 0, where
+
+        def same_step(t, rew, done, info_cols, limits):
+            where = "at step %d (script entry %d)" % (t, rec["phase"][t])
+            same("done", done, rec["done"][t], where)
+            same("reward", rew, rec["reward"][t], where)
+            same("info", info_cols, rec["info"][t], where)
+            assert tuple(int(v) for v in limits) == tuple(int(v) for v in rec["limits"][t]), ("max_changes / max_iterations", where, limits, rec["limits"][t])
+
+        same_state(rec["start"], "after reset()")
+        t = 0
+        for p, (kind, arg) in enumerate(script):
+            if kind == "event":
+                arg(env, None)
+            elif kind == "step":
+                for _ in range(int(arg)):
+                    obs, rew, done, info = env.step(acts[t] if wide_act else acts[t, :, 0])
+                    same_step(t, rew.cpu().numpy(), done.cpu().numpy(), np.stack([info[k].cpu().numpy() for k in keys], 1).astype(np.int64),
+                              (info["max_changes"], info["max_iterations"]))
+                    t += 1
+            else:
+                n = int(arg)
+                tape = torch.as_tensor(acts[t:t + n] if wide_act else acts[t:t + n, :, 0], device=env.device)
+                rew, done, info = env.rollout(tape)
+                cols = np.stack([info[k].view(n, E).cpu().numpy() for k in keys], 2).astype(np.int64)
+                rew, done = rew.cpu().numpy(), done.cpu().numpy()
+                for j in range(n):
+                    same_step(t + j, rew[j], done[j], cols[j], (info["max_changes"], info["max_iterations"]))
+                t += n
+            same_state(rec["states"][p], "after script entry %d (%s)" % (p, kind))
+    finally:
+        env.close()
+    return rec
 
 
 def expected_image(m, pos, oh, ow, centered, pad, depth):
