@@ -70,6 +70,26 @@ def make_batched(env_id, num_envs, **kwargs):
     return BatchedPcgrlEnv(prob=prob, rep=rep, num_envs=num_envs, **kwargs)
 
 
+def evaluate_levels(prob, maps, device=None, **params):
+    """Problem.get_stats of a stack of levels in one call: `maps` array-like uint8 [M, H, W] (width and height are taken from it),
+    `params` as for adjust_param (smb: solver_power is set as an attribute, smb_prob.py:40-53 has no such key).  Returns
+    BatchedPcgrlEnv.evaluate()'s Evaluation (rows, stats)."""
+    import numpy as np
+    from .envs import BatchedPcgrlEnv
+    shape = tuple(maps.shape) if hasattr(maps, "shape") else np.asarray(maps).shape
+    if len(shape) != 3:
+        raise ValueError("evaluate_levels(): maps must be [M, H, W], got shape %s" % (shape,))
+    env = BatchedPcgrlEnv(prob=prob, rep="wide", num_envs=1, device=device, seed=0, auto_reset=False)
+    try:
+        power = params.pop("solver_power", None) if prob == "smb" else None
+        env.adjust_param(width=int(shape[2]), height=int(shape[1]), **params)
+        if power is not None:
+            env._prob._solver_power = int(power)
+            env.adjust_param()
+        return env.evaluate(maps)
+    finally:
+        env.close()
+
 
 register_with_gym()      # no-op without a gym of the reference's era (none is on the MI355X image)
 register_with_gymnasium()   # likewise for gymnasium / gym >= 0.26 (five-tuple adapter)

@@ -1,0 +1,135 @@
+// pcgrl_get_stats / pcgrl_get_reward: Problem.get_stats, get_reward and get_episode_over as pure functions of the caller's maps and
+// statistics rows -- no episode, no handle state but the sticky status word.  Part of the single translation unit pcgrl_abi.hip.
+//   k_get_stats          a lane group per map (four maps a wavefront at <= 16 rows, a wavefront per map beyond), grid-stride over
+//                        `count`: the caller's bytes -> an LDS stage -> row planes in registers -> compute_item_stats -> the row.
+//                        A map that needs the planner gets its partial row and a place on the job list (counter + indices in `work`).
+//   k_get_stats_search   sokoban / mdungeon / ddave: persistent blocks shaped like the search phase of k_step_solver -- eight
+//                        wavefronts try a chunk of jobs in small private regions, wavefront 0 redoes what was stopped by the small
+//                        limit in the full region with the full solver_power.  The job count is read from device memory.
+//   k_get_reward         a thread per row: compute_reward + episode_over (pcgrl_algos.h).
+#pragma once
+
+// words of the workspace's head: the job counter k_get_stats appends with, the chunk ticket of k_get_stats_search
+enum { EVAL_HEAD_NJOBS = 0, EVAL_HEAD_TICKET = 1 };
+#define EVAL_JOBS_PER_WAVE 8                                       /* jobs a wavefront of k_get_stats_search tries per chunk */
+#define EVAL_CHUNK (SS_SEARCH_WAVES * EVAL_JOBS_PER_WAVE)          /* jobs a block takes per ticket */
+#define EVAL_STAGE_BYTES 256                                       /* a compact search level has at most 256 bordered cells */
+
+// the caller's tile bytes of map m into the group's LDS stage: a tile id beyond the last is clamped here (the caller's map stays as
+// it is) and reported in the status word
+__device__ __forceinline__ void eval_stage_map(const uint8_t* __restrict__ maps, long long m, int cells, int ntiles, uint8_t* stage, int lane, int nlanes,
+                                               int32_t* status) {
+    const uint8_t* src = maps + (size_t)m * cells;
+    for (int c = lane; c < cells; c += nlanes) {
+        uint8_t t = src[c];
+        if (t >= ntiles) { atomicOr(status, PCGRL_STATUS_BAD_TILE); t = (uint8_t)(ntiles - 1); }
+        stage[c] = t;
+    }
+}
+
+template <int PROB, int G, class MaskT>
+__global__ __launch_bounds__(PCGRL_BLOCK) void k_get_stats(PcgrlParams P, const uint8_t* __restrict__ maps, int count, int32_t* __restrict__ rows_out,
+                                                            int32_t* status, int32_t* head, int32_t* jobs) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];      // per lane group the tile bytes of its map
+    constexpr int GPW = 64 / G, WPB = PCGRL_BLOCK / 64;
+    constexpr int NSTATS = PROB == PCGRL_PROB_BINARY ? 2 : (PROB == PCGRL_PROB_ZELDA ? 7 : (PROB == PCGRL_PROB_SOKOBAN ? 6 : 8));
+    DevGroup<G, MaskT> g;
+    const int lane64 = threadIdx.x & 63, wv = threadIdx.x >> 6, gw = lane64 / G;
+    const int W = P.width, H = P.height, cells = W * H;
+    uint8_t* tiles = smem + (size_t)(wv * GPW + gw) * reset_tile_bytes(cells);
+    const MaskT rowmask = row_valid<MaskT>(g.lane, W, H);
+    // wave-uniform loop: the groups of a wavefront go round together, a group beyond `count` sits the round out
+    for (long long base = ((long long)blockIdx.x * WPB + wv) * GPW; base < count; base += (long long)gridDim.x * WPB * GPW) {
+        const long long m = base + gw;
+        const bool have = m < count;
+        if (have) eval_stage_map(maps, m, cells, P.ntiles, tiles, g.lane, G, status);
+        __builtin_amdgcn_wave_barrier();
+        MaskT b0, b1, b2;
+        planes_from_tiles<MaskT>(P, tiles, (MaskT*)nullptr, have ? g.lane : -1, b0, b1, b2, false);
+        __builtin_amdgcn_wave_barrier();                                // (the stage is free for the next round)
+        int32_t s[PCGRL_MAX_STATS] = {0, 0, 0, 0, 0, 0, 0, 0};
+        bool need_solver = false;
+        if (have) need_solver = compute_item_stats<PROB>(g, P, b0, b1, b2, rowmask, s);
+        if (g.lane == 0 && have) {
+            int32_t* row = rows_out + (size_t)m * 8;
+#pragma unroll
+            for (int k = 0; k < 8; k++) row[k] = k < NSTATS ? s[k] : 0;      // (binary: the champion flag and bound of slots 2, 3 stay inside)
+            if (need_solver) jobs[atomicAdd(head + EVAL_HEAD_NJOBS, 1)] = (int32_t)m;
+        }
+    }
+}
+
+// `Bs`: what search_game_run reads of a DevBufs -- status, sok_use_lds, sok_fast_maxc (SearchGame<PROB>::build) and `map`, which every
+// wavefront points at its own clamped LDS copy of the job's map (environment 0 of a one-map batch): the agents work on the level
+// that build() left in LDS and on the regions and pools they are handed, nothing else of the struct is dereferenced.
+template <int PROB>
+__global__ __launch_bounds__(SS_THREADS) void k_get_stats_search(PcgrlParams P, DevBufs Bs, const uint8_t* __restrict__ maps, int32_t* __restrict__ rows_out,
+                                                                  int32_t* head, const int32_t* __restrict__ jobs, SokNode* pools, int pool_stride) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t ss_lds[];     // the full search region; the small ones are carved out of it
+    typedef SearchGame<PROB> Game;
+    typedef typename Game::Shared GameShared;
+    __shared__ GameShared s_game0;
+    __shared__ __attribute__((aligned(16))) uint8_t s_stage[SS_SEARCH_WAVES][EVAL_STAGE_BYTES];
+    __shared__ int s_big[EVAL_CHUNK];
+    __shared__ int s_nbig, s_base;
+    const int tid = (int)threadIdx.x, lane64 = tid & 63, wv = tid >> 6;
+    const int cells = P.width * P.height;
+    const int njobs = __hip_atomic_load(head + EVAL_HEAD_NJOBS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    SokNode* pool = pools + (size_t)blockIdx.x * pool_stride;
+    const int small_power = P.solver_power < SS_SMALL_POPS ? P.solver_power : SS_SMALL_POPS;
+    GameShared* small_games = reinterpret_cast<GameShared*>(ss_lds + SS_SEARCH_WAVES * SS_SMALL_WORDS);
+    DevBufs B = Bs;
+    B.map = s_stage[wv < SS_SEARCH_WAVES ? wv : 0];
+    for (;;) {
+        if (tid == 0) { s_base = atomicAdd(head + EVAL_HEAD_TICKET, EVAL_CHUNK); s_nbig = 0; }
+        __syncthreads();
+        const int base = s_base;
+        if (base >= njobs) break;                                           // block-uniform
+        const int n = njobs - base < EVAL_CHUNK ? njobs - base : EVAL_CHUNK;
+        if (wv < SS_SEARCH_WAVES) {
+            for (int j = wv; j < n; j += SS_SEARCH_WAVES) {
+                const int m = jobs[base + j];
+                eval_stage_map(maps, m, cells, P.ntiles, s_stage[wv], lane64, 64, B.status);
+                __builtin_amdgcn_wave_barrier();
+                __threadfence_block();
+                int res[Game::NRES] = {};
+                const bool final = search_game_run<PROB>(P, B, 0, small_games[wv], ss_lds + wv * SS_SMALL_WORDS, SS_SMALL_HEAP, SS_SMALL_TABLE, small_power,
+                                                         pool + (size_t)wv * SS_SMALL_NODES, lane64, res);
+                if (lane64 == 0) {
+                    if (final) Game::pack(rows_out + (size_t)m * 8, res);
+                    else s_big[atomicAdd(&s_nbig, 1)] = m;
+                }
+                __builtin_amdgcn_wave_barrier();
+            }
+        }
+        __syncthreads();
+        if (wv == 0) {
+            const int nbig = s_nbig;
+            for (int q = 0; q < nbig; q++) {
+                const int m = s_big[q];
+                eval_stage_map(maps, m, cells, P.ntiles, s_stage[0], lane64, 64, B.status);
+                __builtin_amdgcn_wave_barrier();
+                __threadfence_block();
+                int res[Game::NRES] = {};
+                search_game_run<PROB>(P, B, 0, s_game0, ss_lds, SOK_LDS_HEAP, SOK_LDS_TABLE, P.solver_power, pool, lane64, res);
+                if (lane64 == 0) Game::pack(rows_out + (size_t)m * 8, res);
+                __builtin_amdgcn_wave_barrier();
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// Problem.get_reward(new, old) and Problem.get_episode_over(new, start) over rows: `ref` is both the old and the start statistics
+// (a template like k_smb<0>: only the part that launches it holds an instance)
+template <int UNUSED>
+__global__ __launch_bounds__(256) void k_get_reward(PcgrlParams P, const int32_t* __restrict__ rows, const int32_t* __restrict__ ref, int count,
+                                                    double* __restrict__ reward_out, uint8_t* __restrict__ over_out) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < count; i += (long long)gridDim.x * 256) {
+        int32_t n[PCGRL_MAX_STATS], o[PCGRL_MAX_STATS];
+#pragma unroll
+        for (int k = 0; k < PCGRL_MAX_STATS; k++) { n[k] = rows[(size_t)i * 8 + k]; o[k] = ref[(size_t)i * 8 + k]; }
+        if (reward_out) reward_out[i] = compute_reward(P, n, o, P.prob);
+        if (over_out) over_out[i] = episode_over(P, n, o, P.prob) ? 1 : 0;
+    }
+}

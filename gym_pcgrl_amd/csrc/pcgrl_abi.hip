@@ -82,6 +82,7 @@
 #include "kernels_smb.h"
 #include "kernels_step_solver.h"
 #include "kernels_search_async.h"
+#include "kernels_evaluate.h"
 #include "search_big.h"
 #include "kernels_search_big.h"
 #if PCGRL_IN_PART(PART_CORE)
@@ -621,6 +622,8 @@ PCGRL_LOCAL int launch_step_zelda(pcgrl_env* h, const int32_t* actions, int pari
 PCGRL_LOCAL int launch_search(pcgrl_env* h, int32_t* sync, int list_a, int mode_a, int list_b, int mode_b, int parity, int rst_list, int clr, hipStream_t st);
 PCGRL_LOCAL int launch_smb(pcgrl_env* h, int32_t* sync, int list_a, int mode_a, int list_b, int mode_b, int parity, int rst_list, int clr, hipStream_t st, int inline_reset);
 PCGRL_LOCAL int launch_step_solver(pcgrl_env* h, const int32_t* actions, hipStream_t st, const RolloutArgs& R, int epb);
+PCGRL_LOCAL int launch_get_stats(pcgrl_env* h, const uint8_t* maps, int count, int32_t* rows_out, int32_t* head, int32_t* jobs, hipStream_t st);
+PCGRL_LOCAL int launch_get_stats_search(pcgrl_env* h, const uint8_t* maps, int32_t* rows_out, int32_t* head, const int32_t* jobs, SokNode* pools, int blocks, hipStream_t st);
 PCGRL_LOCAL int launch_search_async(pcgrl_env* h, int32_t* tickets, int list_a, int mode_a, int list_b, int mode_b, int parity, int rst_list, int clr, int budget, int resume, int small, hipStream_t st);
 // A launch with more than 64 KB of dynamic LDS needs the kernel's cap raised first.  That is a driver call (about a microsecond of
 // host time -- a fifth of what issuing a step costs), so it is made only when this process has not yet raised the cap of this kernel
@@ -755,6 +758,35 @@ static int launch_update_m(pcgrl_env* h, const int32_t* actions, int parity, hip
 
 PCGRL_LOCAL int launch_update(pcgrl_env* h, const int32_t* actions, int parity, hipStream_t st) {
     return h->P.mask_bytes == 4 ? launch_update_m<uint32_t>(h, actions, parity, st) : launch_update_m<uint64_t>(h, actions, parity, st);
+}
+// pcgrl_get_stats, first launch (kernels_evaluate.h): a lane group per map, grid-stride over `count`
+template <int PROB>
+static int launch_get_stats_p(pcgrl_env* h, const uint8_t* maps, int count, int32_t* rows_out, int32_t* head, int32_t* jobs, hipStream_t st) {
+    const PcgrlParams& P = h->P;
+    const int per_block = (PCGRL_BLOCK / 64) * (64 / P.group);            // maps a block takes per round
+    const long long blocks = ((long long)count + per_block - 1) / per_block;
+    const int grid = (int)(blocks < 8192 ? blocks : 8192);
+    const size_t lds = (size_t)per_block * reset_tile_bytes(P.width * P.height);
+    if (P.group == 16 && P.mask_bytes == 4)
+        hipLaunchKernelGGL((k_get_stats<PROB, 16, uint32_t>), dim3(grid), dim3(PCGRL_BLOCK), lds, st, P, maps, count, rows_out, h->B.status, head, jobs);
+    else if (P.group == 16)
+        hipLaunchKernelGGL((k_get_stats<PROB, 16, uint64_t>), dim3(grid), dim3(PCGRL_BLOCK), lds, st, P, maps, count, rows_out, h->B.status, head, jobs);
+    else if (P.mask_bytes == 4)
+        hipLaunchKernelGGL((k_get_stats<PROB, 64, uint32_t>), dim3(grid), dim3(PCGRL_BLOCK), lds, st, P, maps, count, rows_out, h->B.status, head, jobs);
+    else
+        hipLaunchKernelGGL((k_get_stats<PROB, 64, uint64_t>), dim3(grid), dim3(PCGRL_BLOCK), lds, st, P, maps, count, rows_out, h->B.status, head, jobs);
+    HIPCHK(hipGetLastError());
+    return PCGRL_OK;
+}
+PCGRL_LOCAL int launch_get_stats(pcgrl_env* h, const uint8_t* maps, int count, int32_t* rows_out, int32_t* head, int32_t* jobs, hipStream_t st) {
+    switch (h->P.prob) {
+        case PCGRL_PROB_BINARY: return launch_get_stats_p<PCGRL_PROB_BINARY>(h, maps, count, rows_out, head, jobs, st);
+        case PCGRL_PROB_ZELDA: return launch_get_stats_p<PCGRL_PROB_ZELDA>(h, maps, count, rows_out, head, jobs, st);
+        case PCGRL_PROB_MDUNGEON: return launch_get_stats_p<PCGRL_PROB_MDUNGEON>(h, maps, count, rows_out, head, jobs, st);
+        case PCGRL_PROB_DDAVE: return launch_get_stats_p<PCGRL_PROB_DDAVE>(h, maps, count, rows_out, head, jobs, st);
+        case PCGRL_PROB_SOKOBAN: return launch_get_stats_p<PCGRL_PROB_SOKOBAN>(h, maps, count, rows_out, head, jobs, st);
+        default: return PCGRL_EINVAL;
+    }
 }
 #endif  // PART_UPDATE
 
@@ -1014,6 +1046,29 @@ PCGRL_LOCAL int launch_step_solver(pcgrl_env* h, const int32_t* actions, hipStre
         case PCGRL_PROB_SOKOBAN: return m4 ? launch_step_solver_p<PCGRL_PROB_SOKOBAN, uint32_t>(h, actions, st, R, epb) : launch_step_solver_p<PCGRL_PROB_SOKOBAN, uint64_t>(h, actions, st, R, epb);
         case PCGRL_PROB_MDUNGEON: return m4 ? launch_step_solver_p<PCGRL_PROB_MDUNGEON, uint32_t>(h, actions, st, R, epb) : launch_step_solver_p<PCGRL_PROB_MDUNGEON, uint64_t>(h, actions, st, R, epb);
         default: return m4 ? launch_step_solver_p<PCGRL_PROB_DDAVE, uint32_t>(h, actions, st, R, epb) : launch_step_solver_p<PCGRL_PROB_DDAVE, uint64_t>(h, actions, st, R, epb);
+    }
+}
+
+// pcgrl_get_stats, second launch (kernels_evaluate.h): the parked maps' searches on `blocks` persistent blocks, each with a node pool
+// of its own in the caller's workspace.  Of the DevBufs copy the kernel reads the three fields SearchGame<PROB>::build looks at.
+template <int PROB>
+static int launch_get_stats_search_p(pcgrl_env* h, const uint8_t* maps, int32_t* rows_out, int32_t* head, const int32_t* jobs, SokNode* pools, int blocks, hipStream_t st) {
+    const size_t lds = sok_lds_bytes();
+    { const int rca = lds_cap<k_get_stats_search<PROB>>(h->device, lds); if (rca) return rca; }
+    DevBufs Bs;
+    memset(&Bs, 0, sizeof(Bs));
+    Bs.status = h->B.status; Bs.sok_use_lds = h->B.sok_use_lds; Bs.sok_fast_maxc = h->B.sok_fast_maxc;
+    const int pool_stride = (int)(sok_pool_bytes(&h->cfg) / sizeof(SokNode));
+    hipLaunchKernelGGL((k_get_stats_search<PROB>), dim3(blocks), dim3(SS_THREADS), lds, st, h->P, Bs, maps, rows_out, head, jobs, pools, pool_stride);
+    HIPCHK(hipGetLastError());
+    return PCGRL_OK;
+}
+PCGRL_LOCAL int launch_get_stats_search(pcgrl_env* h, const uint8_t* maps, int32_t* rows_out, int32_t* head, const int32_t* jobs, SokNode* pools, int blocks, hipStream_t st) {
+    switch (h->P.prob) {
+        case PCGRL_PROB_SOKOBAN: return launch_get_stats_search_p<PCGRL_PROB_SOKOBAN>(h, maps, rows_out, head, jobs, pools, blocks, st);
+        case PCGRL_PROB_MDUNGEON: return launch_get_stats_search_p<PCGRL_PROB_MDUNGEON>(h, maps, rows_out, head, jobs, pools, blocks, st);
+        case PCGRL_PROB_DDAVE: return launch_get_stats_search_p<PCGRL_PROB_DDAVE>(h, maps, rows_out, head, jobs, pools, blocks, st);
+        default: return PCGRL_EINVAL;
     }
 }
 
@@ -1630,6 +1685,63 @@ int pcgrl_set_maps(pcgrl_env* h, const uint8_t* maps, void* stream) {
     rc = set_maps_one(h, maps, stream);
     if (rc) return rc;
     h->parity ^= 1;
+    return PCGRL_OK;
+}
+
+// ---- pcgrl_get_stats / pcgrl_get_reward (kernels_evaluate.h): the problem's pure functions on the caller's maps and rows -------------
+// The fast form: the row-bitboard statistics (maps up to 64 x 64) and, for the search problems, the compact searches in LDS.
+static bool eval_applies(const pcgrl_config* c) {
+    if (c->prob == PCGRL_SMB || big_map(c)) return false;
+    return !solver_prob(c->prob) || (!big_search(c) && sok_in_lds(c));
+}
+// The caller's workspace, cut like `scratch` (ScratchPlan): pcgrl_get_stats_bytes reports `total`, pcgrl_get_stats points its two
+// launches at the regions.  head: the job counter and the chunk ticket; jobs: the indices of the maps that need the planner; pools:
+// a node pool per persistent block of k_get_stats_search (as many blocks as `count` maps can keep busy, SOK_BLOCKS at most).
+struct EvalPlan { Region head, jobs, pools; int blocks; size_t total; };
+static EvalPlan eval_plan(const pcgrl_config* c, int count) {
+    EvalPlan E = {};
+    Bump b = {0};
+    E.head = b.take(256);
+    if (solver_prob(c->prob)) {
+        const int chunks = (int)(((long long)count + EVAL_CHUNK - 1) / EVAL_CHUNK);
+        E.blocks = chunks < SOK_BLOCKS ? chunks : SOK_BLOCKS;
+        E.jobs = b.take(align_up((size_t)count * 4, 256));
+        E.pools = b.take((size_t)E.blocks * sok_pool_bytes(c));
+    }
+    E.total = b.off;
+    return E;
+}
+size_t pcgrl_get_stats_bytes(const pcgrl_config* c, int32_t count) {
+    if (!c || count < 1) return 0;
+    pcgrl_config one = *c;
+    one.num_envs = 1;                    // (the workspace does not depend on the handle's batch)
+    if (validate_config(&one) != PCGRL_OK || !eval_applies(&one)) return 0;
+    return eval_plan(&one, count).total;
+}
+int pcgrl_get_stats(pcgrl_env* h, const uint8_t* maps, int32_t count, int32_t* rows_out, void* work, size_t work_bytes, void* stream) {
+    if (!h || !h->bound) return PCGRL_ESTATE;
+    if (!maps || !rows_out || !work || count < 1 || ((uintptr_t)work & 255) != 0) return PCGRL_EINVAL;
+    const size_t need = pcgrl_get_stats_bytes(&h->cfg, count);
+    if (need == 0 || work_bytes < need) return PCGRL_EINVAL;
+    DeviceGuard guard(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    const EvalPlan E = eval_plan(&h->cfg, count);
+    uint8_t* w = (uint8_t*)work;
+    int32_t* head = at<int32_t>(w, E.head);
+    HIPCHK(hipMemsetAsync(head, 0, E.head.bytes, st));
+    int rc = launch_get_stats(h, maps, count, rows_out, head, at<int32_t>(w, E.jobs), st);
+    if (rc) return rc;
+    // the job count stays on the device: the search launch reads it there
+    if (E.pools.bytes) rc = launch_get_stats_search(h, maps, rows_out, head, at<int32_t>(w, E.jobs), at<SokNode>(w, E.pools), E.blocks, st);
+    return rc;
+}
+int pcgrl_get_reward(pcgrl_env* h, const int32_t* rows, const int32_t* ref_rows, int32_t count, double* reward_out, uint8_t* over_out, void* stream) {
+    if (!h || !h->bound) return PCGRL_ESTATE;
+    if (!rows || !ref_rows || count < 1 || (!reward_out && !over_out)) return PCGRL_EINVAL;
+    DeviceGuard guard(h->device);
+    const int grid = (int)(((long long)count + 255) / 256 < 4096 ? ((long long)count + 255) / 256 : 4096);
+    hipLaunchKernelGGL(k_get_reward<0>, dim3(grid), dim3(256), 0, (hipStream_t)stream, h->P, rows, ref_rows, count, reward_out, over_out);
+    HIPCHK(hipGetLastError());
     return PCGRL_OK;
 }
 

@@ -53,6 +53,15 @@ class InfoBatch:
         return out
 
 
+class Evaluation:
+    """What BatchedPcgrlEnv.evaluate() returns: `rows` int32 [M, 8] (the packed device rows, include/pcgrl_hip.h pcgrl_layout.stats),
+    `stats` (the same decoded: the columns of env.stats), and -- with a `ref` -- `reward` float64 [M] and `over` bool [M]; None without."""
+    __slots__ = ("rows", "stats", "reward", "over")
+
+    def __init__(self, rows, stats, reward=None, over=None):
+        self.rows, self.stats, self.reward, self.over = rows, stats, reward, over
+
+
 class BatchedPcgrlEnv:
     metadata = {"render.modes": []}
 
@@ -91,6 +100,9 @@ class BatchedPcgrlEnv:
         self._async_nslots = 0
         self._row = None               # bind_rollout_row(): (column pointers in _lib.ROW_FIELDS order, the tensors kept alive)
         self._row_applied = None       # what the handle was last told (pcgrl_bind_row): (column pointers, actions are int64)
+        self._eval_work = None         # evaluate(): the workspace of pcgrl_get_stats, regrown on demand
+        self._eval_scratch = None      # evaluate(), configurations without a fast form: a private scratch environment
+        self._was_reset = False        # the handle has been reset since it was allocated: it carries episodes
         self._update_spaces()
         self.seed(seed)
 
@@ -186,6 +198,7 @@ class BatchedPcgrlEnv:
             setattr(bufs, name, b[name].data_ptr() if b[name] is not None else None)
         _lib.check(self._lib.pcgrl_bind(handle, C.byref(bufs), self._stream()), "pcgrl_bind")
         self._handle, self._bufs, self._layout = handle, b, lay
+        self._was_reset = False
         self._alloc_dims = (w, h)
         if first or self._probs_dirty:
             _lib.check(self._lib.pcgrl_set_tile_probs(self._handle, self._stream()), "pcgrl_set_tile_probs")
@@ -242,6 +255,7 @@ class BatchedPcgrlEnv:
         self._prob.adjust_param(**kwargs)
         self._rep.adjust_param(**kwargs)
         self._update_spaces()
+        self._drop_eval_scratch()          # (evaluate()'s scratch environment carries the parameters it was made with)
         if self._handle is not None:
             # A new width / height takes effect on the maps at the next reset() (representation.py:40-45: only reset() makes a map of
             # the new size); until then the allocated maps go on being stepped, with the problem's new size in its formulas -- what
@@ -259,14 +273,16 @@ class BatchedPcgrlEnv:
                                  "16384 bordered cells, 1 <= solver_power <= 10^6; smb: width <= 250, height 3..32, solver_power <= 16383)" %
                                  ", ".join("%s=%r" % kv for kv in kwargs.items()))
             rc = self._lib.pcgrl_configure(self._handle, C.byref(cfg))
-            if rc == _lib.PCGRL_EINVAL and not self._needs_reset:
+            if rc == _lib.PCGRL_EINVAL:
                 # a valid configuration the handle cannot take in place: a solver_power beyond what its search arena was sized for, or one
                 # that moves the searches to the other kernel family.  The buffers are re-allocated by the next reset(), which has to
-                # come first (the reference would let the new solver_power take effect in the middle of the episode)
+                # come first (the reference would let the new solver_power take effect in the middle of the episode) -- also where the
+                # handle has not been reset yet (evaluate() binds one before the first reset()): it keeps NONE of this call's parameters
                 self._realloc = True
-                self._needs_reset = True
-                self._reset_reason = "adjust_param(%s) needs another search arena" % ", ".join("%s=%r" % kv for kv in kwargs.items())
-            elif rc != _lib.PCGRL_EINVAL:
+                if not self._needs_reset:
+                    self._needs_reset = True
+                    self._reset_reason = "adjust_param(%s) needs another search arena" % ", ".join("%s=%r" % kv for kv in kwargs.items())
+            else:
                 _lib.check(rc, "pcgrl_configure")
             if rc == 0 and self._prob._probs_touched:
                 _lib.check(self._lib.pcgrl_set_tile_probs(self._handle, self._stream()), "pcgrl_set_tile_probs")
@@ -294,6 +310,7 @@ class BatchedPcgrlEnv:
             self._realloc = False
         _lib.check(self._lib.pcgrl_reset(self._handle, self._stream()), "pcgrl_reset")
         self._needs_reset = False
+        self._was_reset = True
         self._reset_reason = None
         return self._obs()
 
@@ -641,6 +658,94 @@ class BatchedPcgrlEnv:
         self._last_maps = m
         _lib.check(self._lib.pcgrl_set_maps(self._handle, C.c_void_p(m.data_ptr()), self._stream()), "pcgrl_set_maps")
 
+    # ---- Problem.get_stats / get_reward / get_episode_over on any level (pcgrl_get_stats, pcgrl_get_reward)
+    def evaluate(self, maps, ref=None, chunk=65536):
+        """Score `maps` -- array-like uint8 [M, H, W] on any device, M independent of num_envs -- with this environment's problem and
+        the parameters in force (adjust_param applies): Problem.get_stats of every map, and with `ref` (int32 [M, 8] rows, or [8]
+        for all: an earlier evaluate().rows or this environment's own stats / start-stats rows) Problem.get_reward(new=maps, old=ref)
+        and Problem.get_episode_over(new=maps, start=ref).  Returns an Evaluation (rows, stats, reward, over).  A pure function: the
+        running episodes, their random streams and pending asynchronous searches are not touched, nothing needs a reset() first, the
+        input is not modified (a tile id >= get_num_tiles() is clamped on the way and reported by check_status()), and nothing is
+        waited for.  Where the library has no one-call form (smb, maps beyond 64 x 64, the general searches) the maps go, `chunk` at a
+        time, through a private scratch environment's set_maps() instead -- and so they do while an adjust_param() that the handle
+        could not take in place (a larger solver_power: another search arena) waits for the next reset(): the handle still carries
+        the episodes and the old parameters, the scratch environment scores -- rewards included -- with the new ones.
+        The calls on one environment share a cached workspace: issue them on one stream (the current stream of the first call),
+        or synchronise between calls made on different streams."""
+        torch = self._torch
+        dims = (self._prob._width, self._prob._height)
+        if self._handle is None or (not self._was_reset and (self._realloc or dims != self._alloc_dims)):
+            # no handle yet, or one that was only ever bound for scoring and cannot take the parameters in force: a new one
+            # (bound, not reset: step() and set_maps() still ask for reset())
+            self._allocate()
+            self._realloc = False
+        stale = self._realloc              # the handle keeps its episodes and, until the next reset(), the parameters before the refused change
+        m = maps if torch.is_tensor(maps) else torch.as_tensor(np.asarray(maps))
+        if m.dim() != 3:
+            raise ValueError("evaluate(): maps must be [M, H, W], got shape %s" % (tuple(m.shape),))
+        w, h = self._alloc_dims
+        if tuple(m.shape[1:]) != (h, w) or m.shape[0] < 1:
+            raise ValueError("evaluate(): maps of shape %s for an environment of %d rows x %d columns (at least one map)" % (tuple(m.shape), h, w))
+        m = m.to(device=self.device, dtype=torch.uint8).contiguous()
+        M = int(m.shape[0])
+        rows = torch.empty((M, 8), dtype=torch.int32, device=self.device)
+        cfg = self._config(self._alloc_dims)
+        need = 0 if stale else int(self._lib.pcgrl_get_stats_bytes(C.byref(cfg), M))
+        if need:
+            if self._eval_work is None or self._eval_work.numel() < need:
+                self._eval_work = torch.empty((need,), dtype=torch.uint8, device=self.device)
+            _lib.check(self._lib.pcgrl_get_stats(self._handle, C.c_void_p(m.data_ptr()), M, C.c_void_p(rows.data_ptr()),
+                                                 C.c_void_p(self._eval_work.data_ptr()), self._eval_work.numel(), self._stream()), "pcgrl_get_stats")
+        else:
+            self._evaluate_by_set_maps(m, rows, int(chunk))
+        reward = over = None
+        if ref is not None:
+            r = ref if torch.is_tensor(ref) else torch.as_tensor(np.asarray(ref))
+            if r.dtype not in (torch.int32, torch.int64) or tuple(r.shape) not in ((8,), (M, 8)):
+                raise ValueError("evaluate(): ref must be int32 rows of shape [%d, 8] or [8], got %s %s" % (M, r.dtype, tuple(r.shape)))
+            r = r.to(device=self.device, dtype=torch.int32)
+            r = (r.expand(M, 8) if r.dim() == 1 else r).contiguous()
+            reward = torch.empty((M,), dtype=torch.float64, device=self.device)
+            over = torch.empty((M,), dtype=torch.uint8, device=self.device)
+            scorer = self._eval_scratch._handle if stale else self._handle
+            _lib.check(self._lib.pcgrl_get_reward(scorer, C.c_void_p(rows.data_ptr()), C.c_void_p(r.data_ptr()), M,
+                                                  C.c_void_p(reward.data_ptr()), C.c_void_p(over.data_ptr()), self._stream()), "pcgrl_get_reward")
+            over = over.view(torch.bool)
+        return Evaluation(rows, self._prob.decode_rows(rows), reward, over)
+
+    def _evaluate_by_set_maps(self, m, rows, chunk):
+        """evaluate() where pcgrl_get_stats_bytes is 0: a scratch environment of this problem (wide representation, the same
+        adjust_param state, no auto-reset) of min(M, chunk) maps, reset once; the maps go through its set_maps() chunk by chunk and
+        the rows are copied out with the library's private slots zeroed.  This environment's handle is not touched -- its status word
+        included: what set_maps() clamps on this route is reported by the scratch environment's (self._eval_scratch.check_status())."""
+        import copy
+        torch = self._torch
+        M = int(m.shape[0])
+        n = max(1, min(M, chunk))
+        sc = self._eval_scratch
+        if sc is None or sc.num_envs != n:
+            self._drop_eval_scratch()
+            sc = BatchedPcgrlEnv(prob=self._prob.name, rep="wide", num_envs=n, device=self.device, seed=0, auto_reset=False, tuning=self._tuning)
+            sc._prob = copy.deepcopy(self._prob)
+            sc._prob._width, sc._prob._height = self._alloc_dims
+            sc._update_spaces()
+            sc.reset()
+            self._eval_scratch = sc
+        nstats = int(sc._layout.nstats)
+        for i in range(0, M, n):
+            part = m[i:i + n]
+            k = int(part.shape[0])
+            if k < n:                      # the last chunk: the handle takes exactly n maps
+                part = torch.cat([part, torch.zeros((n - k,) + tuple(part.shape[1:]), dtype=torch.uint8, device=self.device)])
+            sc.set_maps(part)
+            rows[i:i + k] = sc._bufs["stats"][:k]
+        rows[:, nstats:] = 0
+
+    def _drop_eval_scratch(self):
+        if self._eval_scratch is not None:
+            self._eval_scratch.close()
+            self._eval_scratch = None
+
     def check_status(self):
         """Raise if a kernel flagged an unsupported case (synchronises)."""
         st = C.c_int32()
@@ -654,7 +759,7 @@ class BatchedPcgrlEnv:
             raise IndexError("an action outside the action space was passed to step()/rollout() (it was clamped into range; "
                              "the reference raises IndexError or writes the bad value)")
         if st.value & 4:
-            raise ValueError("set_maps() was given a tile id >= get_num_tiles() (it was clamped)")
+            raise ValueError("set_maps() / evaluate() was given a tile id >= get_num_tiles() (it was clamped)")
         return st.value
 
     def profile(self, enable=True):
@@ -834,10 +939,12 @@ class BatchedPcgrlEnv:
         return out
 
     def close(self):
+        self._drop_eval_scratch()
         self._free()
 
     def __del__(self):
         try:
+            self._drop_eval_scratch()
             self._free()
         except Exception:
             pass

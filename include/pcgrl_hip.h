@@ -16,6 +16,7 @@
  *                                    vector-env auto-reset the reference delegates to SubprocVecEnv (utils.py:60-71)
  *   pcgrl_set_tile_probs             Problem.adjust_param(probs=...) probs/problem.py:68-72
  *   pcgrl_set_maps                   direct assignment of Representation._map (tests, curriculum loaders)
+ *   pcgrl_get_stats / pcgrl_get_reward   Problem.get_stats / get_reward / get_episode_over called on any level, outside an episode
  *
  * Conventions: plain pointers and sizes only; every function returns 0 on success or a negative
  * PCGRL_E* code (no exceptions cross the ABI); all device buffers are OWNED BY THE CALLER (hipMalloc,
@@ -41,7 +42,9 @@ extern "C" {
  * 15: without auto_reset the heat map holds 32-bit counts (an episode goes on past done); max_changes beyond 65 535 there.
  *     Still 15: + pcgrl_row / pcgrl_bind_row -- purely additive (one struct, one entry point; no existing struct or signature
  *     changed), so the number stays; a caller detects the feature by the symbol pcgrl_bind_row.
- *     Still 15: + pcgrl_render_desc / pcgrl_render -- additive in the same way; a caller detects it by the symbol pcgrl_render. */
+ *     Still 15: + pcgrl_render_desc / pcgrl_render -- additive in the same way; a caller detects it by the symbol pcgrl_render.
+ *     Still 15: + pcgrl_get_stats_bytes / pcgrl_get_stats / pcgrl_get_reward -- additive in the same way (three entry points, no struct);
+ *     a caller detects them by the symbol pcgrl_get_stats. */
 #define PCGRL_ABI_VERSION 15
 #define PCGRL_OK 0
 #define PCGRL_EINVAL (-1)   /* bad argument / unsupported configuration */
@@ -282,6 +285,38 @@ typedef struct pcgrl_render_desc {
     uint8_t* out;                   /* DEVICE, 16-byte aligned */
 } pcgrl_render_desc;
 int pcgrl_render(pcgrl_env* env, const pcgrl_render_desc* d, void* stream);
+/* ---- The problem's pure functions on levels and statistics rows of the caller's: what the reference's users get from calling
+ * Problem.get_stats(map), Problem.get_reward(new, old) and Problem.get_episode_over(new, old) on any level -- a generator's output, a
+ * level corpus, the candidates of an evolutionary search -- not only on the one an episode edits.  `count` is independent of num_envs;
+ * no episode state is read or written (maps, counters, statistics, random streams, work lists, pending asynchronous searches: all
+ * untouched, nothing is flushed); pcgrl_bind is needed, pcgrl_reset is not (PCGRL_ESTATE before bind); asynchronous on the stream.
+ * The parameters (targets, solver_power, reward weights) are the ones in force on the handle: a pcgrl_configure before the call applies.
+ *
+ * Problem.get_stats (binary_prob.py:81-92, zelda_prob.py:80-122, sokoban_prob.py:85-145, mdungeon_prob.py, ddave_prob.py)
+ *   maps      DEVICE u8 [count,H,W] for the handle's current width / height; read only.
+ *   rows_out  DEVICE i32 [count,8] in the packed layout of pcgrl_layout.stats: slots [0,nstats) as in the handle's `stats` rows,
+ *             slots [nstats,8) zero (binary: the library's private slots 2 and 3 are zero here).
+ *   work      DEVICE, 256-byte aligned, at least pcgrl_get_stats_bytes(cfg, count) bytes; the call's own, free again when the stream
+ *             has passed it.
+ *   Of the handle only the sticky status word is written: bit 0 for a level outside the search limits, bit 2 for a tile id >= the
+ *   number of tiles (the tile is clamped in registers: the caller's map is not modified).
+ *   PCGRL_EINVAL: a NULL pointer, count < 1, work not 256-byte aligned, work_bytes below pcgrl_get_stats_bytes, or a configuration
+ *   without a fast form.
+ * pcgrl_get_stats_bytes: from the configuration alone (num_envs is ignored; no GPU needed).  0 = this configuration has no fast form
+ *   (or count < 1); else >= 256.  The fast form: binary, zelda, sokoban, mdungeon and ddave on maps up to 64 x 64 -- the search
+ *   problems with levels of at most 256 bordered cells and solver_power <= 5000 (the searches that run in LDS).  smb, larger maps and
+ *   the general searches: score them through a scratch handle and pcgrl_set_maps. */
+size_t pcgrl_get_stats_bytes(const pcgrl_config* cfg, int32_t count);
+int    pcgrl_get_stats(pcgrl_env* env, const uint8_t* maps, int32_t count, int32_t* rows_out,
+                       void* work, size_t work_bytes, void* stream);
+/* Problem.get_reward + Problem.get_episode_over on statistics rows (binary_prob.py:98-120, zelda_prob.py:124-156,
+ * sokoban_prob.py:157-189, mdungeon_prob.py:183-222, ddave_prob.py:187-220, smb_prob.py:169-192): every problem and size, smb included.
+ *   rows, ref_rows  DEVICE i32 [count,8]: outputs of pcgrl_get_stats or the handle's own stats / start_stats buffers (the private
+ *                   binary slots are not read).  ref_rows is `old_stats` for the reward and the start statistics for `over`.
+ *   reward_out      DEVICE f64 [count];  over_out  DEVICE u8 [count] -- either may be NULL, not both.
+ *   `over` is the problem's own criterion only: max_changes / max_iterations belong to an episode, not to a level. */
+int    pcgrl_get_reward(pcgrl_env* env, const int32_t* rows, const int32_t* ref_rows, int32_t count,
+                        double* reward_out, uint8_t* over_out, void* stream);
 /* ActionMap.step for the wide representation (wrappers.py:139-154): flat DEVICE i32 [N] index into
  * (H, W, tiles) -> xyv DEVICE i32 [N,3] = (x, y, tile), the action pcgrl_step takes. */
 int pcgrl_action_map(pcgrl_env* env, const int32_t* flat, int32_t* xyv, void* stream);

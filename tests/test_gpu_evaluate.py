@@ -1,0 +1,408 @@
+"""BatchedPcgrlEnv.evaluate() / pcgrl_get_stats / pcgrl_get_reward on the GPU: Problem.get_stats, get_reward and get_episode_over of
+arbitrary levels, bit for bit against the golden fixtures and the CPU oracle, and without a trace on the handle that computed them.
+Every case uses a handle of THREE environments and scores another number of maps."""
+import os
+
+import numpy as np
+import pytest
+
+import oracle_lib as ol
+
+pytestmark = pytest.mark.gpu
+G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+N_ENVS = 3
+
+
+def _torch():
+    import torch
+    assert torch.cuda.is_available(), "these tests need the MI355X"
+    return torch
+
+
+def _make(prob, h, w, power=None, rep="wide", tuning=None, seed=1000, auto_reset=True):
+    from gym_pcgrl_amd.envs import BatchedPcgrlEnv
+    env = BatchedPcgrlEnv(prob=prob, rep=rep, num_envs=N_ENVS, seed=seed, auto_reset=auto_reset, tuning=tuning)
+    kw = dict(width=w, height=h)
+    if power is not None and prob != "smb":
+        kw["solver_power"] = int(power)
+    env.adjust_param(**kw)
+    if power is not None and prob == "smb":      # smb_prob.py:40-53: solver_power is an attribute there, not an adjust_param key
+        env._prob._solver_power = int(power)
+        env.adjust_param()
+    return env
+
+
+def _fixture(name):
+    d = np.load(os.path.join(G, "stats_%s.npz" % name))
+    prob = name.split("_")[0]
+    power = int(d["solver_power"]) if "solver_power" in d.files else None
+    return prob, d["maps"], d["stats"], power
+
+
+def _has_fast_form(env, count):
+    import ctypes as C
+    cfg = env._config()
+    return int(env._lib.pcgrl_get_stats_bytes(C.byref(cfg), count)) > 0
+
+
+def _check_fixture(name, tuning=None, fast=True):
+    _torch()
+    prob, maps, want, power = _fixture(name)
+    assert maps.shape[0] != N_ENVS
+    env = _make(prob, maps.shape[1], maps.shape[2], power, tuning=tuning)
+    assert _has_fast_form(env, maps.shape[0]) == fast
+    ev = env.evaluate(maps)
+    got = ev.stats.cpu().numpy().astype(np.int64)
+    assert env.check_status() == 0
+    bad = np.nonzero((got != want).any(1))[0]
+    assert bad.size == 0, (bad[:5], got[bad[:5]], want[bad[:5]])
+    rows = ev.rows.cpu().numpy()
+    assert rows.shape == (maps.shape[0], 8) and rows.dtype == np.int32
+    assert not rows[:, env._layout.nstats:].any()           # the slots beyond the problem's statistics (binary: the private ones) are zero
+    env.close()
+
+
+# ------------------------------------------------------------------ known answers at the edges of each mapping
+KAT = ["binary_1x1", "binary_8x1", "binary_1x9", "binary_5x5", "binary_16x11", "binary_14x14", "binary_64x64",
+       "zelda_5x5", "zelda_11x16", "zelda_16x11",
+       "sokoban_4x6", "sokoban_5x5", "sokoban_8x8",
+       "mdungeon_1x6_p5000", "mdungeon_5x5_p5000", "mdungeon_6x9_p300",
+       "ddave_1x5_p5000", "ddave_5x5_p5000", "ddave_6x9_p150"]
+
+
+@pytest.mark.parametrize("name", KAT)
+def test_known_answers(name):
+    _check_fixture(name)
+
+
+def test_known_answers_generic_search():
+    _check_fixture("sokoban_5x5", tuning={"sok_generic": 1})
+
+
+@pytest.mark.parametrize("name", ["binary_65x130", "sokoban_16x24_p2500", "smb_4x9_p200"])
+def test_fallback_matches_fixture(name):
+    """No one-call form (pcgrl_get_stats_bytes == 0): the maps go through a private scratch environment."""
+    _check_fixture(name, fast=False)
+
+
+# ------------------------------------------------------------------ shapes no fixture has, against the CPU oracle
+@pytest.mark.parametrize("prob,h,w", [("binary", 7, 40), ("zelda", 16, 33), ("binary", 17, 5), ("binary", 64, 33)])
+def test_random_maps_vs_oracle(prob, h, w):
+    _torch()
+    rs = np.random.RandomState(h * 1000 + w)
+    nt = len(ol.TILES[prob])
+    maps = np.empty((40, h, w), np.uint8)
+    for i in range(40):                              # from nearly empty to nearly full, every tile
+        p_solid = rs.uniform(0.1, 0.7)
+        p = np.full(nt, (1.0 - p_solid) / max(nt - 1, 1))
+        p[1] = p_solid
+        if prob == "zelda":                          # mostly floor besides the walls
+            p[:] = (1.0 - p_solid) * 0.4 / (nt - 2)
+            p[0], p[1] = (1.0 - p_solid) * 0.6, p_solid
+        maps[i] = rs.choice(nt, size=(h, w), p=p / p.sum())
+    want = np.stack([ol.get_stats(prob, m) for m in maps])
+    env = _make(prob, h, w)
+    assert _has_fast_form(env, 40)
+    got = env.evaluate(maps).stats.cpu().numpy().astype(np.int64)
+    assert env.check_status() == 0
+    assert np.array_equal(got, want), np.nonzero((got != want).any(1))[0][:5]
+    env.close()
+
+
+# ------------------------------------------------------------------ count handling
+@pytest.mark.parametrize("name", ["binary_14x14", "sokoban_5x5", "zelda_16x11"])
+def test_count_one_and_five(name):
+    torch = _torch()
+    prob, maps, _, power = _fixture(name)
+    env = _make(prob, maps.shape[1], maps.shape[2], power)
+    full = env.evaluate(maps).rows.clone()
+    one = env.evaluate(maps[7:8]).rows.clone()
+    five = env.evaluate(maps[20:25]).rows.clone()
+    assert torch.equal(one, full[7:8]) and torch.equal(five, full[20:25])
+    assert env.check_status() == 0
+    env.close()
+
+
+# ------------------------------------------------------------------ purity
+def _random_actions(env, rs, steps):
+    nt = env.get_num_tiles()
+    return rs.randint(0, nt + 1, size=(steps, N_ENVS)).astype(np.int32)      # narrow: 0 = no change, else tile + 1
+
+
+def _step_outputs(env, a):
+    obs, rew, done, info = env.step(a)
+    return [obs["map"].clone(), obs["pos"].clone(), obs["heatmap"].clone(), rew.clone(), done.clone(), info.table.clone()]
+
+
+@pytest.mark.parametrize("prob", ["binary", "sokoban"])
+def test_evaluate_leaves_no_trace(prob):
+    torch = _torch()
+    from gym_pcgrl_amd.envs import BatchedPcgrlEnv
+    _, maps, want, power = _fixture("binary_14x14" if prob == "binary" else "sokoban_5x5")
+    envs = [BatchedPcgrlEnv(prob=prob, rep="narrow", num_envs=N_ENVS, seed=77) for _ in range(2)]
+    rs = np.random.RandomState(5)
+    acts = _random_actions(envs[0], rs, 40)
+    for env in envs:
+        env.reset()
+        for t in range(20):
+            env.step(acts[t])
+    env, twin = envs
+    before = env.state_dict()
+    given = torch.as_tensor(maps[:5]).to(env.device)
+    kept = given.clone()
+    ev = env.evaluate(given)
+    assert np.array_equal(ev.stats.cpu().numpy().astype(np.int64), want[:5])
+    after = env.state_dict()
+    assert torch.equal(given, kept)                              # the input is the caller's
+    assert before.keys() == after.keys()
+    for k in before:
+        assert (before[k] is None and after[k] is None) or torch.equal(before[k], after[k]), k
+    for t in range(20, 40):                                      # ... and the episodes go on as if nothing had happened
+        got, exp = _step_outputs(env, acts[t]), _step_outputs(twin, acts[t])
+        if t % 5 == 0:
+            env.evaluate(given)
+        for k, (x, y) in enumerate(zip(got, exp)):
+            assert torch.equal(x, y), (t, k)
+    assert env.check_status() == 0
+    for e in envs:
+        e.close()
+
+
+def _long_search_changes(maps, n):
+    """n (map, (x, y, tile)) pairs from the sokoban fixture: turning that wall cell into floor leaves a level the solver has to work on
+    for a while (the oracle's agents pop dozens of states), so a tick with a one-pop budget cannot finish its step."""
+    out = []
+    for m in maps:
+        for y, x in zip(*np.nonzero(m == 1)):
+            b = m.copy()
+            b[y, x] = 0
+            _, it = ol.get_stats("sokoban", b, with_iters=True)
+            if int(it.max()) >= 40:
+                out.append((m, (int(x), int(y), 0)))
+                break
+        if len(out) == n:
+            return out
+    raise AssertionError("the fixture has no such levels")
+
+
+def test_evaluate_leaves_pending_searches_alone():
+    torch = _torch()
+    from gym_pcgrl_amd.envs import BatchedPcgrlEnv
+    _, maps, want, _ = _fixture("sokoban_5x5")
+    picks = _long_search_changes(maps, N_ENVS)
+    env = BatchedPcgrlEnv(prob="sokoban", rep="wide", num_envs=N_ENVS, seed=11)
+    assert env.enable_async(nslots=8)
+    env.reset()
+    env.set_maps(np.stack([m for m, _ in picks]))
+    given = torch.as_tensor(maps[:7]).to(env.device)
+    *_, pending = env.tick(np.array([a for _, a in picks], np.int32), pop_budget=1)       # one pop: every search is suspended
+    before_p, before_c = pending.clone(), env._async["counters"].clone()               # (device copies: nothing is waited for)
+    ev = env.evaluate(given)                                                           # ... with the tick's searches in flight
+    torch.cuda.synchronize()
+    assert before_p.any() and env.async_counters()["suspended"] > 0                    # something IS pending
+    assert np.array_equal(ev.stats.cpu().numpy().astype(np.int64), want[:7])
+    assert torch.equal(env._async["pending"], before_p) and torch.equal(env._async["counters"], before_c)
+    for _ in range(200):                                                               # the suspended steps still complete
+        *_, pending = env.tick(np.array([a for _, a in picks], np.int32), pop_budget=4096)
+        if not pending.any():
+            break
+    assert not pending.any()
+    assert env.check_status() == 0
+    env.close()
+
+
+def test_works_before_reset():
+    _torch()
+    prob, maps, want, _ = _fixture("binary_5x5")
+    env = _make(prob, 5, 5, rep="narrow")
+    ev = env.evaluate(maps)                                       # no reset() so far
+    assert np.array_equal(ev.stats.cpu().numpy().astype(np.int64), want)
+    assert ev.reward is None and ev.over is None
+    with pytest.raises(RuntimeError):
+        env.set_maps(maps[:N_ENVS])
+    env.reset()                                                   # ... and the environment starts as ever
+    env.close()
+
+
+def test_evaluate_levels_convenience():
+    _torch()
+    import gym_pcgrl_amd
+    for name in ("zelda_5x5", "ddave_6x9_p150", "smb_4x9_p200"):
+        prob, maps, want, power = _fixture(name)
+        kw = {} if power is None else dict(solver_power=power)
+        ev = gym_pcgrl_amd.evaluate_levels(prob, maps, **kw)
+        assert np.array_equal(ev.stats.cpu().numpy().astype(np.int64), want), name
+
+
+# ------------------------------------------------------------------ a tile id beyond the last
+@pytest.mark.parametrize("name", ["binary_14x14", "mdungeon_5x5_p5000", "sokoban_5x5"])
+def test_bad_tile_is_clamped_and_reported(name):
+    torch = _torch()
+    prob, maps, _, power = _fixture(name)
+    env = _make(prob, maps.shape[1], maps.shape[2], power)
+    nt = env.get_num_tiles()
+    bad, clamped = maps[:5].copy(), maps[:5].copy()
+    for i in range(5):
+        bad[i, i % maps.shape[1], (2 * i) % maps.shape[2]] = 200
+        clamped[i, i % maps.shape[1], (2 * i) % maps.shape[2]] = nt - 1
+    want = env.evaluate(clamped).rows.clone()
+    assert env.check_status() == 0
+    given = torch.as_tensor(bad).to(env.device)
+    got = env.evaluate(given).rows.clone()
+    assert torch.equal(got, want)
+    with pytest.raises(ValueError):
+        env.check_status()
+    assert np.array_equal(given.cpu().numpy(), bad) and (given == 200).sum().item() == 5     # the caller's tensor still holds 200
+    env.close()
+
+
+# ------------------------------------------------------------------ reward and over, against the oracle's stepping
+# Per problem thirty triples (A0, A, B): A0 = the oracle's reset map for a seed, A = a level of the problem's fixture, B = A with one
+# cell changed by a wide action.  The master seeds were chosen on the CPU oracle so that every problem has a triple with over == 1
+# and one with a non-zero reward (asserted below).
+TRIPLES = {"binary": ("binary_14x14", 2), "zelda": ("zelda_7x11", 0), "sokoban": ("sokoban_5x5", 47)}
+
+
+def _triples(prob):
+    fixture, master = TRIPLES[prob]
+    _, maps, _, power = _fixture(fixture)
+    rs = np.random.RandomState(master)
+    nt = len(ol.TILES[prob])
+    out = []
+    for i in range(30):
+        a = maps[rs.randint(len(maps))]
+        while True:
+            x, y, v = rs.randint(a.shape[1]), rs.randint(a.shape[0]), rs.randint(nt)
+            if a[y, x] != v:
+                break
+        o = ol.OracleEnv(prob, "wide")
+        o.adjust_param(width=a.shape[1], height=a.shape[0])
+        o.seed(9000 + 31 * master + i)
+        a0 = o.reset()["map"].copy()
+        o.set_map(a)
+        obs, reward, _, _ = o.step([x, y, v])
+        b = obs["map"].copy()
+        assert (b != a).sum() == 1
+        obs, _, done, info = o.step([x, y, v])                    # rewrites the cell with its own value
+        assert np.array_equal(obs["map"], b)
+        assert info["changes"] < info["max_changes"] and info["iterations"] < info["max_iterations"]     # `done` is the problem's criterion alone
+        out.append((a0, a, b, reward, done))
+    return out, power
+
+
+@pytest.mark.parametrize("prob", ["binary", "zelda", "sokoban"])
+def test_reward_and_over_vs_oracle_steps(prob):
+    torch = _torch()
+    triples, power = _triples(prob)
+    a0, a, b = (np.stack([t[k] for t in triples]) for k in range(3))
+    reward = np.array([t[3] for t in triples], np.float64)
+    done = np.array([t[4] for t in triples], bool)
+    assert done.any() and (reward != 0).any()                     # (what the master seed was chosen for)
+    env = _make(prob, a.shape[1], a.shape[2], power)
+    got_r = env.evaluate(b, ref=env.evaluate(a).rows).reward
+    got_o = env.evaluate(b, ref=env.evaluate(a0).rows).over
+    assert got_r.dtype == torch.float64 and got_o.dtype == torch.bool
+    assert np.array_equal(got_r.cpu().numpy(), reward), (got_r.cpu().numpy(), reward)
+    assert np.array_equal(got_o.cpu().numpy(), done), (got_o.cpu().numpy(), done)
+    # one row for all: the broadcast form
+    one = env.evaluate(b, ref=env.evaluate(a[:1]).rows[0])
+    assert torch.equal(one.reward, env.evaluate(b, ref=env.evaluate(np.repeat(a[:1], len(b), 0)).rows).reward)
+    assert env.check_status() == 0
+    env.close()
+
+
+@pytest.mark.parametrize("prob", ["binary", "sokoban"])
+def test_own_start_stats_as_ref(prob):
+    """The handle's start-statistics buffer itself as `ref` (its private binary slots are not read)."""
+    torch = _torch()
+    from gym_pcgrl_amd.envs import BatchedPcgrlEnv
+    _, maps, _, _ = _fixture("binary_14x14" if prob == "binary" else "sokoban_5x5")
+    env = BatchedPcgrlEnv(prob=prob, rep="narrow", num_envs=N_ENVS, seed=123)
+    start_maps = env.reset()["map"].clone()
+    # levels that end an episode and levels that do not: the longest and the shortest paths / solutions of the fixture
+    _, _, stats, _ = _fixture("binary_14x14" if prob == "binary" else "sokoban_5x5")
+    order = np.argsort(-stats[:, 1] if prob == "binary" else -stats[:, 5], kind="stable")
+    overs = []
+    for k in range(4):
+        b = maps[[order[k], order[-1 - k]]]
+        own = env.evaluate(b, ref=env._bufs["start_stats"][:2])
+        via = env.evaluate(b, ref=env.evaluate(start_maps[:2]).rows)
+        assert torch.equal(own.over, via.over) and torch.equal(own.reward, via.reward)
+        overs.append(own.over.cpu().numpy())
+    overs = np.concatenate(overs)
+    assert overs.any() and not overs.all(), overs                # both outcomes were compared
+    env.close()
+
+
+# ------------------------------------------------------------------ a search problem on a 64-row lane group
+def test_sokoban_17_rows_vs_oracle():
+    """k_get_stats<sokoban, 64, ...>: a wavefront per map parks the jobs of k_get_stats_search."""
+    _torch()
+    rs = np.random.RandomState(175)
+    h, w = 17, 5
+    maps = rs.choice(5, size=(40, h, w), p=[0.8, 0.12, 0.0, 0.04, 0.04]).astype(np.uint8)
+    for m in maps:                                               # one player each, as many targets as crates: the solver runs
+        ys, xs = np.nonzero(m == 0)
+        k = rs.randint(len(ys))
+        m[ys[k], xs[k]] = 2
+        nc, nt = int((m == 3).sum()), int((m == 4).sum())
+        tile, extra = (4, nc - nt) if nc > nt else (3, nt - nc)
+        ys, xs = np.nonzero(m == 0)
+        pick = rs.permutation(len(ys))[:extra]
+        m[ys[pick], xs[pick]] = tile
+    want = np.stack([ol.get_stats("sokoban", m, solver_power=1500) for m in maps])
+    assert (want[:, 5] > 0).any() or (want[:, 4] < h * w * (h + w)).any()             # searches ran
+    env = _make("sokoban", h, w, 1500)
+    assert _has_fast_form(env, 40)
+    got = env.evaluate(maps).stats.cpu().numpy().astype(np.int64)
+    assert env.check_status() == 0
+    assert np.array_equal(got, want), np.nonzero((got != want).any(1))[0][:5]
+    env.close()
+
+
+# ------------------------------------------------------------------ a parameter change the handle cannot take in place
+def _sok_steps(env, acts):
+    out = []
+    for a in acts:
+        obs, rew, done, info = env.step(a)
+        out.append([obs["map"].clone(), rew.clone(), done.clone(), info.table.clone()])
+    return out
+
+
+@pytest.mark.parametrize("after_reset", [False, True])
+def test_solver_power_raised_between_evaluations(after_reset):
+    """adjust_param(solver_power=more than the handle's search arena was cut for): the next evaluate() scores with the new power, and
+    the next reset() steps like an environment that never evaluated."""
+    torch = _torch()
+    from gym_pcgrl_amd.envs import BatchedPcgrlEnv
+    _, maps, want, power = _fixture("sokoban_5x5")
+    assert power == 5000
+    low = 300
+    acts = np.random.RandomState(8).randint(0, 6, size=(16, N_ENVS)).astype(np.int32)
+    env, twin = (BatchedPcgrlEnv(prob="sokoban", rep="narrow", num_envs=N_ENVS, seed=55) for _ in range(2))
+    for e in (env, twin):
+        e.adjust_param(solver_power=low)
+        if after_reset:
+            e.reset()
+            _sok_steps(e, acts[:4])
+    at_low = env.evaluate(maps).stats.cpu().numpy().astype(np.int64)
+    assert (at_low != want).any()                                # the fixture has searches that 300 pops do not finish
+    for e in (env, twin):
+        e.adjust_param(solver_power=power, rewards={"sol-length": 3})
+    ev = env.evaluate(maps, ref=np.zeros(8, np.int32))
+    got = ev.stats.cpu().numpy().astype(np.int64)
+    assert np.array_equal(got, want), np.nonzero((got != want).any(1))[0][:5]
+    fresh = BatchedPcgrlEnv(prob="sokoban", rep="wide", num_envs=N_ENVS, seed=1)
+    fresh.adjust_param(solver_power=power, rewards={"sol-length": 3})
+    fv = fresh.evaluate(maps, ref=np.zeros(8, np.int32))
+    assert torch.equal(ev.rows, fv.rows) and torch.equal(ev.reward, fv.reward) and torch.equal(ev.over, fv.over)
+    with pytest.raises(RuntimeError):
+        env.step(acts[4])                                        # reset() has to come first, as without evaluate()
+    for e in (env, twin):
+        e.reset()
+    for t, (x, y) in enumerate(zip(_sok_steps(env, acts[4:]), _sok_steps(twin, acts[4:]))):
+        for k, (p, q) in enumerate(zip(x, y)):
+            assert torch.equal(p, q), (t, k)
+    assert env.check_status() == 0
+    for e in (env, twin, fresh):
+        e.close()
