@@ -83,6 +83,7 @@
 #include "kernels_step_solver.h"
 #include "kernels_search_async.h"
 #include "kernels_evaluate.h"
+#include "kernels_solution.h"
 #include "search_big.h"
 #include "kernels_search_big.h"
 #if PCGRL_IN_PART(PART_CORE)
@@ -624,6 +625,7 @@ PCGRL_LOCAL int launch_smb(pcgrl_env* h, int32_t* sync, int list_a, int mode_a, 
 PCGRL_LOCAL int launch_step_solver(pcgrl_env* h, const int32_t* actions, hipStream_t st, const RolloutArgs& R, int epb);
 PCGRL_LOCAL int launch_get_stats(pcgrl_env* h, const uint8_t* maps, int count, int32_t* rows_out, int32_t* head, int32_t* jobs, hipStream_t st);
 PCGRL_LOCAL int launch_get_stats_search(pcgrl_env* h, const uint8_t* maps, int32_t* rows_out, int32_t* head, const int32_t* jobs, SokNode* pools, int blocks, hipStream_t st);
+PCGRL_LOCAL int launch_get_solution(pcgrl_env* h, const uint8_t* maps, int32_t* rows_out, const SolOut& out, int32_t* head, const int32_t* jobs, SokNode* pools, int blocks, hipStream_t st);
 PCGRL_LOCAL int launch_search_async(pcgrl_env* h, int32_t* tickets, int list_a, int mode_a, int list_b, int mode_b, int parity, int rst_list, int clr, int budget, int resume, int small, hipStream_t st);
 // A launch with more than 64 KB of dynamic LDS needs the kernel's cap raised first.  That is a driver call (about a microsecond of
 // host time -- a fifth of what issuing a step costs), so it is made only when this process has not yet raised the cap of this kernel
@@ -1070,6 +1072,19 @@ PCGRL_LOCAL int launch_get_stats_search(pcgrl_env* h, const uint8_t* maps, int32
         case PCGRL_PROB_DDAVE: return launch_get_stats_search_p<PCGRL_PROB_DDAVE>(h, maps, rows_out, head, jobs, pools, blocks, st);
         default: return PCGRL_EINVAL;
     }
+}
+
+// pcgrl_get_solution, second launch (kernels_solution.h): k_get_stats_search's shape with the traced sokoban searches
+PCGRL_LOCAL int launch_get_solution(pcgrl_env* h, const uint8_t* maps, int32_t* rows_out, const SolOut& out, int32_t* head, const int32_t* jobs, SokNode* pools, int blocks, hipStream_t st) {
+    const size_t lds = sok_lds_bytes();
+    { const int rca = lds_cap<k_get_solution<0>>(h->device, lds); if (rca) return rca; }
+    DevBufs Bs;
+    memset(&Bs, 0, sizeof(Bs));
+    Bs.status = h->B.status; Bs.sok_use_lds = h->B.sok_use_lds; Bs.sok_fast_maxc = h->B.sok_fast_maxc;
+    const int pool_stride = (int)(sok_pool_bytes(&h->cfg) / sizeof(SokNode));
+    hipLaunchKernelGGL(k_get_solution<0>, dim3(blocks), dim3(SS_THREADS), lds, st, h->P, Bs, maps, rows_out, out, head, jobs, pools, pool_stride);
+    HIPCHK(hipGetLastError());
+    return PCGRL_OK;
 }
 
 #endif  // PART_STEP_SOLVER
@@ -1743,6 +1758,46 @@ int pcgrl_get_reward(pcgrl_env* h, const int32_t* rows, const int32_t* ref_rows,
     hipLaunchKernelGGL(k_get_reward<0>, dim3(grid), dim3(256), 0, (hipStream_t)stream, h->P, rows, ref_rows, count, reward_out, over_out);
     HIPCHK(hipGetLastError());
     return PCGRL_OK;
+}
+
+// ---- pcgrl_get_solution (kernels_solution.h): the moves behind sokoban's sol-length -----------------------------------------------
+// The workspace, cut from one plan like pcgrl_get_stats': its three regions, and rows for a caller that wants none.
+struct SolPlan { EvalPlan E; Region rows; size_t total; };
+static SolPlan sol_plan(const pcgrl_config* c, int count) {
+    SolPlan S = {};
+    S.E = eval_plan(c, count);
+    Bump b = {S.E.total};
+    S.rows = b.take(align_up((size_t)count * 8 * 4, 256));
+    S.total = b.off;
+    return S;
+}
+size_t pcgrl_get_solution_bytes(const pcgrl_config* c, int32_t count, int32_t max_len) {
+    if (!c || c->prob != PCGRL_SOKOBAN || max_len < 1 || pcgrl_get_stats_bytes(c, count) == 0) return 0;
+    pcgrl_config one = *c;
+    one.num_envs = 1;
+    return sol_plan(&one, count).total;
+}
+int pcgrl_get_solution(pcgrl_env* h, const uint8_t* maps, int32_t count, int32_t max_len, int8_t* moves_out, int32_t* length_out, int8_t* agent_out,
+                       int32_t* rows_out, void* work, size_t work_bytes, void* stream) {
+    if (!h || !h->bound) return PCGRL_ESTATE;
+    if (!maps || !moves_out || !length_out || !work || count < 1 || max_len < 1 || ((uintptr_t)work & 255) != 0) return PCGRL_EINVAL;
+    const size_t need = pcgrl_get_solution_bytes(&h->cfg, count, max_len);
+    if (need == 0 || work_bytes < need) return PCGRL_EINVAL;
+    DeviceGuard guard(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    const SolPlan S = sol_plan(&h->cfg, count);
+    uint8_t* w = (uint8_t*)work;
+    int32_t* head = at<int32_t>(w, S.E.head);
+    int32_t* rows = rows_out ? rows_out : at<int32_t>(w, S.rows);
+    HIPCHK(hipMemsetAsync(head, 0, S.E.head.bytes, st));
+    // what a level keeps when its planner does not run or nobody wins: an all -1 row, length 0, agent -2 (k_get_solution: -1)
+    HIPCHK(hipMemsetAsync(moves_out, 0xFF, (size_t)count * (size_t)max_len, st));
+    HIPCHK(hipMemsetAsync(length_out, 0, (size_t)count * 4, st));
+    if (agent_out) { HIPCHK(hipMemsetAsync(agent_out, 0xFE, (size_t)count, st)); }
+    int rc = launch_get_stats(h, maps, count, rows, head, at<int32_t>(w, S.E.jobs), st);
+    if (rc) return rc;
+    const SolOut out = {moves_out, length_out, agent_out, max_len};
+    return launch_get_solution(h, maps, rows, out, head, at<int32_t>(w, S.E.jobs), at<SokNode>(w, S.E.pools), S.E.blocks, st);
 }
 
 }  // extern "C"

@@ -21,6 +21,8 @@
 #define SOK_POLL_MASK 31           /* an A* agent looks at its stop word every 32 pops (the hooks in kernels_sokoban.h / _mdungeon.h / _ddave.h) */
 
 struct alignas(16) SokFastNode { uint64_t cr; uint32_t ph; uint32_t depth; };   // ph = player | h << 16
+// (a traced search -- SokTrace, sokoban_solver.h -- also keeps how a node was made in the free bits: ph = player | move << 8 | h << 16,
+//  depth = depth | parent's pool index << 16; the root has move 0 and parent 0)
 
 template <int NW>
 struct SokFastLevel {
@@ -315,11 +317,18 @@ PCGRL_D int sok_rs_limit(const SokNoResume&) { return 0x7FFFFFFF; }
 
 // One search.  `table` must be all zeros; `cache`
 // is room for four nodes (LDS on the device).  Same contract as sok_search otherwise.
-template <int NW, class HP, class TP, class Hook, class Kids, class RSP = SokNoResume>
+// A traced search is the one-wavefront loop only, and its entry is sok_search_fast_traced below, which has no `duo` parameter: here
+// TRP = SokTrace does not compile (the deleted overload behind this function), and the two-wavefront branch is compiled out of the
+// instantiation that sok_search_fast_traced makes (TRP = SokTraceNoDuo).
+struct SokTraceNoDuo { int* win; };
+template <> struct SokTr<SokTraceNoDuo> { static constexpr bool on = true; };
+PCGRL_D void sok_tr_win(const SokTraceNoDuo& t, int idx) { *t.win = idx; }
+template <int NW, class HP, class TP, class Hook, class Kids, class RSP = SokNoResume, class TRP = SokNoTrace>
 PCGRL_D bool sok_search_fast(const SokLevel& L, SokFastNode* pool, HP heap, TP table, int table_mask,
                              SokFastNode* cache, const SokNode& root, int k, int power, int& out_h, int& out_depth, int& out_iters,
-                             bool& out_exhausted, Hook hook, Kids kids, SokDuoBox* duo = nullptr, RSP rsp = RSP()) {
+                             bool& out_exhausted, Hook hook, Kids kids, SokDuoBox* duo = nullptr, RSP rsp = RSP(), TRP trp = TRP()) {
     constexpr bool RS = SokRs<RSP>::on;
+    constexpr bool TRC = SokTr<TRP>::on;
     SokResume* const rst = sok_rs_state(rsp);
     const int rs_limit = sok_rs_limit(rsp);
     const bool resumed = RS && rst->iterations > 0;
@@ -347,7 +356,7 @@ PCGRL_D bool sok_search_fast(const SokLevel& L, SokFastNode* pool, HP heap, TP t
     }
     int result_h = root.h, result_depth = 0;
 #if defined(__HIPCC__)
-    if (duo && k >= 0) {
+    if (!TRC && duo && k >= 0) {
         // the search wavefront of a two-wavefront A* search: see SokDuoBox.  (heap[0] = the root's word is in place.)
         uint32_t cur_word = (uint32_t)(2 * root.h + k * root.depth) << 16;     // the root's word: pool index 0
         int hn = 0;                                      // (RS) the heap's entries after the server's removal for the pending pop
@@ -472,11 +481,11 @@ PCGRL_D bool sok_search_fast(const SokLevel& L, SokFastNode* pool, HP heap, TP t
         }
         SKP(1);
         const uint64_t cr = nd.cr;
-        const int node_player = (int)(nd.ph & 0xFFu), node_h = (int)(nd.ph >> 16), node_depth = (int)nd.depth;
+        const int node_player = (int)(nd.ph & 0xFFu), node_h = (int)(nd.ph >> 16), node_depth = TRC ? (int)(nd.depth & 0xFFFFu) : (int)nd.depth;
         uint64_t cb[NW];
         for (int i = 0; i < NW; i++) cb[i] = 0;
         for (int i = 0; i < nc; i++) sokf_flip<NW>(cb, (int)((cr >> (8 * i)) & 0xFF));
-        if (sokf_covers<NW>(cb, F.tmask)) { win = true; result_h = node_h; result_depth = node_depth; break; }   // engine.py:272-280
+        if (sokf_covers<NW>(cb, F.tmask)) { win = true; result_h = node_h; result_depth = node_depth; sok_tr_win(trp, cur); break; }   // engine.py:272-280
         // visited test-and-add on the exact key
         const uint64_t key = (cr << 8) | (uint64_t)node_player;
         uint64_t hs = key * 0x9E3779B97F4A7C15ull;
@@ -503,6 +512,7 @@ PCGRL_D bool sok_search_fast(const SokLevel& L, SokFastNode* pool, HP heap, TP t
             if (!kid[d].ok) continue;
             SokFastNode ch;
             ch.cr = kid[d].cr; ch.ph = (uint32_t)kid[d].np | ((uint32_t)kid[d].h << 16); ch.depth = (uint32_t)(node_depth + 1);
+            if (TRC) { ch.ph |= (uint32_t)d << 8; ch.depth |= (uint32_t)cur << 16; }      // the move that made it, the node it came from
             pool[npool] = ch;
             if (k >= 0) {
                 cache[cache_n++] = ch;
@@ -524,6 +534,29 @@ PCGRL_D bool sok_search_fast(const SokLevel& L, SokFastNode* pool, HP heap, TP t
     out_h = result_h; out_depth = result_depth; out_iters = iterations;
     out_exhausted = !win && !aborted && !suspended && !(k >= 0 ? heapn > 0 : head < npool);
     return win;
+}
+
+// No traced search with a heap server: a call of sok_search_fast with a SokTrace is a compile error ...
+template <int NW, class HP, class TP, class Hook, class Kids, class RSP>
+bool sok_search_fast(const SokLevel&, SokFastNode*, HP, TP, int, SokFastNode*, const SokNode&, int, int, int&, int&, int&, bool&, Hook, Kids, SokDuoBox*, RSP,
+                     SokTrace) = delete;
+// ... and this is the traced compact search: sok_search_fast's one-wavefront loop, same contract, no `duo`.
+template <int NW, class HP, class TP, class Hook, class Kids>
+PCGRL_D bool sok_search_fast_traced(const SokLevel& L, SokFastNode* pool, HP heap, TP table, int table_mask, SokFastNode* cache, const SokNode& root, int k,
+                                    int power, int& out_h, int& out_depth, int& out_iters, bool& out_exhausted, Hook hook, Kids kids, SokTrace tr) {
+    const SokTraceNoDuo t = {tr.win};
+    return sok_search_fast<NW>(L, pool, heap, table, table_mask, cache, root, k, power, out_h, out_depth, out_iters, out_exhausted, hook, kids, nullptr,
+                               SokNoResume(), t);
+}
+
+// sok_walk_back for the pool of a traced compact search
+PCGRL_D void sokf_walk_back(const SokFastNode* pool, int win, int depth, int8_t* out, int max_len) {
+    int idx = win;
+    for (int i = depth - 1; i >= 0; i--) {
+        const uint32_t ph = pool[idx].ph, dp = pool[idx].depth;
+        if (i < max_len) out[i] = (int8_t)((ph >> 8) & 3u);
+        idx = (int)(dp >> 16);
+    }
 }
 
 #if defined(__HIPCC__)

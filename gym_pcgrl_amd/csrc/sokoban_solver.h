@@ -222,10 +222,23 @@ PCGRL_D bool sok_same(const SokLevel& L, const SokNode& a, const SokNode& b) {
 // known (BFS: the next queue entry; A*: the heap top after the repair), which takes the global-memory
 // latency of the pop off the serial chain.
 struct SokNoHook { PCGRL_D bool operator()(int) const { return false; } };
-template <class HP, class TP, class Hook>
+// ---- Traced searches (pcgrl_get_solution, kernels_solution.h): Node.getActions (engine.py:38-44) needs every node's parent and
+// action, which the reward path never looks at.  A search handed `SokTrace{&win}` records in every child it writes to the pool the
+// pool index of the node it was expanded from and the direction d = 0..3 (L, R, U, D: engine.py's `directions`) that made it -- in
+// bits that are free (SokNode: pad = move, pad2 = parent; SokFastNode: sokoban_fast.h) -- and, when it wins, stores the winning
+// node's pool index in *win: the moves are read off the parent chain from there (sok_walk_back).  Nothing else changes: same pops in
+// the same order, same counts, same results.  SokNoTrace (the default) compiles every trace of this away, like SokNoResume.
+struct SokTrace { int* win; };
+struct SokNoTrace {};
+template <class TRP> struct SokTr { static constexpr bool on = false; };
+template <> struct SokTr<SokTrace> { static constexpr bool on = true; };
+PCGRL_D void sok_tr_win(const SokTrace& t, int idx) { *t.win = idx; }
+PCGRL_D void sok_tr_win(const SokNoTrace&, int) {}
+template <class HP, class TP, class Hook, class TRP = SokNoTrace>
 PCGRL_D bool sok_search(const SokLevel& L, SokNode* pool, HP heap, TP table, int table_mask, SokNode& w,
                         const SokNode& root, int k, int power, int& out_h, int& out_depth, int& out_iters,
-                        bool& out_exhausted, Hook hook) {
+                        bool& out_exhausted, Hook hook, TRP trp = TRP()) {
+    constexpr bool TRC = SokTr<TRP>::on;
     int npool = 0, head = 0, heapn = 0, iterations = 0, best = -1, best_h = 0, best_depth = 0;
     SokRaw ahead = sok_load(&root);
     int ahead_idx = 0;
@@ -257,7 +270,7 @@ PCGRL_D bool sok_search(const SokLevel& L, SokNode* pool, HP heap, TP table, int
             if (head < npool) { ahead_idx = head; ahead = sok_load(pool + head); }
         }
         const int node_h = w.h, node_depth = w.depth, node_player = w.player;
-        if (sok_win(L, w.crate)) { win = true; result_h = node_h; result_depth = node_depth; break; }
+        if (sok_win(L, w.crate)) { win = true; result_h = node_h; result_depth = node_depth; sok_tr_win(trp, cur); break; }
         // visited test-and-add (open addressing; slot = node index + 1, low 16 bits; hash tag in the high bits)
         const uint32_t hs = sok_hash(L, w);
         uint32_t slot = hs & (uint32_t)table_mask;
@@ -273,6 +286,7 @@ PCGRL_D bool sok_search(const SokLevel& L, SokNode* pool, HP heap, TP table, int
         table[slot] = tag | (uint32_t)(cur + 1);
         if (best < 0 || node_h < best_h || (node_h == best_h && node_depth < best_depth)) { best = cur; best_h = node_h; best_depth = node_depth; }
         w.depth = (uint16_t)(node_depth + 1);
+        if (TRC) w.pad2 = (uint16_t)cur;       // the children's parent
         for (int d = 0; d < 4; d++) {          // Node.getChildren: L, R, U, D
             // State.update engine.py:298-327 (the popped node is never a win)
             const int np = node_player + L.dirs[d];
@@ -293,6 +307,7 @@ PCGRL_D bool sok_search(const SokLevel& L, SokNode* pool, HP heap, TP table, int
                 if (keep) w.h = (uint16_t)sok_heuristic(L, w.crate);
             }
             if (keep) {
+                if (TRC) w.pad = (uint8_t)d;   // the move that makes it
                 sok_store(pool + npool, sok_load(&w));
                 if (k >= 0) {
                     heap[heapn] = ((uint32_t)(2 * w.h + k * w.depth) << 16) | (uint32_t)npool;
@@ -342,4 +357,15 @@ PCGRL_D void sok_run_game(const SokLevel& L, SokNode* pool, HP heap, TP table, i
     }
     dist_win = win ? 0 : hh;
     sol_len = win ? dd : 0;
+}
+
+// Node.getActions (engine.py:38-44) of a traced search's winning node: move i of the solution (i = depth-1 .. 0, walking the parent
+// chain from `win` to the root) goes to out[i] where i < max_len.  One lane; `pool` is the one the search filled.
+PCGRL_D void sok_walk_back(const SokNode* pool, int win, int depth, int8_t* out, int max_len) {
+    int idx = win;
+    for (int i = depth - 1; i >= 0; i--) {
+        const SokNode* n = pool + idx;
+        if (i < max_len) out[i] = (int8_t)(n->pad & 3);
+        idx = n->pad2;
+    }
 }

@@ -62,6 +62,20 @@ class Evaluation:
         self.rows, self.stats, self.reward, self.over = rows, stats, reward, over
 
 
+class Solutions:
+    """What BatchedPcgrlEnv.solve() returns: `moves` int8 [M, max_len] (0..3 = left, right, up, down; -1 beyond the solution),
+    `length` int32 [M] (the full len(solution), also beyond max_len), `agent` int8 [M] (-2 the planner did not run, -1 no agent won,
+    0..3 = BFS, A*(1), A*(0.5), A*(0)), `rows` / `stats` as in an Evaluation; `truncated` bool [M]: the row holds only a prefix."""
+    __slots__ = ("moves", "length", "agent", "rows", "stats")
+
+    def __init__(self, moves, length, agent, rows, stats):
+        self.moves, self.length, self.agent, self.rows, self.stats = moves, length, agent, rows, stats
+
+    @property
+    def truncated(self):
+        return self.length > self.moves.shape[1]
+
+
 class BatchedPcgrlEnv:
     metadata = {"render.modes": []}
 
@@ -712,6 +726,60 @@ class BatchedPcgrlEnv:
                                                   C.c_void_p(reward.data_ptr()), C.c_void_p(over.data_ptr()), self._stream()), "pcgrl_get_reward")
             over = over.view(torch.bool)
         return Evaluation(rows, self._prob.decode_rows(rows), reward, over)
+
+    # ---- SokobanProblem.get_stats(map)["solution"] on any level (pcgrl_get_solution)
+    def solve(self, maps=None, max_len=None):
+        """The planner's moves for `maps` -- array-like uint8 [M, H, W] as for evaluate(); None: this environment's current levels
+        (after a reset(); the handle's own map buffer is read in place) -- with the parameters in force: what the reference returns
+        as get_stats(map)["solution"].  `max_len`: columns of the move rows, by default min(solver_power, 255).  Returns Solutions
+        (moves, length, agent, rows, stats), all on the device.  A pure function like evaluate(): episodes, random streams and
+        pending asynchronous searches are not touched, a tile id >= get_num_tiles() is clamped on the way and reported by
+        check_status(), nothing is waited for; the workspace is evaluate()'s (the same one-stream rule).  NotImplementedError where
+        the library has no one-call form: there is no scratch-environment route for the moves."""
+        torch = self._torch
+        if self._prob.name != "sokoban":
+            raise NotImplementedError("solve(): only sokoban's get_stats returns its planner's moves (problem %r keeps at most their number)" % (self._prob.name,))
+        if maps is None:
+            if self._handle is None or not self._was_reset or self._needs_reset:
+                raise RuntimeError("solve() without maps reads the environment's current levels: call reset() first")
+        dims = (self._prob._width, self._prob._height)
+        if self._handle is None or (not self._was_reset and (self._realloc or dims != self._alloc_dims)):
+            self._allocate()               # (as in evaluate(): bound, not reset)
+            self._realloc = False
+        if self._realloc:
+            raise NotImplementedError("solve(): an adjust_param() that this handle could not take in place waits for the next reset(); "
+                                      "the handle still plans with the old parameters")
+        w, h = self._alloc_dims
+        if maps is None:
+            m = self._bufs["map"]
+        else:
+            m = maps if torch.is_tensor(maps) else torch.as_tensor(np.asarray(maps))
+            if m.dim() != 3:
+                raise ValueError("solve(): maps must be [M, H, W], got shape %s" % (tuple(m.shape),))
+            if tuple(m.shape[1:]) != (h, w) or m.shape[0] < 1:
+                raise ValueError("solve(): maps of shape %s for an environment of %d rows x %d columns (at least one map)" % (tuple(m.shape), h, w))
+            m = m.to(device=self.device, dtype=torch.uint8).contiguous()
+        M = int(m.shape[0])
+        power = int(self._prob._solver_power)
+        max_len = min(power, 255) if max_len is None else int(max_len)
+        if max_len < 1:
+            raise ValueError("solve(): max_len must be at least 1, got %d" % max_len)
+        cfg = self._config(self._alloc_dims)
+        need = int(self._lib.pcgrl_get_solution_bytes(C.byref(cfg), M, max_len))
+        if not need:
+            raise NotImplementedError("solve(): no one-call form for this configuration (levels of %d x %d = %d bordered cells, solver_power %d): "
+                                      "the traced searches are the ones that run in LDS -- at most 256 bordered cells and solver_power <= 5000"
+                                      % (h + 2, w + 2, (h + 2) * (w + 2), power))
+        moves = torch.empty((M, max_len), dtype=torch.int8, device=self.device)
+        length = torch.empty((M,), dtype=torch.int32, device=self.device)
+        agent = torch.empty((M,), dtype=torch.int8, device=self.device)
+        rows = torch.empty((M, 8), dtype=torch.int32, device=self.device)
+        if self._eval_work is None or self._eval_work.numel() < need:
+            self._eval_work = torch.empty((need,), dtype=torch.uint8, device=self.device)
+        _lib.check(self._lib.pcgrl_get_solution(self._handle, C.c_void_p(m.data_ptr()), M, max_len, C.c_void_p(moves.data_ptr()),
+                                                C.c_void_p(length.data_ptr()), C.c_void_p(agent.data_ptr()), C.c_void_p(rows.data_ptr()),
+                                                C.c_void_p(self._eval_work.data_ptr()), self._eval_work.numel(), self._stream()), "pcgrl_get_solution")
+        return Solutions(moves, length, agent, rows, self._prob.decode_rows(rows))
 
     def _evaluate_by_set_maps(self, m, rows, chunk):
         """evaluate() where pcgrl_get_stats_bytes is 0: a scratch environment of this problem (wide representation, the same

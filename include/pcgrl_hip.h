@@ -17,6 +17,7 @@
  *   pcgrl_set_tile_probs             Problem.adjust_param(probs=...) probs/problem.py:68-72
  *   pcgrl_set_maps                   direct assignment of Representation._map (tests, curriculum loaders)
  *   pcgrl_get_stats / pcgrl_get_reward   Problem.get_stats / get_reward / get_episode_over called on any level, outside an episode
+ *   pcgrl_get_solution               SokobanProblem.get_stats(map)["solution"] sokoban_prob.py:133-145: the planner's moves
  *
  * Conventions: plain pointers and sizes only; every function returns 0 on success or a negative
  * PCGRL_E* code (no exceptions cross the ABI); all device buffers are OWNED BY THE CALLER (hipMalloc,
@@ -44,7 +45,8 @@ extern "C" {
  *     changed), so the number stays; a caller detects the feature by the symbol pcgrl_bind_row.
  *     Still 15: + pcgrl_render_desc / pcgrl_render -- additive in the same way; a caller detects it by the symbol pcgrl_render.
  *     Still 15: + pcgrl_get_stats_bytes / pcgrl_get_stats / pcgrl_get_reward -- additive in the same way (three entry points, no struct);
- *     a caller detects them by the symbol pcgrl_get_stats. */
+ *     a caller detects them by the symbol pcgrl_get_stats.
+ *     Still 15: + pcgrl_get_solution_bytes / pcgrl_get_solution -- additive in the same way; detected by the symbol pcgrl_get_solution. */
 #define PCGRL_ABI_VERSION 15
 #define PCGRL_OK 0
 #define PCGRL_EINVAL (-1)   /* bad argument / unsupported configuration */
@@ -317,6 +319,28 @@ int    pcgrl_get_stats(pcgrl_env* env, const uint8_t* maps, int32_t count, int32
  *   `over` is the problem's own criterion only: max_changes / max_iterations belong to an episode, not to a level. */
 int    pcgrl_get_reward(pcgrl_env* env, const int32_t* rows, const int32_t* ref_rows, int32_t count,
                         double* reward_out, uint8_t* over_out, void* stream);
+/* SokobanProblem.get_stats(map)["solution"] (sokoban_prob.py:133-145): the list of moves that _run_game (:85-122) got from the first
+ * agent whose returned state wins -- Node.getActions (engine.py:38-44) of that agent's winning node -- of which `sol-length` is only
+ * the len().  Same contract as pcgrl_get_stats: a bound handle, no reset needed, no episode state read or written, of the handle only
+ * the sticky status word written (bit 0, bit 2: a bad tile id is clamped in the LDS copy, the caller's map stays), asynchronous.
+ *   maps        DEVICE u8 [count,H,W], read only.
+ *   max_len     columns of a row of moves_out, >= 1.
+ *   moves_out   DEVICE i8 [count,max_len]: move i of the solution as the index into engine.py:3 `directions` -- 0..3 = left, right,
+ *               up, down -- for i < min(length, max_len); -1 from there to the end of the row.
+ *   length_out  DEVICE i32 [count]: the full len(solution), also when it is > max_len (the row then holds the first max_len moves).
+ *               0 with an all -1 row: the planner did not run (sokoban_prob.py:143) or no agent won (:122).
+ *   agent_out   DEVICE i8 [count] or NULL: -2 = the planner did not run, -1 = no agent won, else the agent of _run_game that won:
+ *               0 = BFSAgent (:110), 1..3 = AStarAgent with balance 1, 0.5, 0 (:113-121).
+ *   rows_out    DEVICE i32 [count,8] or NULL: exactly what pcgrl_get_stats writes for these maps.
+ *   work        DEVICE, 256-byte aligned, at least pcgrl_get_solution_bytes(cfg, count, max_len) bytes; the call's own.
+ *   PCGRL_EINVAL: a NULL maps / moves_out / length_out / work, count < 1, max_len < 1, work not 256-byte aligned or too small, or a
+ *   configuration for which pcgrl_get_solution_bytes is 0.
+ * pcgrl_get_solution_bytes: from the configuration alone.  0 wherever pcgrl_get_stats_bytes is 0, for every problem but sokoban (the
+ *   other planners' get_stats keep only the length; binary, zelda and smb have no move list) and for max_len < 1; else >= 256. */
+size_t pcgrl_get_solution_bytes(const pcgrl_config* cfg, int32_t count, int32_t max_len);
+int    pcgrl_get_solution(pcgrl_env* env, const uint8_t* maps, int32_t count, int32_t max_len,
+                          int8_t* moves_out, int32_t* length_out, int8_t* agent_out, int32_t* rows_out,
+                          void* work, size_t work_bytes, void* stream);
 /* ActionMap.step for the wide representation (wrappers.py:139-154): flat DEVICE i32 [N] index into
  * (H, W, tiles) -> xyv DEVICE i32 [N,3] = (x, y, tile), the action pcgrl_step takes. */
 int pcgrl_action_map(pcgrl_env* env, const int32_t* flat, int32_t* xyv, void* stream);
