@@ -237,15 +237,37 @@ __device__ __forceinline__ void stats_wave_task(const PcgrlParams& P, const DevB
         bool full = compute;
         if (kInc && G == 16) {
             const bool t = compute && tch;
+            TouchMemo<MaskT> memo = touch_memo_empty(g, b0);
             if (t) {       // the change is in the champion or next to it: its pieces / its union with the cell, one double sweep
                 const MaskT cbit = (g.lane == wl_inc_row<G>(raw)) ? (MaskT)1 << wl_inc_col<G>(raw) : (MaskT)0;
                 const MaskT champ_old = champ_base[(size_t)e * G + g.lane];
                 const int4 old = *reinterpret_cast<const int4*>(B.stats + (size_t)e * 8);
                 int regions, path, ub2;
-                if (binary_touch(g, (MaskT)(~b0 & rowmask), cbit, (wl_inc_code<G>(raw) & 1u) != 0, old.x, champ_old, old.w - 1, regions, path, champ, ub2)) {
+                if (binary_touch(g, (MaskT)(~b0 & rowmask), cbit, (wl_inc_code<G>(raw) & 1u) != 0, old.x, champ_old, old.w - 1, regions, path, champ, ub2, memo)) {
                     s[0] = regions; s[1] = path; s[2] = 1; s[3] = ub2 + 1;
                     full = false;
                 }
+            }
+#ifdef PCGRL_TIMELINE
+            {   // what the task holds: 32 + groups whose touch gave up + 8 * groups with a plain full item (tools/timeline.py)
+                const uint64_t gu = __ballot(t && full && g.lane == 0), pl = __ballot(compute && !tch && g.lane == 0);
+                TL(32 + __popcll(gu) + 8 * __popcll(pl));
+            }
+#endif
+            // A touch that gave up resumes from what it found instead of starting over (rlp_resume).  The plain items of the wavefront
+            // (no champion, no bound) take the same routine with an empty memo: one extraction phase and one round of sweeps for both.
+            // (k_step only: k_update puts no touch on the lists of k_stats -- every item there is a plain one, for the restart below.
+            //  32-bit row masks only: the tape and row-writing forms of k_step for 64-bit masks are at 128 registers without scratch, and
+            //  what the resume carries through the extraction phase -- champion rows, bound, the early-exit flag -- spilled 8 to 20 bytes
+            //  there; maps of 33 .. 64 columns keep the restart)
+            constexpr bool kResume = FUSED && sizeof(MaskT) == 4;
+            if (kResume && B.touch_resume) {      // (kernel-uniform; pcgrl_tuning touch_resume = 0: the restart below)
+                if (full) {
+                    int regions, path, ub2;
+                    rlp_resume(g, (MaskT)(~b0 & rowmask), memo, regions, path, champ, ub2, (B.step_tight & 1) != 0);
+                    s[0] = regions; s[1] = path; s[2] = g.any(champ) ? 1 : 0; s[3] = ub2 + 1;
+                }
+                full = false;
             }
         }
         if (full) need_solver = compute_item_stats<PROB>(g, P, b0, b1, b2, rowmask, s, champ, (B.step_tight & 1) != 0);      // (also what binary_touch gave up on)

@@ -388,6 +388,7 @@ static void resolve_tuning(pcgrl_env* h) {
     B.step_prio = tun_or(T.step_prio, h->cfg.prob == PCGRL_BINARY ? (h->cfg.rep == PCGRL_NARROW ? (15 | (3 << 6)) : 15) : 0) & 0xFFF;
     B.step_ipw = (i == 1 || i == 2) ? i : 4;
     B.step_touch = tun_or(T.no_touch, 0) ? 0 : 1;
+    B.touch_resume = tun_or(T.touch_resume, 1) ? 1 : 0;
     B.step_pair = tun_or(T.step_pair, 6);        // (C3: fifteen certain resets a block and step; 32.2 -> 29.8 us.  C2 has two or three: unaffected)
     B.step_tight = B.step_touch ? tun_or(T.touch_tight, 1) : 0;
     h->no_inc = tun_or(T.no_inc, 0) != 0;       // every change takes the full statistics (A/B, tests)

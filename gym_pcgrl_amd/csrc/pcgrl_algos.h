@@ -211,7 +211,10 @@ PCGRL_HD int num_stats(int prob) { return prob == PCGRL_PROB_BINARY ? 2 : (prob 
 //   * the first component visited is the one through the fullest row, which is almost always the
 //     giant one, so the four maps that share a wavefront do their long sweeps at the same time;
 //   * BFS levels are kept per lane (iteration of the lane's last change) and reduced once per
-//     sweep, so the sweep loop needs a single wave-uniform exit test and no per-group ballot.
+//     sweep, so the sweep loop needs a single wave-uniform exit test and no per-group ballot;
+//   * an update through the champion that has to give up (binary_touch) hands what it found to the recomputation (rlp_resume): the
+//     components it swept are not extracted or swept again, and with the region count known the extraction of the others stops as
+//     soon as what is left is too small to matter.
 template <class B>
 PCGRL_D typename B::mask_t pcg_expand(B& g, typename B::mask_t f) {
     return f | (f << 1) | (f >> 1) | g.up(f) | g.down(f);
@@ -602,9 +605,28 @@ PCGRL_D void binary_incremental(B& g, typename B::mask_t pass_new, typename B::m
 //     "the others": ub2 grows by their bounds.
 // false (the new value is below the bound, the champion is gone, three pieces that matter): the caller computes from scratch.
 // One double sweep serves both cases, so the lane groups of a wavefront stay in lockstep whatever their changes were.
+// What a touch knows when it gives up, for rlp_resume below: the (up to) two components of the NEW map it swept or measured -- an
+// addition: the merged component; a removal: the two largest pieces of the old champion -- each with its exact double-sweep value
+// (0: none, the sweep was pruned or never made) and the best bound known of it (the value, 2 * e1 of a pruned sweep, or size - 1);
+// the new region count, which is exact whether or not the touch gave up; and the bound of the pieces beyond the second (size - 1 of
+// the third largest, -1: none), kept apart from ub2_old.  An empty memo (valid = false) is "nothing known".
+template <class M>
+struct TouchMemo {
+    M comp1, comp2;
+    int val1, bd1, val2, bd2, bd3, regions, k;
+    bool valid;
+};
+template <class B>
+PCGRL_D TouchMemo<typename B::mask_t> touch_memo_empty(B& g, typename B::mask_t any_mask) {
+    TouchMemo<typename B::mask_t> m;
+    m.comp1 = any_mask ^ any_mask; m.comp2 = m.comp1;
+    m.val1 = 0; m.bd1 = -1; m.val2 = 0; m.bd2 = -1; m.bd3 = -1; m.regions = 0; m.k = 0; m.valid = false;
+    return m;
+}
 template <class B>
 PCGRL_D bool binary_touch(B& g, typename B::mask_t pass_new, typename B::mask_t cbit, bool added, int regions_old,
-                          typename B::mask_t champ_old, int ub2_old, int& regions, int& path, typename B::mask_t& champ, int& ub2) {
+                          typename B::mask_t champ_old, int ub2_old, int& regions, int& path, typename B::mask_t& champ, int& ub2,
+                          TouchMemo<typename B::mask_t>& memo) {
     typedef typename B::mask_t M;
     const M base = pass_new & ~cbit;
     const M dom = added ? (base & ~champ_old) : (champ_old & ~cbit);      // where the fills may go
@@ -626,10 +648,13 @@ PCGRL_D bool binary_touch(B& g, typename B::mask_t pass_new, typename B::mask_t 
     }
     const M target = added ? (champ_old | cbit | uni) : big1;
     // (added: a sweep that cannot reach ub2 may give up -- the answer is then "false" anyway)
-    int e = pcg_double_sweep(g, target, added ? ub2_old - 1 : -1);
+    int bd1 = 0;
+    int e = pcg_double_sweep(g, target, added ? ub2_old - 1 : -1, bd1);
     bool ok = true;
     int ub = ub2_old;
     champ = target;
+    memo.comp1 = target; memo.val1 = e; memo.bd1 = bd1;
+    memo.comp2 = uni ^ uni; memo.val2 = 0; memo.bd2 = -1; memo.bd3 = -1; memo.k = k; memo.valid = true;
     if (added) {
         regions = regions_old - k;
     } else {
@@ -639,17 +664,117 @@ PCGRL_D bool binary_touch(B& g, typename B::mask_t pass_new, typename B::mask_t 
             int bd = size2 - 1, e2 = 0;
             const int thr = e < ub ? e : ub;
             if (bd > thr) e2 = pcg_double_sweep(g, big2, thr, bd);
+            memo.comp2 = big2; memo.val2 = e2; memo.bd2 = bd;
             if (e2 > e) { ub = e > ub ? e : ub; e = e2; champ = big2; }
             else ub = bd > ub ? bd : ub;
         }
         if (size3 > 0) {
+            memo.bd3 = size3 - 1;
             if (size3 - 1 > e) ok = false;
             else ub = size3 - 1 > ub ? size3 - 1 : ub;
         }
+        // (k == 0: the champion was the changed cell alone -- nothing of the new map is known)
+        if (k == 0) { memo.comp1 = uni ^ uni; memo.val1 = 0; memo.bd1 = -1; }
     }
+    memo.regions = regions;
     path = e;
     ub2 = ub;
     return ok && e >= ub2_old;
+}
+template <class B>
+PCGRL_D bool binary_touch(B& g, typename B::mask_t pass_new, typename B::mask_t cbit, bool added, int regions_old,
+                          typename B::mask_t champ_old, int ub2_old, int& regions, int& path, typename B::mask_t& champ, int& ub2) {
+    TouchMemo<typename B::mask_t> memo;
+    return binary_touch(g, pass_new, cbit, added, regions_old, champ_old, ub2_old, regions, path, champ, ub2, memo);
+}
+
+// regions_and_longest_path (the 16-lane form: extraction first, sweeps after) entered with what a given-up touch already knows --
+// the restart without the work the touch has done:
+//   * the memo's components are not extracted again, and one whose sweep was exact is not swept again: its value is the path to
+//     beat from the first moment on.  (A pruned sweep left a bound only: the component enters as "the largest found so far" with
+//     that bound, and is swept again if the bound says it could still matter.)
+//   * the region count is the touch's, so the other components are extracted only while they could still matter: the loop ends as
+//     soon as popcount(rest) - 1 <= path -- a component of the rest has at most that many cells, and a k-cell component holds no
+//     shortest path longer than k - 1.  Seeds come from the fullest row, which finds the large components first.
+// With an empty memo it is the plain computation (no early exit: the regions have to be counted), so the lane groups of a wavefront
+// that hold given-up touches and the ones that hold plain items go through ONE extraction phase and ONE round of sweeps together.
+// path and regions are what regions_and_longest_path returns; the champion and ub2 may differ from its choice (ties in size are
+// broken by discovery order) but keep their meaning: a whole component whose double sweep gave `path`, or empty; a bound on the
+// value of every other component -- exact where swept, 2 * e1 where pruned, size - 1 otherwise, popcount(rest) - 1 for what was
+// never extracted, the closed-form value of the tiny ones -- capped at path.
+template <class B>
+PCGRL_D void rlp_resume(B& g, typename B::mask_t pass, const TouchMemo<typename B::mask_t>& memo, int& regions, int& path,
+                        typename B::mask_t& champ, int& ub2, bool tight = true) {
+    typedef typename B::mask_t M;
+    typedef typename B::ivec_t I;
+    regions = 0;
+    path = 0;
+    champ = pass ^ pass;
+    const M nontiny = pass & ~pcg_tiny_components(g, pass, regions, path);
+    const bool known = memo.valid;
+    int ub = path;                                 // the bound on everything that is not the champion, so far: the tiny components
+    // the memo's components with an exact value are settled here (a tiny one among them changes nothing: its value is in `path` already)
+    if (known && memo.val1 > 0) {
+        if (memo.val1 > path) { path = memo.val1; champ = memo.comp1; }
+    }
+    if (known && memo.val2 > 0) {
+        if (memo.val2 > path) { ub = path > ub ? path : ub; path = memo.val2; champ = memo.comp2; }
+        else ub = memo.val2 > ub ? memo.val2 : ub;
+    } else if (known && memo.bd2 > ub) ub = memo.bd2;      // (not swept or pruned: its bound was at most the first one's value)
+    // a pruned sweep left a bound only: the component enters as the largest found so far, with the size its bound allows (sizes
+    // only rank the components and bound their values by size - 1)
+    const bool pend1 = known && memo.val1 <= 0 && g.any(memo.comp1);
+    M rest = nontiny & ~memo.comp1 & ~memo.comp2;
+    M big1 = pend1 ? memo.comp1 : (pass ^ pass), big2 = pass ^ pass;
+    int size1 = 0, size2 = 0, size3 = 0;
+    const int count = known ? 0 : 1;               // the touch's region count is exact: nothing to count then, and the loop may end early
+    if (known) regions = memo.regions;
+    if (pend1) { size1 = g.popcount_sum(memo.comp1); size1 = memo.bd1 + 1 < size1 ? memo.bd1 + 1 : size1; }
+    if (g.any(rest)) {
+        const PcgFillCtx<B> ctx = pcg_fill_ctx(g, pass);    // components never touch, so the full mask is safe
+        while (g.any(rest)) {
+            if (count == 0) {
+                const int n = g.popcount_sum(rest);
+                if (n - 1 <= path) { ub = n - 1 > ub ? n - 1 : ub; break; }      // (what is never extracted: n - 1 bounds it)
+            }
+            const I cnt = g.popc_lanes(rest);
+            const M comp = pcg_component(g, g.first_bit(g.keep_where_eq(cnt, g.imax(cnt), rest)), ctx);
+            rest = rest & ~comp;
+            regions += count;
+            const int size = g.popcount_sum(comp);
+            if (size > size1) { size3 = size2; size2 = size1; big2 = big1; size1 = size; big1 = comp; }
+            else if (size > size2) { size3 = size2; size2 = size; big2 = comp; }
+            else if (size > size3) size3 = size;
+        }
+    }
+    int b1 = size1 - 1, b2 = size2 - 1;             // what is known of the two largest (-1 once one is the champion)
+    if (b1 > path) {
+        const int e = pcg_double_sweep(g, big1, path, b1);
+        if (e > path) { ub = path > ub ? path : ub; path = e; champ = big1; b1 = -1; }
+    }
+    {
+        int rest_b = size3 - 1 > ub ? size3 - 1 : ub;
+        rest_b = b1 > rest_b ? b1 : rest_b;
+        if (b2 > path) {
+            const int e = pcg_double_sweep(g, big2, path, b2);
+            if (e > path) { ub = path > ub ? path : ub; path = e; champ = big2; b2 = -1; }
+        } else if (tight && b2 > rest_b) pcg_double_sweep(g, big2, rest_b, b2);
+    }
+    if (size3 - 1 > path) {   // rare: a third component is still large enough to matter
+        rest = nontiny & ~champ & ~big1 & ~big2;      // (whatever else is looked at again can only confirm what is known of it)
+        const PcgFillCtx<B> ctx = pcg_fill_ctx(g, pass);
+        while (g.any(rest)) {
+            const M comp = pcg_component(g, g.first_bit(rest), ctx);
+            rest = rest & ~comp;
+            if (g.popcount_sum(comp) - 1 > path) {
+                const int e = pcg_double_sweep(g, comp, path);
+                if (e > path) { ub = path > ub ? path : ub; path = e; champ = comp; }
+            }
+        }
+    }
+    // every component but the champion: what was settled above, the two largest by what is known of them, the rest by their size
+    ub = b1 > ub ? b1 : ub; ub = b2 > ub ? b2 : ub; ub = size3 - 1 > ub ? size3 - 1 : ub;
+    ub2 = ub > path ? path : ub;                     // (no component has a value above the maximum)
 }
 
 // ---------------------------------------------------------------- one map, several cooperating lane groups

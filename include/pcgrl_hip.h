@@ -158,6 +158,9 @@ typedef struct pcgrl_tuning {
     int32_t obs_at_end;      /* k_step with a bound observation (pcgrl_bind_observation): 1 = every image at the end of the launch (the form up to
                                 round 5); default 0 = the images leave while the step runs -- a reset's wavefront writes its new map's, a wide
                                 change's lane its piece, "observation tasks" between the statistics tasks the rest (csrc/kernels_step.h) */
+    int32_t touch_resume;    /* k_step, binary, maps of at most 16 x 32: 0 = a change to the champion that binary_touch gives up on is computed
+                                from scratch; default 1 = the computation resumes from what the touch found (csrc/pcgrl_algos.h rlp_resume).
+                                Wider maps (64-bit row masks) and the two-launch pipeline, which has no touch, always compute from scratch */
 } pcgrl_tuning;
 
 int pcgrl_abi_version(void);

@@ -42,7 +42,10 @@ SLOTS, WAVES = 48, EPB // 16
 nblk = (n + EPB - 1) // EPB
 names = {1: "start", 2: "update done", 3: "lists ready", 4: "task: certain reset", 5: "task: full", 6: "task: incremental", 7: "task end", 8: "wave end",
          9: "reset done", 10: "stats done", 11: "finalized", 12: "late reset", 13: "ring staged", 14: "map made", 15: "cursor drawn", 16: "reset stored", 17: "state staged", 18: "ticket"}
-summ = []
+for _g in range(5):
+    for _p in range(5):
+        names[32 + _g + 8 * _p] = "holds %dg%dp" % (_g, _p)      # full task: touches that gave up / plain full items among its maps
+summ, all_comp = [], []
 for rep_i in range(5):
     buf = torch.zeros((nblk * WAVES * SLOTS,), dtype=torch.int64, device=env.device)
     _lib.check(L.pcgrl_debug_timeline(C.c_void_p(buf.data_ptr())), "timeline")
@@ -102,6 +105,30 @@ for rep_i in range(5):
     print("certain reset chain (us from task start, p50 / p90 / max):", "  ".join(
         "%s %.1f/%.1f/%.1f" % (names[k], np.percentile(v, 50), np.percentile(v, 90), np.max(v)) for k, v in chain.items() if v))
     print("full task chain:", "  ".join("%s %.1f/%.1f/%.1f" % (names[k], np.percentile(v, 50), np.percentile(v, 90), np.max(v)) for k, v in fullc.items() if v))
+    # binary: what the full tasks hold (the mark 32 + give-ups + 8 * plain items of stats_wave_task) against how long they last
+    comp = []                # (duration, touches that gave up, plain full items)
+    for b, w in zip(*np.nonzero((tag == 5).any(axis=2))):
+        tg, tt = tag[b, w], tm[b, w]
+        for i in np.nonzero(tg == 5)[0]:
+            j, mk = i + 1, -1
+            while j < SLOTS and tg[j] not in (7, 0):
+                if 32 <= tg[j] < 72:
+                    mk = int(tg[j]) - 32
+                j += 1
+            if j < SLOTS and tg[j] == 7 and mk >= 0:
+                comp.append((tt[j] - tt[i], mk & 7, mk >> 3))
+    if comp:
+        c = np.array(comp)
+        d, gu, pl = c[:, 0], c[:, 1], c[:, 2]
+        all_comp.append(c)
+        p90, p99 = np.percentile(d, 90), np.percentile(d, 99)
+        print("full tasks: n %d, with a give-up %.1f %%, with a plain item %.1f %%" % (len(d), 100 * (gu > 0).mean(), 100 * (pl > 0).mean()))
+        for nm, sel in (("all", d >= 0), ("> p90 (%.1f us)" % p90, d > p90), ("> p99 (%.1f us)" % p99, d > p99)):
+            print("   %-18s n %5d  give-up %5.1f %%  plain %5.1f %%  neither %5.1f %%" % (nm, sel.sum(), 100 * (gu[sel] > 0).mean(), 100 * (pl[sel] > 0).mean(),
+                                                                                         100 * ((gu[sel] == 0) & (pl[sel] == 0)).mean()))
+        for nm, sel in (("touches only", (gu == 0) & (pl == 0)), ("with a give-up", gu > 0), ("with a plain item", pl > 0)):
+            if sel.any():
+                print("   %-18s n %5d  %s" % (nm, sel.sum(), pct(d[sel])))
     # the slowest blocks: their marks
     worst = np.argsort(end_b)[-3:]
     for b in worst:
@@ -110,4 +137,16 @@ for rep_i in range(5):
             seq = ["%s@%.1f" % (names[int(g)].split(":")[-1].strip(), t) for g, t in zip(tag[b, w], tm[b, w]) if g]
             print("   wave", w, " ".join(seq))
     summ.append(float(end_b.max()))
+if all_comp:
+    c = np.concatenate(all_comp)
+    d, gu, pl = c[:, 0], c[:, 1], c[:, 2]
+    print("== full tasks of all %d steps: n %d" % (len(all_comp), len(d)))
+    for q in (90, 99, 99.9):
+        sel = d > np.percentile(d, q)
+        print("   above p%-5s (%.1f us) n %5d  give-up %5.1f %%  plain %5.1f %%  neither %5.1f %%" % (q, np.percentile(d, q), sel.sum(), 100 * (gu[sel] > 0).mean(),
+                                                                                                       100 * (pl[sel] > 0).mean(), 100 * ((gu[sel] == 0) & (pl[sel] == 0)).mean()))
+    for nm, sel in (("touches only", (gu == 0) & (pl == 0)), ("with a give-up", gu > 0), ("with a plain item", pl > 0)):
+        if sel.any():
+            x = d[sel]
+            print("   %-18s n %5d  p50 %.1f  p90 %.1f  p99 %.1f  max %.1f" % (nm, sel.sum(), np.percentile(x, 50), np.percentile(x, 90), np.percentile(x, 99), x.max()))
 print("kernel span (first start -> last end), us:", [round(x, 1) for x in summ])
