@@ -32,6 +32,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <type_traits>
 #include <vector>
 
 #include "../../include/pcgrl_hip.h"
@@ -371,7 +372,7 @@ static void resolve_tuning(pcgrl_env* h) {
     // (C4: 1 300 fresh jobs of ~30 pops a tick, 240 -> 275 M env-steps/s); MiniDungeons / Dave have under a hundred and the extra
     // launch -- whose length is one job's chain of pops, like the other's -- costs more than it saves (M1 277 -> 207 M)
     h->async_split = tun_or(T.async_split, h->cfg.prob == PCGRL_SOKOBAN ? 1 : 0) ? 1 : 0;
-    // k_step: environments per block (see launch_step_pm).  The largest block that still gives (about) every compute unit one and
+    // k_step: environments per block (see launch_step_p).  The largest block that still gives (about) every compute unit one and
     // is resident in one round: 256 environments -> one block per CU (LDS), 128 -> two, 64 -> four.
     const int n_ = h->cfg.num_envs;
     h->step_epb = T.step_epb > 0 ? T.step_epb : ((n_ >= 192 * 256 && n_ <= 256 * 256) ? 256 : (n_ >= 192 * 128 ? 128 : 64));
@@ -642,10 +643,41 @@ static int lds_cap(int device, size_t lds) {
     }
     return PCGRL_OK;
 }
+// One launch: the cap, the kernel, the check.  launch_fn: a kernel chosen through a function pointer (its cap was raised at pcgrl_bind).
+template <class... Params, class... Args>
+static int launch_fn(void (*kfn)(Params...), int grid, int block, size_t lds, hipStream_t st, const Args&... args) {
+    hipLaunchKernelGGL(kfn, dim3(grid), dim3(block), lds, st, args...);
+    HIPCHK(hipGetLastError());
+    return PCGRL_OK;
+}
+template <auto KFN, class... Args>
+static int launch(pcgrl_env* h, int grid, int block, size_t lds, hipStream_t st, const Args&... args) {
+    { const int rc = lds_cap<KFN>(h->device, lds); if (rc) return rc; }
+    return launch_fn(KFN, grid, block, lds, st, args...);
+}
 static int grid_for(int items, int per_block, int cap) {
     int g = (items + per_block - 1) / per_block;
     if (g < 1) g = 1;
     return g < cap ? g : cap;
+}
+// Tag dispatch: a run-time fact of the handle becomes a compile-time tag -- Int<V> for a value, Type<T> for a mask type -- that a
+// generic lambda is called with.  with_prob / with_rep name the set their site instantiates; a value outside it: PCGRL_EINVAL.
+template <int V> using Int = std::integral_constant<int, V>;
+template <class T> struct Type { using type = T; };
+template <class Tag> using type_of = typename Tag::type;
+template <int... VS, class F>
+static int with_value(int v, F&& f) {
+    int rc = PCGRL_EINVAL;
+    (void)(... || (v == VS ? (rc = f(Int<VS>{}), true) : false));     // (a left fold: the kernels are instantiated, and emitted, in the list's order)
+    return rc;
+}
+template <int... PROBS, class F> static int with_prob(int prob, F&& f) { return with_value<PROBS...>(prob, f); }
+template <int... REPS, class F> static int with_rep(int rep, F&& f) { return with_value<REPS...>(rep, f); }
+template <class F> static int with_mask(int mask_bytes, F&& f) { return mask_bytes == 4 ? f(Type<uint32_t>{}) : f(Type<uint64_t>{}); }
+template <class F>
+static int with_lanes(int group, int mask_bytes, F&& f) {       // (GROUP, MaskT): the lanes that share a map x the width of a row mask
+    if (group == 16) return with_mask(mask_bytes, [&](auto m) { return f(Int<16>{}, m); });
+    return with_mask(mask_bytes, [&](auto m) { return f(Int<64>{}, m); });
 }
 
 #if PCGRL_IN_PART(PART_STATS)
@@ -676,23 +708,17 @@ static int launch_stats_p(pcgrl_env* h, int list, int parity, int mode, int clr,
         // is latency-bound and more wavefronts per map pay (PCGRL_WIDE_WAVES overrides for experiments)
         // (a step of a single-cell representation: k_update ranked the list in two classes, the second goes two items to a block)
         const int pair_few = (mode == MODE_STEP && list == WL_CHG && P.rep <= PCGRL_REP_TURTLE && h->wide_pairs) ? 1 : 0;
-#define LAUNCH_WIDE(NW) do { if (P.mask_bytes == 4) hipLaunchKernelGGL((k_stats_wide<uint32_t, NW>), dim3(gridw), dim3(NW * 64), lds1, st, P, h->B, list, parity, mode, clr, inline_reset, gen, pair_few); \
-                             else hipLaunchKernelGGL((k_stats_wide<uint64_t, NW>), dim3(gridw), dim3(NW * 64), lds1, st, P, h->B, list, parity, mode, clr, inline_reset, gen, pair_few); } while (0)
-        if (nw == 8) LAUNCH_WIDE(8); else LAUNCH_WIDE(4);
-#undef LAUNCH_WIDE
-        HIPCHK(hipGetLastError());
-        return PCGRL_OK;
+        const auto wide = [&](auto waves) {
+            constexpr int NW = waves();
+            return with_mask(P.mask_bytes, [&](auto m) {
+                return launch<k_stats_wide<type_of<decltype(m)>, NW>>(h, gridw, NW * 64, lds1, st, P, h->B, list, parity, mode, clr, inline_reset, gen, pair_few);
+            });
+        };
+        return nw == 8 ? wide(Int<8>{}) : wide(Int<4>{});
     }
-    if (P.group == 16 && P.mask_bytes == 4)
-        hipLaunchKernelGGL((k_stats<PROB, 16, uint32_t>), dim3(grid), dim3(PCGRL_BLOCK), lds, st, P, h->B, list, parity, mode, clr, inline_reset, gen, lone0);
-    else if (P.group == 16)
-        hipLaunchKernelGGL((k_stats<PROB, 16, uint64_t>), dim3(grid), dim3(PCGRL_BLOCK), lds, st, P, h->B, list, parity, mode, clr, inline_reset, gen, lone0);
-    else if (P.mask_bytes == 4)
-        hipLaunchKernelGGL((k_stats<PROB, 64, uint32_t>), dim3(grid), dim3(PCGRL_BLOCK), lds, st, P, h->B, list, parity, mode, clr, inline_reset, gen, lone0);
-    else
-        hipLaunchKernelGGL((k_stats<PROB, 64, uint64_t>), dim3(grid), dim3(PCGRL_BLOCK), lds, st, P, h->B, list, parity, mode, clr, inline_reset, gen, lone0);
-    HIPCHK(hipGetLastError());
-    return PCGRL_OK;
+    return with_lanes(P.group, P.mask_bytes, [&](auto g, auto m) {
+        return launch<k_stats<PROB, g(), type_of<decltype(m)>>>(h, grid, PCGRL_BLOCK, lds, st, P, h->B, list, parity, mode, clr, inline_reset, gen, lone0);
+    });
 }
 // Maps beyond 64 x 64 (bigmap.h, kernels_big.h): a wavefront per item, as many wavefronts per block as the LDS holds
 template <int PROB>
@@ -706,90 +732,52 @@ static int launch_big_p(pcgrl_env* h, int list, int parity, int mode, int clr, i
     nw = nw > nw_max ? nw_max : nw;
     if (nw < 1) return PCGRL_EINVAL;
     const size_t lds = (size_t)nw * per_wave;
-    { const int rc = lds_cap<k_big<PROB>>(h->device, lds); if (rc) return rc; }
-    const int grid = grid_for(P.num_envs, nw, 2048);
-    hipLaunchKernelGGL((k_big<PROB>), dim3(grid), dim3(nw * 64), lds, st, P, h->B, list, parity, mode, clr, inline_reset, gen_flag(h), park_list);
-    HIPCHK(hipGetLastError());
-    return PCGRL_OK;
+    return launch<k_big<PROB>>(h, grid_for(P.num_envs, nw, 2048), nw * 64, lds, st, P, h->B, list, parity, mode, clr, inline_reset, gen_flag(h), park_list);
 }
+// (every problem with bit planes or a general map but smb, which has no statistics pass and whose maps are never `big`)
 static int launch_big(pcgrl_env* h, int list, int parity, int mode, int clr, int inline_reset, int park_list, hipStream_t st) {
-    switch (h->P.prob) {
-        case PCGRL_PROB_BINARY: return launch_big_p<PCGRL_PROB_BINARY>(h, list, parity, mode, clr, inline_reset, park_list, st);
-        case PCGRL_PROB_ZELDA: return launch_big_p<PCGRL_PROB_ZELDA>(h, list, parity, mode, clr, inline_reset, park_list, st);
-        case PCGRL_PROB_MDUNGEON: return launch_big_p<PCGRL_PROB_MDUNGEON>(h, list, parity, mode, clr, 0, park_list, st);
-        case PCGRL_PROB_DDAVE: return launch_big_p<PCGRL_PROB_DDAVE>(h, list, parity, mode, clr, 0, park_list, st);
-        default: return launch_big_p<PCGRL_PROB_SOKOBAN>(h, list, parity, mode, clr, 0, park_list, st);
-    }
+    return with_prob<PCGRL_PROB_BINARY, PCGRL_PROB_ZELDA, PCGRL_PROB_MDUNGEON, PCGRL_PROB_DDAVE, PCGRL_PROB_SOKOBAN>(h->P.prob, [&](auto prob) {
+        return launch_big_p<prob()>(h, list, parity, mode, clr, inline_reset, park_list, st);
+    });
 }
 PCGRL_LOCAL int launch_stats(pcgrl_env* h, int list, int parity, int mode, int clr, int inline_reset, hipStream_t st) {
+    // the search problems' episodes are reset by a launch of their own (k_reset parks the new maps' solver jobs), never inside this one
+    if (solver_prob(h->P.prob)) inline_reset = 0;
     if (h->P.big) return launch_big(h, list, parity, mode, clr, inline_reset, -1, st);
-    switch (h->P.prob) {
-        case PCGRL_PROB_BINARY: return launch_stats_p<PCGRL_PROB_BINARY>(h, list, parity, mode, clr, inline_reset, st);
-        case PCGRL_PROB_ZELDA: return launch_stats_p<PCGRL_PROB_ZELDA>(h, list, parity, mode, clr, inline_reset, st);
-        case PCGRL_PROB_MDUNGEON: return launch_stats_p<PCGRL_PROB_MDUNGEON>(h, list, parity, mode, clr, 0, st);
-        case PCGRL_PROB_DDAVE: return launch_stats_p<PCGRL_PROB_DDAVE>(h, list, parity, mode, clr, 0, st);
-        default: return launch_stats_p<PCGRL_PROB_SOKOBAN>(h, list, parity, mode, clr, 0, st);
-    }
+    return with_prob<PCGRL_PROB_BINARY, PCGRL_PROB_ZELDA, PCGRL_PROB_MDUNGEON, PCGRL_PROB_DDAVE, PCGRL_PROB_SOKOBAN>(h->P.prob, [&](auto prob) {
+        return launch_stats_p<prob()>(h, list, parity, mode, clr, inline_reset, st);
+    });
 }
 
 #endif  // PART_STATS (continued below: launch_reset, launch_planes_from_map)
 
 #if PCGRL_IN_PART(PART_UPDATE)
-template <class MaskT>
-static int launch_update_m(pcgrl_env* h, const int32_t* actions, int parity, hipStream_t st) {
+PCGRL_LOCAL int launch_update(pcgrl_env* h, const int32_t* actions, int parity, hipStream_t st) {
     const PcgrlParams& P = h->P;
     // (a tick of pcgrl_step_async: the kernel's threads also look through the slots of the suspended searches, one each)
     const int nthreads = P.num_envs > h->B.async_nslots ? P.num_envs : h->B.async_nslots;
     const int grid = (nthreads + PCGRL_BLOCK - 1) / PCGRL_BLOCK;
-    switch (P.rep) {
-        case PCGRL_REP_NARROW:
-            hipLaunchKernelGGL((k_update<PCGRL_REP_NARROW, MaskT>), dim3(grid), dim3(PCGRL_BLOCK), 0, st, P, h->B, actions, parity); break;
-        case PCGRL_REP_WIDE:
-            hipLaunchKernelGGL((k_update<PCGRL_REP_WIDE, MaskT>), dim3(grid), dim3(PCGRL_BLOCK), 0, st, P, h->B, actions, parity); break;
-        case PCGRL_REP_TURTLE:
-            hipLaunchKernelGGL((k_update<PCGRL_REP_TURTLE, MaskT>), dim3(grid), dim3(PCGRL_BLOCK), 0, st, P, h->B, actions, parity); break;
-        case PCGRL_REP_NARROW_CAST:
-            hipLaunchKernelGGL((k_update_block<PCGRL_REP_NARROW_CAST, MaskT>), dim3(grid), dim3(PCGRL_BLOCK), 0, st, P, h->B, actions, parity); break;
-        case PCGRL_REP_NARROW_MULTI:
-            hipLaunchKernelGGL((k_update_block<PCGRL_REP_NARROW_MULTI, MaskT>), dim3(grid), dim3(PCGRL_BLOCK), 0, st, P, h->B, actions, parity); break;
-        default:
-            hipLaunchKernelGGL((k_update_block<PCGRL_REP_TURTLE_CAST, MaskT>), dim3(grid), dim3(PCGRL_BLOCK), 0, st, P, h->B, actions, parity); break;
-    }
-    HIPCHK(hipGetLastError());
-    return PCGRL_OK;
-}
-
-PCGRL_LOCAL int launch_update(pcgrl_env* h, const int32_t* actions, int parity, hipStream_t st) {
-    return h->P.mask_bytes == 4 ? launch_update_m<uint32_t>(h, actions, parity, st) : launch_update_m<uint64_t>(h, actions, parity, st);
+    return with_mask(P.mask_bytes, [&](auto m) {
+        using MaskT = type_of<decltype(m)>;
+        return with_rep<PCGRL_REP_NARROW, PCGRL_REP_WIDE, PCGRL_REP_TURTLE, PCGRL_REP_NARROW_CAST, PCGRL_REP_NARROW_MULTI, PCGRL_REP_TURTLE_CAST>(P.rep, [&](auto rep) {
+            if constexpr (rep() <= PCGRL_REP_TURTLE) return launch<k_update<rep(), MaskT>>(h, grid, PCGRL_BLOCK, 0, st, P, h->B, actions, parity);
+            else return launch<k_update_block<rep(), MaskT>>(h, grid, PCGRL_BLOCK, 0, st, P, h->B, actions, parity);     // (an action changes a block of cells)
+        });
+    });
 }
 // pcgrl_get_stats, first launch (kernels_evaluate.h): a lane group per map, grid-stride over `count`
-template <int PROB>
-static int launch_get_stats_p(pcgrl_env* h, const uint8_t* maps, int count, int32_t* rows_out, int32_t* head, int32_t* jobs, hipStream_t st) {
+PCGRL_LOCAL int launch_get_stats(pcgrl_env* h, const uint8_t* maps, int count, int32_t* rows_out, int32_t* head, int32_t* jobs, hipStream_t st) {
     const PcgrlParams& P = h->P;
     const int per_block = (PCGRL_BLOCK / 64) * (64 / P.group);            // maps a block takes per round
     const long long blocks = ((long long)count + per_block - 1) / per_block;
     const int grid = (int)(blocks < 8192 ? blocks : 8192);
     const size_t lds = (size_t)per_block * reset_tile_bytes(P.width * P.height);
-    if (P.group == 16 && P.mask_bytes == 4)
-        hipLaunchKernelGGL((k_get_stats<PROB, 16, uint32_t>), dim3(grid), dim3(PCGRL_BLOCK), lds, st, P, maps, count, rows_out, h->B.status, head, jobs);
-    else if (P.group == 16)
-        hipLaunchKernelGGL((k_get_stats<PROB, 16, uint64_t>), dim3(grid), dim3(PCGRL_BLOCK), lds, st, P, maps, count, rows_out, h->B.status, head, jobs);
-    else if (P.mask_bytes == 4)
-        hipLaunchKernelGGL((k_get_stats<PROB, 64, uint32_t>), dim3(grid), dim3(PCGRL_BLOCK), lds, st, P, maps, count, rows_out, h->B.status, head, jobs);
-    else
-        hipLaunchKernelGGL((k_get_stats<PROB, 64, uint64_t>), dim3(grid), dim3(PCGRL_BLOCK), lds, st, P, maps, count, rows_out, h->B.status, head, jobs);
-    HIPCHK(hipGetLastError());
-    return PCGRL_OK;
-}
-PCGRL_LOCAL int launch_get_stats(pcgrl_env* h, const uint8_t* maps, int count, int32_t* rows_out, int32_t* head, int32_t* jobs, hipStream_t st) {
-    switch (h->P.prob) {
-        case PCGRL_PROB_BINARY: return launch_get_stats_p<PCGRL_PROB_BINARY>(h, maps, count, rows_out, head, jobs, st);
-        case PCGRL_PROB_ZELDA: return launch_get_stats_p<PCGRL_PROB_ZELDA>(h, maps, count, rows_out, head, jobs, st);
-        case PCGRL_PROB_MDUNGEON: return launch_get_stats_p<PCGRL_PROB_MDUNGEON>(h, maps, count, rows_out, head, jobs, st);
-        case PCGRL_PROB_DDAVE: return launch_get_stats_p<PCGRL_PROB_DDAVE>(h, maps, count, rows_out, head, jobs, st);
-        case PCGRL_PROB_SOKOBAN: return launch_get_stats_p<PCGRL_PROB_SOKOBAN>(h, maps, count, rows_out, head, jobs, st);
-        default: return PCGRL_EINVAL;
-    }
+    return with_prob<PCGRL_PROB_BINARY, PCGRL_PROB_ZELDA, PCGRL_PROB_MDUNGEON, PCGRL_PROB_DDAVE, PCGRL_PROB_SOKOBAN>(P.prob, [&](auto prob) {
+        constexpr int PROB = prob();
+        return with_lanes(P.group, P.mask_bytes, [&](auto g, auto m) {
+            return launch<k_get_stats<PROB, g(), type_of<decltype(m)>>>(h, grid, PCGRL_BLOCK, lds, st, P, maps, count, rows_out, h->B.status, head, jobs);
+        });
+    });
 }
 #endif  // PART_UPDATE
 
@@ -815,47 +803,46 @@ static int launch_step_pme(pcgrl_env* h, const int32_t* actions, int parity, hip
                                        P.rep == PCGRL_REP_NARROW, P.rep == PCGRL_REP_WIDE ? 3 : 1, EPB);
     const size_t lds = (size_t)SL.total + (EPB / 16) * (size_t)reset_stage_bytes(P.width * P.height);
     const int grid = (P.num_envs + EPB - 1) / EPB;
-#define PCGRL_LAUNCH_STEP(REPV, MULTI, OBSV, ROWV) do { \
-        { const int rca = lds_cap<k_step<PROB, REPV, MaskT, MULTI, EPB, OBSV, ROWV>>(h->device, lds); if (rca) return rca; } \
-        hipLaunchKernelGGL((k_step<PROB, REPV, MaskT, MULTI, EPB, OBSV, ROWV>), dim3(grid), dim3(EPB * 4), lds, st, P, h->B, actions, \
-                           parity, gen_flag(h), R.steps, R.action_stride, R.reward_out, R.done_out, R.info_out); } while (0)
     const bool multi = R.steps > 1 || R.reward_out || R.done_out || R.info_out;
     // a single step with a bound observation of a lean shape: the instantiation that writes the images while it runs (32-bit row masks)
-    constexpr bool kObsKernel = sizeof(MaskT) == 4;
-    const bool obs = kObsKernel && !multi && h->B.obs.out && h->B.obs.fused && !h->obs_at_end;
+    constexpr std::bool_constant<sizeof(MaskT) == 4> obs_kernel{};
+    const bool obs = obs_kernel() && !multi && h->B.obs.out && h->B.obs.fused && !h->obs_at_end;
     // a step that fills a rollout row (pcgrl_bind_row; never the tape form): the row-writing instantiation
     const bool row = h->row_live != 0;
-#define PCGRL_LAUNCH_STEP3(REPV) do { if (multi) PCGRL_LAUNCH_STEP(REPV, true, false, false); \
-                                      else if (obs && row) PCGRL_LAUNCH_STEP(REPV, false, kObsKernel, true); \
-                                      else if (obs) PCGRL_LAUNCH_STEP(REPV, false, kObsKernel, false); \
-                                      else if (row) PCGRL_LAUNCH_STEP(REPV, false, false, true); \
-                                      else PCGRL_LAUNCH_STEP(REPV, false, false, false); } while (0)
-    switch (P.rep) {
-        case PCGRL_REP_NARROW: PCGRL_LAUNCH_STEP3(PCGRL_REP_NARROW); break;
-        case PCGRL_REP_WIDE: PCGRL_LAUNCH_STEP3(PCGRL_REP_WIDE); break;
-        default: PCGRL_LAUNCH_STEP3(PCGRL_REP_TURTLE); break;
-    }
-#undef PCGRL_LAUNCH_STEP3
-#undef PCGRL_LAUNCH_STEP
-    HIPCHK(hipGetLastError());
-    return PCGRL_OK;
+    return with_rep<PCGRL_REP_NARROW, PCGRL_REP_WIDE, PCGRL_REP_TURTLE>(P.rep, [&](auto rep) {
+        constexpr int REP = rep();
+        const auto go = [&](auto multi_t, auto obs_t, auto row_t) {
+            return launch<k_step<PROB, REP, MaskT, multi_t(), EPB, obs_t(), row_t()>>(h, grid, EPB * 4, lds, st, P, h->B, actions, parity, gen_flag(h), R.steps,
+                                                                                    R.action_stride, R.reward_out, R.done_out, R.info_out);
+        };
+        constexpr std::true_type yes{};
+        constexpr std::false_type no{};
+        if (multi) return go(yes, no, no);
+        if (obs && row) return go(no, obs_kernel, yes);
+        if (obs) return go(no, obs_kernel, no);
+        if (row) return go(no, no, yes);
+        return go(no, no, no);
+    });
 }
-template <int PROB, class MaskT>
-static int launch_step_pm(pcgrl_env* h, const int32_t* actions, int parity, hipStream_t st, const RolloutArgs& R) {
-    // (the 128-environment form is built for 32-bit row masks only: the common case)
-    if (sizeof(MaskT) == 4 && h->step_epb == 128) return launch_step_pme<PROB, uint32_t, 128>(h, actions, parity, st, R);
-    if (sizeof(MaskT) == 4 && h->step_epb == 256) return launch_step_pme<PROB, uint32_t, 256>(h, actions, parity, st, R);
-    return launch_step_pme<PROB, MaskT, 64>(h, actions, parity, st, R);
+template <int PROB>
+static int launch_step_p(pcgrl_env* h, const int32_t* actions, int parity, hipStream_t st, const RolloutArgs& R) {
+    return with_mask(h->P.mask_bytes, [&](auto m) {
+        using MaskT = type_of<decltype(m)>;
+        // (the 128- and 256-environment forms are built for 32-bit row masks only: the common case)
+        if (sizeof(MaskT) == 4 && h->step_epb == 128) return launch_step_pme<PROB, uint32_t, 128>(h, actions, parity, st, R);
+        if (sizeof(MaskT) == 4 && h->step_epb == 256) return launch_step_pme<PROB, uint32_t, 256>(h, actions, parity, st, R);
+        return launch_step_pme<PROB, MaskT, 64>(h, actions, parity, st, R);
+    });
 }
 #endif
 #if PCGRL_IN_PART(PART_STEP_BINARY)
 PCGRL_LOCAL int launch_step_binary(pcgrl_env* h, const int32_t* actions, int parity, hipStream_t st, const RolloutArgs& R) {
-    return h->P.mask_bytes == 4 ? launch_step_pm<PCGRL_PROB_BINARY, uint32_t>(h, actions, parity, st, R) : launch_step_pm<PCGRL_PROB_BINARY, uint64_t>(h, actions, parity, st, R);
+    return launch_step_p<PCGRL_PROB_BINARY>(h, actions, parity, st, R);
 }
 #endif
 #if PCGRL_IN_PART(PART_STEP_ZELDA)
 PCGRL_LOCAL int launch_step_zelda(pcgrl_env* h, const int32_t* actions, int parity, hipStream_t st, const RolloutArgs& R) {
-    return h->P.mask_bytes == 4 ? launch_step_pm<PCGRL_PROB_ZELDA, uint32_t>(h, actions, parity, st, R) : launch_step_pm<PCGRL_PROB_ZELDA, uint64_t>(h, actions, parity, st, R);
+    return launch_step_p<PCGRL_PROB_ZELDA>(h, actions, parity, st, R);
 }
 #endif
 static int launch_step(pcgrl_env* h, const int32_t* actions, int parity, hipStream_t st, const RolloutArgs& R = RolloutArgs{1, 0, nullptr, nullptr, nullptr}) {
@@ -885,10 +872,8 @@ PCGRL_LOCAL int launch_smb(pcgrl_env* h, int32_t* sync, int list_a, int mode_a, 
     nw = nw > SMB_MAX_WAVES ? SMB_MAX_WAVES : (nw < 1 ? 1 : nw);
     if ((size_t)nw * per_wave > SMB_LDS_BUDGET) return PCGRL_EINVAL;      // one search does not fit a compute unit's LDS
     // (a step's changed levels come on two lists: WL_INC = the ones expected to take long, first; see k_update)
-    hipLaunchKernelGGL(k_smb<0>, dim3(SOK_BLOCKS), dim3(nw * 64), nw * per_wave, st, h->P, h->B, (list_a == WL_CHG && mode_a == MODE_STEP) ? (int)WL_INC : -1,
-                       list_a, mode_a, list_b, mode_b, parity, rst_list, sync, clr, heap_n, inline_reset, gen_flag(h));
-    HIPCHK(hipGetLastError());
-    return PCGRL_OK;
+    return launch_fn(k_smb<0>, SOK_BLOCKS, nw * 64, nw * per_wave, st, h->P, h->B, (list_a == WL_CHG && mode_a == MODE_STEP) ? (int)WL_INC : -1,
+                     list_a, mode_a, list_b, mode_b, parity, rst_list, sync, clr, heap_n, inline_reset, gen_flag(h));
 }
 #endif  // PART_SMB
 #if PCGRL_IN_PART(PART_SEARCH)
@@ -913,9 +898,7 @@ PCGRL_LOCAL int launch_search_async(pcgrl_env* h, int32_t* tickets, int list_a, 
     const int toff = small ? ASYNC_SMALL_HEAP : SOK_LDS_HEAP, tsize = small ? ASYNC_SMALL_TABLE : SOK_LDS_TABLE;
     const size_t lds = (size_t)(toff + 2 * tsize) * 4;
     const int grid = small ? ASYNC_SMALL_BLOCKS : SOK_BLOCKS;
-    hipLaunchKernelGGL(async_kernel(h->P.prob), dim3(grid), dim3(128), lds, st, h->P, h->B, h->async, list_a, mode_a, list_b, mode_b, parity, rst_list, tickets, clr, budget, resume, toff, tsize, small);
-    HIPCHK(hipGetLastError());
-    return PCGRL_OK;
+    return launch_fn(async_kernel(h->P.prob), grid, 128, lds, st, h->P, h->B, h->async, list_a, mode_a, list_b, mode_b, parity, rst_list, tickets, clr, budget, resume, toff, tsize, small);
 }
 template <int PROB>
 static int launch_search_big_p(pcgrl_env* h, int32_t* sync, int list_a, int mode_a, int list_b, int mode_b, int parity, int rst_list, int clr, hipStream_t st) {
@@ -923,33 +906,25 @@ static int launch_search_big_p(pcgrl_env* h, int32_t* sync, int list_a, int mode
     const BigSearchArena A = {h->B.big_arena, D.block_bytes, D.heap_off, D.table_off, D.nodes_cap, D.tsize};
     const int cells = (h->P.width + 2) * (h->P.height + 2);
     const size_t lds = (((size_t)cells * 4 + 15) & ~(size_t)15) + (size_t)(BIG_MAX_WORDS + SOKB_MAXC / 64) * 8;
-    { const int rca = lds_cap<k_search_big<PROB>>(h->device, lds); if (rca) return rca; }       // (levels beyond ~15 000 cells: more than 64 KB of cell coordinates)
-    hipLaunchKernelGGL((k_search_big<PROB>), dim3(D.nblocks), dim3(64), lds, st, h->P, h->B, A, list_a, mode_a, list_b, mode_b, parity, rst_list, sync, clr);
-    HIPCHK(hipGetLastError());
-    return PCGRL_OK;
+    // (levels beyond ~15 000 cells: more than 64 KB of cell coordinates)
+    return launch<k_search_big<PROB>>(h, D.nblocks, 64, lds, st, h->P, h->B, A, list_a, mode_a, list_b, mode_b, parity, rst_list, sync, clr);
 }
 PCGRL_LOCAL int launch_search(pcgrl_env* h, int32_t* sync, int list_a, int mode_a, int list_b, int mode_b, int parity, int rst_list, int clr, hipStream_t st) {
-    if (h->P.big_search) {
-        if (h->P.prob == PCGRL_PROB_DDAVE) return launch_search_big_p<PCGRL_PROB_DDAVE>(h, sync, list_a, mode_a, list_b, mode_b, parity, rst_list, clr, st);
-        if (h->P.prob == PCGRL_PROB_MDUNGEON) return launch_search_big_p<PCGRL_PROB_MDUNGEON>(h, sync, list_a, mode_a, list_b, mode_b, parity, rst_list, clr, st);
-        return launch_search_big_p<PCGRL_PROB_SOKOBAN>(h, sync, list_a, mode_a, list_b, mode_b, parity, rst_list, clr, st);
-    }
+    if (h->P.big_search)
+        return with_prob<PCGRL_PROB_DDAVE, PCGRL_PROB_MDUNGEON, PCGRL_PROB_SOKOBAN>(h->P.prob, [&](auto prob) {
+            return launch_search_big_p<prob()>(h, sync, list_a, mode_a, list_b, mode_b, parity, rst_list, clr, st);
+        });
+    // (the compact searches are not templates over the problem: two signatures, caps raised at pcgrl_bind)
     const size_t lds = h->B.sok_use_lds ? sok_lds_bytes() : 0;   // heap + 64-bit-key table
     if (h->P.prob != PCGRL_PROB_SOKOBAN)
-        hipLaunchKernelGGL(agents4_kernel(h->P.prob), dim3(SOK_BLOCKS), dim3(128), lds, st, h->P, h->B, list_a, mode_a, list_b, mode_b, parity, rst_list, sync, clr);
-    else
-        hipLaunchKernelGGL(k_sokoban<0>, dim3(SOK_BLOCKS), dim3(128), lds, st, h->P, h->B, list_a, mode_a, list_b, mode_b, parity, rst_list,
-                           sync, sync + SOK_SY_WORDS, clr);
-    HIPCHK(hipGetLastError());
-    return PCGRL_OK;
+        return launch_fn(agents4_kernel(h->P.prob), SOK_BLOCKS, 128, lds, st, h->P, h->B, list_a, mode_a, list_b, mode_b, parity, rst_list, sync, clr);
+    return launch_fn(k_sokoban<0>, SOK_BLOCKS, 128, lds, st, h->P, h->B, list_a, mode_a, list_b, mode_b, parity, rst_list, sync, sync + SOK_SY_WORDS, clr);
 }
 int pcgrl_selftest_heap(const uint32_t* ops, int32_t n_ops, uint32_t* pops, uint32_t* heap_out, int32_t* n_out, void* stream) {
     if (!ops || !pops || !heap_out || !n_out || n_ops < 0) return PCGRL_EINVAL;
     const int cap = 16384;                               // 64 KB of LDS: fifteen levels, deeper than any search's heap
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_selftest_heap<0>), hipFuncAttributeMaxDynamicSharedMemorySize, cap * 4));
-    hipLaunchKernelGGL(k_selftest_heap<0>, dim3(1), dim3(64), (size_t)cap * 4, (hipStream_t)stream, ops, n_ops, cap, pops, heap_out, n_out);
-    HIPCHK(hipGetLastError());
-    return PCGRL_OK;
+    return launch_fn(k_selftest_heap<0>, 1, 64, (size_t)cap * 4, (hipStream_t)stream, ops, n_ops, cap, pops, heap_out, n_out);
 }
 #endif  // PART_SEARCH
 static int launch_solver(pcgrl_env* h, int slot, int list_a, int mode_a, int list_b, int mode_b, int parity, int rst_list, int clr,
@@ -961,35 +936,19 @@ static int launch_solver(pcgrl_env* h, int slot, int list_a, int mode_a, int lis
 }
 
 #if PCGRL_IN_PART(PART_STATS)
-template <int PROB>
-static int launch_reset_p(pcgrl_env* h, int list, int park_list, int parity, int clr, hipStream_t st) {
-    const PcgrlParams& P = h->P;
-    const int cells = P.width * P.height;
-    const size_t lds = 4 * (size_t)reset_stage_bytes(cells);
-    const int grid = grid_for(P.num_envs, 4, h->was_reset ? 512 : 4096);
-    const int gen = gen_flag(h);
-    if (P.group == 16 && P.mask_bytes == 4)
-        hipLaunchKernelGGL((k_reset<PROB, 16, uint32_t>), dim3(grid), dim3(PCGRL_BLOCK), lds, st, P, h->B, list, park_list, parity, gen, clr);
-    else if (P.group == 16)
-        hipLaunchKernelGGL((k_reset<PROB, 16, uint64_t>), dim3(grid), dim3(PCGRL_BLOCK), lds, st, P, h->B, list, park_list, parity, gen, clr);
-    else if (P.mask_bytes == 4)
-        hipLaunchKernelGGL((k_reset<PROB, 64, uint32_t>), dim3(grid), dim3(PCGRL_BLOCK), lds, st, P, h->B, list, park_list, parity, gen, clr);
-    else
-        hipLaunchKernelGGL((k_reset<PROB, 64, uint64_t>), dim3(grid), dim3(PCGRL_BLOCK), lds, st, P, h->B, list, park_list, parity, gen, clr);
-    HIPCHK(hipGetLastError());
-    return PCGRL_OK;
-}
 // map generation + start stats of every environment on the reset list
 PCGRL_LOCAL int launch_reset(pcgrl_env* h, int list, int park_list, int parity, int clr, hipStream_t st) {
     if (h->P.big) return launch_big(h, list, parity, MODE_START, clr, 0, park_list, st);
-    switch (h->P.prob) {
-        case PCGRL_PROB_BINARY: return launch_reset_p<PCGRL_PROB_BINARY>(h, list, park_list, parity, clr, st);
-        case PCGRL_PROB_ZELDA: return launch_reset_p<PCGRL_PROB_ZELDA>(h, list, park_list, parity, clr, st);
-        case PCGRL_PROB_MDUNGEON: return launch_reset_p<PCGRL_PROB_MDUNGEON>(h, list, park_list, parity, clr, st);
-        case PCGRL_PROB_DDAVE: return launch_reset_p<PCGRL_PROB_DDAVE>(h, list, park_list, parity, clr, st);
-        case PCGRL_PROB_SMB: return launch_reset_p<PCGRL_PROB_SMB>(h, list, park_list, parity, clr, st);
-        default: return launch_reset_p<PCGRL_PROB_SOKOBAN>(h, list, park_list, parity, clr, st);
-    }
+    const PcgrlParams& P = h->P;
+    const size_t lds = 4 * (size_t)reset_stage_bytes(P.width * P.height);
+    const int grid = grid_for(P.num_envs, 4, h->was_reset ? 512 : 4096);
+    const int gen = gen_flag(h);
+    return with_prob<PCGRL_PROB_BINARY, PCGRL_PROB_ZELDA, PCGRL_PROB_MDUNGEON, PCGRL_PROB_DDAVE, PCGRL_PROB_SMB, PCGRL_PROB_SOKOBAN>(P.prob, [&](auto prob) {
+        constexpr int PROB = prob();
+        return with_lanes(P.group, P.mask_bytes, [&](auto g, auto m) {
+            return launch<k_reset<PROB, g(), type_of<decltype(m)>>>(h, grid, PCGRL_BLOCK, lds, st, P, h->B, list, park_list, parity, gen, clr);
+        });
+    });
 }
 
 PCGRL_LOCAL int launch_planes_from_map(pcgrl_env* h, const uint8_t* maps, hipStream_t st) {     // pcgrl_set_maps
@@ -997,18 +956,11 @@ PCGRL_LOCAL int launch_planes_from_map(pcgrl_env* h, const uint8_t* maps, hipStr
     if (P.big) {            // no planes to rebuild: the byte maps are the state
         const size_t total = (size_t)P.num_envs * P.width * P.height;
         const size_t g = (total + 255) / 256;
-        hipLaunchKernelGGL(k_copy_map<0>, dim3((unsigned)(g < 16384 ? g : 16384)), dim3(256), 0, st, P, h->B, maps);
-        HIPCHK(hipGetLastError());
-        return PCGRL_OK;
+        return launch<k_copy_map<0>>(h, (int)(g < 16384 ? g : 16384), 256, 0, st, P, h->B, maps);
     }
     const size_t lds = 4 * (size_t)reset_tile_bytes(P.width * P.height);
     const int grid = grid_for(P.num_envs, 4, 4096);
-    if (P.mask_bytes == 4)
-        hipLaunchKernelGGL((k_planes_from_map<uint32_t>), dim3(grid), dim3(PCGRL_BLOCK), lds, st, P, h->B, maps);
-    else
-        hipLaunchKernelGGL((k_planes_from_map<uint64_t>), dim3(grid), dim3(PCGRL_BLOCK), lds, st, P, h->B, maps);
-    HIPCHK(hipGetLastError());
-    return PCGRL_OK;
+    return with_mask(P.mask_bytes, [&](auto m) { return launch<k_planes_from_map<type_of<decltype(m)>>>(h, grid, PCGRL_BLOCK, lds, st, P, h->B, maps); });
 }
 #endif  // PART_STATS
 
@@ -1025,67 +977,39 @@ static bool solver_rollout_applies(const pcgrl_env* h, int* envs_per_block) {
     return true;
 }
 #if PCGRL_IN_PART(PART_STEP_SOLVER)
-template <int PROB, int REP, class MaskT>
-static int launch_step_solver_t(pcgrl_env* h, const int32_t* actions, hipStream_t st, const RolloutArgs& R, int epb) {
-    const size_t lds = sok_lds_bytes();
-    { const int rca = lds_cap<k_step_solver<PROB, REP, MaskT>>(h->device, lds); if (rca) return rca; }
-    const int grid = (h->P.num_envs + epb - 1) / epb;
-    hipLaunchKernelGGL((k_step_solver<PROB, REP, MaskT>), dim3(grid), dim3(SS_THREADS), lds, st, h->P, h->B, actions, gen_flag(h), R.steps, R.action_stride, epb,
-                       R.reward_out, R.done_out, R.info_out);
-    HIPCHK(hipGetLastError());
-    return PCGRL_OK;
-}
-template <int PROB, class MaskT>
-static int launch_step_solver_p(pcgrl_env* h, const int32_t* actions, hipStream_t st, const RolloutArgs& R, int epb) {
-    switch (h->P.rep) {
-        case PCGRL_REP_NARROW: return launch_step_solver_t<PROB, PCGRL_REP_NARROW, MaskT>(h, actions, st, R, epb);
-        case PCGRL_REP_WIDE: return launch_step_solver_t<PROB, PCGRL_REP_WIDE, MaskT>(h, actions, st, R, epb);
-        default: return launch_step_solver_t<PROB, PCGRL_REP_TURTLE, MaskT>(h, actions, st, R, epb);
-    }
-}
 PCGRL_LOCAL int launch_step_solver(pcgrl_env* h, const int32_t* actions, hipStream_t st, const RolloutArgs& R, int epb) {
-    const bool m4 = h->P.mask_bytes == 4;
-    switch (h->P.prob) {
-        case PCGRL_PROB_SOKOBAN: return m4 ? launch_step_solver_p<PCGRL_PROB_SOKOBAN, uint32_t>(h, actions, st, R, epb) : launch_step_solver_p<PCGRL_PROB_SOKOBAN, uint64_t>(h, actions, st, R, epb);
-        case PCGRL_PROB_MDUNGEON: return m4 ? launch_step_solver_p<PCGRL_PROB_MDUNGEON, uint32_t>(h, actions, st, R, epb) : launch_step_solver_p<PCGRL_PROB_MDUNGEON, uint64_t>(h, actions, st, R, epb);
-        default: return m4 ? launch_step_solver_p<PCGRL_PROB_DDAVE, uint32_t>(h, actions, st, R, epb) : launch_step_solver_p<PCGRL_PROB_DDAVE, uint64_t>(h, actions, st, R, epb);
-    }
+    const size_t lds = sok_lds_bytes();
+    const int grid = (h->P.num_envs + epb - 1) / epb;
+    return with_prob<PCGRL_PROB_SOKOBAN, PCGRL_PROB_MDUNGEON, PCGRL_PROB_DDAVE>(h->P.prob, [&](auto prob) {
+        constexpr int PROB = prob();
+        return with_mask(h->P.mask_bytes, [&](auto m) {
+            using MaskT = type_of<decltype(m)>;
+            return with_rep<PCGRL_REP_NARROW, PCGRL_REP_WIDE, PCGRL_REP_TURTLE>(h->P.rep, [&](auto rep) {
+                return launch<k_step_solver<PROB, rep(), MaskT>>(h, grid, SS_THREADS, lds, st, h->P, h->B, actions, gen_flag(h), R.steps, R.action_stride, epb,
+                                                                 R.reward_out, R.done_out, R.info_out);
+            });
+        });
+    });
 }
 
-// pcgrl_get_stats, second launch (kernels_evaluate.h): the parked maps' searches on `blocks` persistent blocks, each with a node pool
-// of its own in the caller's workspace.  Of the DevBufs copy the kernel reads the three fields SearchGame<PROB>::build looks at.
-template <int PROB>
-static int launch_get_stats_search_p(pcgrl_env* h, const uint8_t* maps, int32_t* rows_out, int32_t* head, const int32_t* jobs, SokNode* pools, int blocks, hipStream_t st) {
-    const size_t lds = sok_lds_bytes();
-    { const int rca = lds_cap<k_get_stats_search<PROB>>(h->device, lds); if (rca) return rca; }
+// The second launches of pcgrl_get_stats and pcgrl_get_solution: the parked maps' searches on `blocks` persistent blocks, each with a
+// node pool of its own in the caller's workspace.  Of DevBufs these kernels read the three fields SearchGame<PROB>::build looks at.
+static DevBufs search_devbufs(const pcgrl_env* h) {
     DevBufs Bs;
     memset(&Bs, 0, sizeof(Bs));
     Bs.status = h->B.status; Bs.sok_use_lds = h->B.sok_use_lds; Bs.sok_fast_maxc = h->B.sok_fast_maxc;
-    const int pool_stride = (int)(sok_pool_bytes(&h->cfg) / sizeof(SokNode));
-    hipLaunchKernelGGL((k_get_stats_search<PROB>), dim3(blocks), dim3(SS_THREADS), lds, st, h->P, Bs, maps, rows_out, head, jobs, pools, pool_stride);
-    HIPCHK(hipGetLastError());
-    return PCGRL_OK;
+    return Bs;
 }
+static int search_pool_stride(const pcgrl_env* h) { return (int)(sok_pool_bytes(&h->cfg) / sizeof(SokNode)); }
+// (kernels_evaluate.h)
 PCGRL_LOCAL int launch_get_stats_search(pcgrl_env* h, const uint8_t* maps, int32_t* rows_out, int32_t* head, const int32_t* jobs, SokNode* pools, int blocks, hipStream_t st) {
-    switch (h->P.prob) {
-        case PCGRL_PROB_SOKOBAN: return launch_get_stats_search_p<PCGRL_PROB_SOKOBAN>(h, maps, rows_out, head, jobs, pools, blocks, st);
-        case PCGRL_PROB_MDUNGEON: return launch_get_stats_search_p<PCGRL_PROB_MDUNGEON>(h, maps, rows_out, head, jobs, pools, blocks, st);
-        case PCGRL_PROB_DDAVE: return launch_get_stats_search_p<PCGRL_PROB_DDAVE>(h, maps, rows_out, head, jobs, pools, blocks, st);
-        default: return PCGRL_EINVAL;
-    }
+    return with_prob<PCGRL_PROB_SOKOBAN, PCGRL_PROB_MDUNGEON, PCGRL_PROB_DDAVE>(h->P.prob, [&](auto prob) {
+        return launch<k_get_stats_search<prob()>>(h, blocks, SS_THREADS, sok_lds_bytes(), st, h->P, search_devbufs(h), maps, rows_out, head, jobs, pools, search_pool_stride(h));
+    });
 }
-
-// pcgrl_get_solution, second launch (kernels_solution.h): k_get_stats_search's shape with the traced sokoban searches
+// (kernels_solution.h: k_get_stats_search's shape with the traced sokoban searches)
 PCGRL_LOCAL int launch_get_solution(pcgrl_env* h, const uint8_t* maps, int32_t* rows_out, const SolOut& out, int32_t* head, const int32_t* jobs, SokNode* pools, int blocks, hipStream_t st) {
-    const size_t lds = sok_lds_bytes();
-    { const int rca = lds_cap<k_get_solution<0>>(h->device, lds); if (rca) return rca; }
-    DevBufs Bs;
-    memset(&Bs, 0, sizeof(Bs));
-    Bs.status = h->B.status; Bs.sok_use_lds = h->B.sok_use_lds; Bs.sok_fast_maxc = h->B.sok_fast_maxc;
-    const int pool_stride = (int)(sok_pool_bytes(&h->cfg) / sizeof(SokNode));
-    hipLaunchKernelGGL(k_get_solution<0>, dim3(blocks), dim3(SS_THREADS), lds, st, h->P, Bs, maps, rows_out, out, head, jobs, pools, pool_stride);
-    HIPCHK(hipGetLastError());
-    return PCGRL_OK;
+    return launch<k_get_solution<0>>(h, blocks, SS_THREADS, sok_lds_bytes(), st, h->P, search_devbufs(h), maps, rows_out, out, head, jobs, pools, search_pool_stride(h));
 }
 
 #endif  // PART_STEP_SOLVER
@@ -1216,6 +1140,9 @@ int pcgrl_bind_row(pcgrl_env* h, const pcgrl_row* r) {
 // What a step with a bound row is handed: src / n = the action values of the row's `actions` column (pcgrl_step_flat: the flat
 // indices, not the decoded triples), src_i64 / step_i64: whether they, and the step's `actions` argument, are int64.
 struct RowCall { bool on; const int32_t* src; int n; int src_i64, step_i64; };
+static RowCall plain_row_call(const pcgrl_env* h, const int32_t* actions) {       // pcgrl_step, pcgrl_step_async: the row's actions are the step's
+    return RowCall{h->row_on != 0, actions, h->cfg.num_envs * action_width(h->cfg.rep), h->row_i64, h->row_i64};
+}
 static void row_devbufs(pcgrl_env* h, bool on, int step_i64) {      // (for the launches of one step, like async_devbufs)
     if (on) { h->B.row = h->row; h->B.act_i64 = step_i64; }
     else { memset(&h->B.row, 0, sizeof(h->B.row)); h->B.act_i64 = 0; }
@@ -1345,7 +1272,7 @@ int pcgrl_step_async(pcgrl_env* h, const int32_t* actions, int32_t pop_budget, v
     const int par = h->parity;
     const bool ar = h->P.auto_reset != 0;
     int rc;
-    const RowCall row = {h->row_on != 0, actions, h->cfg.num_envs * action_width(h->cfg.rep), h->row_i64, h->row_i64};
+    const RowCall row = plain_row_call(h, actions);
     if (row.on && (h->row.ep_return || h->row.ep_length) && !h->B.last_return) return PCGRL_ESTATE;
     HIPCHK(hipMemsetAsync(h->B.sok_sync, 0, 8 * sizeof(int32_t), st));       // the search launches' tickets, the counts of runnable slots and of handed-over jobs
     async_devbufs(h, true);
@@ -1399,7 +1326,7 @@ static int step_impl(pcgrl_env* h, const int32_t* actions, void* stream, const R
 }
 int pcgrl_step(pcgrl_env* h, const int32_t* actions, void* stream) {
     if (!h) return PCGRL_ESTATE;
-    const RowCall row = {h->row_on != 0, actions, h->cfg.num_envs * action_width(h->cfg.rep), h->row_i64, h->row_i64};
+    const RowCall row = plain_row_call(h, actions);
     return step_impl(h, actions, stream, row);
 }
 
