@@ -165,5 +165,159 @@ def replay_sokoban(level, moves):
                          np.array(targets, np.int64).reshape(-1, 2), bool(legal), bool(won))
 
 
+def playthrough_levels(prob, maps, device=None, max_len=None, **params):
+    """The play behind the mdungeon / ddave planner statistics of a stack of levels in one call, next to solve_levels(): `maps`
+    array-like uint8 [M, H, W], `params` as for adjust_param.  Returns BatchedPcgrlEnv.playthrough()'s Playthroughs (moves, length,
+    agent, rows, stats)."""
+    import numpy as np
+    from .envs import BatchedPcgrlEnv
+    shape = tuple(maps.shape) if hasattr(maps, "shape") else np.asarray(maps).shape
+    if len(shape) != 3:
+        raise ValueError("playthrough_levels(): maps must be [M, H, W], got shape %s" % (shape,))
+    env = BatchedPcgrlEnv(prob=prob, rep="wide", num_envs=1, device=device, seed=0, auto_reset=False)
+    try:
+        env.adjust_param(width=int(shape[2]), height=int(shape[1]), **params)
+        return env.playthrough(maps, max_len=max_len)
+    finally:
+        env.close()
+
+
+class MdungeonReplay:
+    """What replay_mdungeon() returns: `player` int [T+1, 2] -- (row, column) per frame, frame 0 the level as given, frame t after move
+    t -- and per frame `health`, `potions`, `treasures`, `enemies` int [T+1] (collected / killed so far); of the last frame `won`
+    (alive on the exit), `dead` (health 0) and `heuristic` (distance to the exit + 4 * (5 - health) - 4 * treasures)."""
+    __slots__ = ("player", "health", "potions", "treasures", "enemies", "won", "dead", "heuristic")
+
+    def __init__(self, player, health, potions, treasures, enemies, won, dead, heuristic):
+        self.player, self.health, self.potions, self.treasures, self.enemies = player, health, potions, treasures, enemies
+        self.won, self.dead, self.heuristic = won, dead, heuristic
+
+
+class DdaveReplay:
+    """What replay_ddave() returns: `player` int [T+1, 2] -- (row, column) per frame, frame 0 the level as given, frame t after move t --
+    and per frame `jumps`, `diamonds`, `has_key`, `air` int [T+1] (jumps made, diamonds collected, 1 once the key is picked up, the air
+    time left); of the last frame `won` (on the exit with the key), `dead` (on a spike) and `heuristic` (distance to the exit, or while
+    the key lies there distance to the key + bordered width + bordered height; minus 5 per diamond)."""
+    __slots__ = ("player", "jumps", "diamonds", "has_key", "air", "won", "dead", "heuristic")
+
+    def __init__(self, player, jumps, diamonds, has_key, air, won, dead, heuristic):
+        self.player, self.jumps, self.diamonds, self.has_key, self.air = player, jumps, diamonds, has_key, air
+        self.won, self.dead, self.heuristic = won, dead, heuristic
+
+
+def _replay_level(name, level, ntiles, need):
+    import numpy as np
+    lv = np.asarray(level)
+    if lv.ndim != 2:
+        raise ValueError("%s(): level must be [H, W], got shape %s" % (name, lv.shape))
+    if lv.size and int(lv.max()) >= ntiles:
+        raise ValueError("%s(): tile id %d is not one of 0..%d" % (name, int(lv.max()), ntiles - 1))
+    where = []
+    for tile, what in need:
+        at = np.argwhere(lv == tile)
+        if len(at) != 1:
+            raise ValueError("%s(): the level needs exactly one %s tile, it has %d" % (name, what, len(at)))
+        where.append((int(at[0][0]), int(at[0][1])))
+    return lv, where
+
+
+def _replay_moves(name, moves):
+    import numpy as np
+    out = []
+    for mv in np.asarray(moves).reshape(-1).tolist():
+        if mv < 0:
+            break
+        if mv > 3:
+            raise ValueError("%s(): move %d is not one of 0..3" % (name, mv))
+        out.append(int(mv))
+    return out
+
+
+def replay_mdungeon(level, moves):
+    """Play `moves` (0..3 = left, right, up, down; a negative entry ends the list, like the -1 padding of Playthroughs.moves) on one
+    MiniDungeons level [H, W] of tile ids (0 empty, 1 solid, 2 player, 3 exit, 4 potion, 5 treasure, 6 goblin, 7 ogre) by the game's
+    rules: outside the level is solid; the player starts with health 5; a step into a solid cell changes nothing; walking onto a potion
+    gives +2 health (at most 5), onto a treasure +1 treasure, onto a goblin / ogre costs 1 / 2 health (not below 0) and counts as a
+    kill; the thing is gone.  Once the player is dead (health 0) or stands on the exit, nothing moves any more.  Host side, numpy.
+    Returns a MdungeonReplay."""
+    import numpy as np
+    lv, (pos, door) = _replay_level("replay_mdungeon", level, 8, ((2, "player"), (3, "exit")))
+    H, W = lv.shape
+    things = {(int(r), int(c)): int(lv[r, c]) for r, c in np.argwhere(lv >= 4)}
+    step = ((0, -1), (0, 1), (-1, 0), (1, 0))
+    health, potions, treasures, enemies = 5, 0, 0, 0
+    frames = [(pos, health, potions, treasures, enemies)]
+    for mv in _replay_moves("replay_mdungeon", moves):
+        to = (pos[0] + step[mv][0], pos[1] + step[mv][1])
+        over = health == 0 or pos == door
+        if not over and 0 <= to[0] < H and 0 <= to[1] < W and lv[to] != 1:
+            pos = to
+            t = things.pop(to, None)
+            if t == 4:
+                health, potions = min(health + 2, 5), potions + 1
+            elif t == 5:
+                treasures += 1
+            elif t is not None:
+                health, enemies = max(health - (2 if t == 7 else 1), 0), enemies + 1
+        frames.append((pos, health, potions, treasures, enemies))
+    col = lambda k: np.array([f[k] for f in frames], np.int64)
+    heuristic = abs(pos[0] - door[0]) + abs(pos[1] - door[1]) + 4 * (5 - health) - 4 * treasures
+    return MdungeonReplay(np.array([f[0] for f in frames], np.int64).reshape(-1, 2), col(1), col(2), col(3), col(4),
+                          bool(health > 0 and pos == door), bool(health == 0), int(heuristic))
+
+
+def replay_ddave(level, moves):
+    """Play `moves` (0..3 = stay, left, right, jump; a negative entry ends the list) on one Dangerous Dave level [H, W] of tile ids
+    (0 empty, 1 solid, 2 player, 3 exit, 4 diamond, 5 key, 6 spike) by the game's rules: outside the level is solid; a sideways move
+    steps into a cell that is not solid; a jump starts only from the ground (a solid cell below) under a free ceiling and gives air
+    time 3 and +1 jump; then, in every move, with air time above 1 it drops by one and the player rises one cell (a solid cell above
+    leaves air time 1 instead), with air time 1 the player hovers (air time 0), else the player falls one cell if the cell below is
+    not solid.  On the cell reached a diamond is picked up, else a spike kills, else the key is picked up.  Once the player is dead or
+    stands on the exit with the key, nothing moves any more.  Host side, numpy.  Returns a DdaveReplay."""
+    import numpy as np
+    lv, (pos, door, key) = _replay_level("replay_ddave", level, 7, ((2, "player"), (3, "exit"), (5, "key")))
+    H, W = lv.shape
+
+    def solid(r, c):
+        return not (0 <= r < H and 0 <= c < W) or lv[r, c] == 1
+
+    left = {(int(r), int(c)) for r, c in np.argwhere(lv == 4)}
+    alive, has_key, air, jumps, diamonds = True, 0, 0, 0, 0
+    frames = [(pos, jumps, diamonds, has_key, air)]
+    for mv in _replay_moves("replay_ddave", moves):
+        if alive and not (has_key and pos == door):
+            r, c = pos
+            if mv == 1 and not solid(r, c - 1):
+                c -= 1
+            elif mv == 2 and not solid(r, c + 1):
+                c += 1
+            elif mv == 3 and solid(pos[0] + 1, pos[1]) and not solid(pos[0] - 1, pos[1]):
+                air, jumps = 3, jumps + 1
+            if air > 1:
+                air -= 1
+                if not solid(r - 1, c):
+                    r -= 1
+                else:
+                    air = 1
+            elif air == 1:
+                air = 0
+            elif not solid(r + 1, c):
+                r += 1
+            pos = (r, c)
+            if pos in left:
+                left.discard(pos)
+                diamonds += 1
+            elif lv[pos] == 6:
+                alive = False
+            elif not has_key and pos == key:
+                has_key = 1
+        frames.append((pos, jumps, diamonds, has_key, air))
+    col = lambda k: np.array([f[k] for f in frames], np.int64)
+    goal = door if has_key else key
+    heuristic = abs(pos[0] - goal[0]) + abs(pos[1] - goal[1]) + (0 if has_key else W + 2 + H + 2) - 5 * diamonds
+    return DdaveReplay(np.array([f[0] for f in frames], np.int64).reshape(-1, 2), col(1), col(2), col(3), col(4),
+                       bool(alive and has_key and pos == door), bool(not alive), int(heuristic))
+
+
 register_with_gym()      # no-op without a gym of the reference's era (none is on the MI355X image)
 register_with_gymnasium()   # likewise for gymnasium / gym >= 0.26 (five-tuple adapter)

@@ -79,11 +79,14 @@ struct DdKidsSerial {     // one lane makes the four children one after the othe
 };
 
 // One search.  `table` (64-bit slots) must be all zeros; `cache` is room for four nodes.  ret_* describe the returned node.
-template <class HP, class TP, class Hook, class Kids, class RSP = SokNoResume>
+// Traced (PlayTrace, mdungeon_solver.h) as md_search_fast is: the one-wavefront loop only, entry dd_search_fast_traced below.
+template <class HP, class TP, class Hook, class Kids, class RSP = SokNoResume, class TRP = PlayNoTrace>
 PCGRL_D bool dd_search_fast(const DdLevel& L, const DdFastLevel& F, DdFastNode* pool, HP heap, TP table, int table_mask, DdFastNode* cache,
                             const DdNode& root, int k, int power, uint64_t& ret_key, int& ret_h, int& ret_depth, int& ret_jumps, int& out_iters,
-                            bool& out_exhausted, Hook hook, Kids kids, SokDuoBox* duo = nullptr, RSP rsp = RSP()) {
+                            bool& out_exhausted, Hook hook, Kids kids, SokDuoBox* duo = nullptr, RSP rsp = RSP(), TRP trp = TRP()) {
     constexpr bool RS = SokRs<RSP>::on;          // suspend / resume: sokoban_fast.h SokResume
+    constexpr bool TRC = PlayTr<TRP>::on;
+    int tr_cur = 0, tr_best = 0, tr_ret = 0;     // (TRC) pool indices: the node in hand, the best node, the returned node
     SokResume* const rst = sok_rs_state(rsp);
     const int rs_limit = sok_rs_limit(rsp);
     const bool resumed = RS && rst->iterations > 0;
@@ -108,7 +111,7 @@ PCGRL_D bool dd_search_fast(const DdLevel& L, const DdFastLevel& F, DdFastNode* 
     }
     ret_key = n0.key; ret_h = root.h; ret_depth = 0; ret_jumps = 0;
 #if defined(__HIPCC__)
-    if (duo && k >= 0) {
+    if (!TRC && duo && k >= 0) {
         // the search wavefront of a two-wavefront A* search (sokoban_fast.h, SokDuoBox; the same split as in mdungeon_fast.h):
         // the block's heap server owns the heap.  Same operations in the same order as the loop below.
         uint32_t cur_word = (uint32_t)(2 * root.h + DD_PRIO_BIAS) << 16;      // the root's word: pool index 0, not flagged
@@ -201,6 +204,7 @@ if (cmin != SOK_DUO_NONE && (nxt == SOK_DUO_NONE || sok_lt(cmin, nxt))) nxt = cm
             ent = heap[0];
             const uint32_t last = heap[--heapn];
             const int cur = (int)(ent & 0x7FFFu);
+            if (TRC) tr_cur = cur;
             if (!(ent & MDF_FLAG) && cur != ahead_idx) {
                 if ((unsigned)(cur - cache_base) < (unsigned)cache_n) nd = cache[cur - cache_base];
                 else nd = pool[cur];
@@ -214,6 +218,7 @@ if (cmin != SOK_DUO_NONE && (nxt == SOK_DUO_NONE || sok_lt(cmin, nxt))) nxt = cm
         } else {
             ent = heap[head++];
             const int cur = (int)(ent & 0x7FFFu);
+            if (TRC) tr_cur = cur;
             if (!(ent & MDF_FLAG) && cur != ahead_idx) nd = pool[cur];
             ahead_idx = -1;
             if (head < heapn) {
@@ -226,7 +231,9 @@ if (cmin != SOK_DUO_NONE && (nxt == SOK_DUO_NONE || sok_lt(cmin, nxt))) nxt = cm
         const int node_player = (int)((key >> 48) & 0xFF);
         const int node_h = (int)(nd.hd & 0xFFFFu) - DD_PRIO_BIAS, node_depth = (int)(nd.hd >> 16), node_aj = (int)nd.aj;
         if (!(key & DDF_KEY_THERE) && node_player == L.door) {   // checkWin
-            win = true; ret_key = key; ret_h = node_h; ret_depth = node_depth; ret_jumps = node_aj >> 2; break;
+            win = true; ret_key = key; ret_h = node_h; ret_depth = node_depth; ret_jumps = node_aj >> 2;
+            if (TRC) tr_ret = tr_cur;
+            break;
         }
         uint32_t slot;
         if (mdf_lookup(table, table_mask, key, slot)) continue;
@@ -234,6 +241,7 @@ if (cmin != SOK_DUO_NONE && (nxt == SOK_DUO_NONE || sok_lt(cmin, nxt))) nxt = cm
         cache_base = npool; cache_n = 0;
         if (!have_best || node_h < best_h || (node_h == best_h && node_depth < best_depth)) {
             have_best = true; best_h = node_h; best_depth = node_depth; best_key = key; best_aj = node_aj;
+            if (TRC) tr_best = tr_cur;
         }
         const bool ground = sok_bit(L.solid, node_player + L.w), ceiling = sok_bit(L.solid, node_player - L.w);
         DdChild kid[4];                         // stay, left, right, jump -- always four
@@ -247,6 +255,7 @@ if (cmin != SOK_DUO_NONE && (nxt == SOK_DUO_NONE || sok_lt(cmin, nxt))) nxt = cm
                 DdFastNode c;
                 c.key = kid[d].key; c.hd = (uint32_t)(kid[d].h + DD_PRIO_BIAS) | ((uint32_t)(node_depth + 1) << 16); c.aj = (uint32_t)kid[d].aj;
                 pool[npool] = c;
+                if (TRC) play_tr_child(trp, npool, tr_cur, d);
                 if (k >= 0) cache[cache_n++] = c;
                 ent_c = (uint32_t)npool;
                 npool++;
@@ -266,9 +275,19 @@ if (cmin != SOK_DUO_NONE && (nxt == SOK_DUO_NONE || sok_lt(cmin, nxt))) nxt = cm
         rst->best_h = best_h; rst->best_depth = best_depth; rst->have_best = have_best ? 1 : 0; rst->best_key = best_key; rst->best_aux = best_aj;
     }
     if (!win && have_best) { ret_key = best_key; ret_h = best_h; ret_depth = best_depth; ret_jumps = best_aj >> 2; }
+    if (TRC) play_tr_node(trp, win ? tr_ret : (have_best ? tr_best : 0));
     out_iters = iterations;
     out_exhausted = !win && !aborted && !suspended && !(k >= 0 ? heapn > 0 : head < heapn);
     return win;
+}
+
+// The traced search: the one-wavefront loop, never suspended.
+template <class HP, class TP, class Hook, class Kids>
+PCGRL_D bool dd_search_fast_traced(const DdLevel& L, const DdFastLevel& F, DdFastNode* pool, HP heap, TP table, int table_mask, DdFastNode* cache,
+                                   const DdNode& root, int k, int power, uint64_t& ret_key, int& ret_h, int& ret_depth, int& ret_jumps, int& out_iters,
+                                   bool& out_exhausted, Hook hook, Kids kids, PlayTrace tr) {
+    return dd_search_fast(L, F, pool, heap, table, table_mask, cache, root, k, power, ret_key, ret_h, ret_depth, ret_jumps, out_iters, out_exhausted, hook,
+                          kids, (SokDuoBox*)nullptr, SokNoResume(), tr);
 }
 
 // dist-win, sol-length, num-jumps, col-diamonds from what a search returned

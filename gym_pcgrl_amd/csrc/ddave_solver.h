@@ -77,10 +77,10 @@ PCGRL_D bool dd_same(const DdNode& a, const DdNode& b) {      // equality of Sta
            a.alive[1] == b.alive[1] && a.alive[2] == b.alive[2] && a.alive[3] == b.alive[3];
 }
 
-// One search (one lane).  Same contract as md_search.
-template <class HP, class TP, class Hook>
+// One search (one lane).  Same contract as md_search, PlayTrace (mdungeon_solver.h) included.
+template <class HP, class TP, class Hook, class TRP = PlayNoTrace>
 PCGRL_D bool dd_search(const DdLevel& L, DdNode* pool, HP heap, TP table, int table_mask, DdNode& w, const DdNode& root, int k,
-                       int power, int& out_iters, bool& out_exhausted, Hook hook) {
+                       int power, int& out_iters, bool& out_exhausted, Hook hook, TRP trp = TRP()) {
     int npool = 0, head = 0, heapn = 0, iterations = 0, best = -1, best_h = 0, best_depth = 0;
     MdNode* mpool = reinterpret_cast<MdNode*>(pool);          // same size and alignment: the 5 x 64-bit copy helpers
     md_copy(mpool, reinterpret_cast<const MdNode*>(&root));
@@ -151,6 +151,7 @@ PCGRL_D bool dd_search(const DdLevel& L, DdNode* pool, HP heap, TP table, int ta
             w.player = (uint8_t)np; w.flags = (uint8_t)(fl | (air << DD_F_AIR_SHIFT)); w.jumps = (uint16_t)jumps;
             w.h = (int16_t)dd_heuristic(L, np, (fl & DD_F_KEY_THERE) != 0, dia);
             md_copy(mpool + npool, reinterpret_cast<const MdNode*>(&w));
+            play_tr_child(trp, npool, cur, d);
             if (k >= 0) {
                 heap[heapn] = ((uint32_t)(2 * w.h + k * w.depth + DD_PRIO_BIAS) << 16) | (uint32_t)npool;
                 heapn++;
@@ -161,6 +162,7 @@ PCGRL_D bool dd_search(const DdLevel& L, DdNode* pool, HP heap, TP table, int ta
         }
     }
     if (!win) result = best < 0 ? 0 : best;
+    play_tr_node(trp, result);
     md_copy(reinterpret_cast<MdNode*>(&w), mpool + result);
     out_iters = iterations;
     out_exhausted = !win && !aborted && !(k >= 0 ? heapn > 0 : head < npool);

@@ -130,11 +130,16 @@ extern __device__ unsigned long long* g_tl_buf;      // worklist.h (developer bu
 // the four children of a pop (serially, or one per lane on the device: the search then runs on four lanes in lockstep,
 // uniform except for that step).
 // ret_key / ret_h / ret_depth describe the returned node (winner, or best node).
-template <class HP, class TP, class Hook, class Kids, class RSP = SokNoResume>
+// A traced search (PlayTraceInNode, mdungeon_solver.h) is the one-wavefront loop only -- its entry is md_search_fast_traced below, which has
+// no `duo` parameter, and the two-wavefront branch is compiled out of that instantiation.  A child that mdf_child drops gets no pool
+// node and so no trace word: neither a winner nor a best node can be one of them.
+template <class HP, class TP, class Hook, class Kids, class RSP = SokNoResume, class TRP = PlayNoTrace>
 PCGRL_D bool md_search_fast(const MdLevel& L, const MdFastLevel& F, MdFastNode* pool, HP heap, TP table, int table_mask, MdFastNode* cache,
                             const MdNode& root, int k, int power, uint64_t& ret_key, int& ret_h, int& ret_depth, int& out_iters,
-                            bool& out_exhausted, Hook hook, Kids kids, SokDuoBox* duo = nullptr, RSP rsp = RSP()) {
+                            bool& out_exhausted, Hook hook, Kids kids, SokDuoBox* duo = nullptr, RSP rsp = RSP(), TRP trp = TRP()) {
     constexpr bool RS = SokRs<RSP>::on;          // suspend / resume: sokoban_fast.h SokResume
+    constexpr bool TRC = PlayTr<TRP>::on;
+    int tr_cur = 0, tr_best = 0, tr_ret = 0;     // (TRC) pool indices: the node in hand, the best node, the returned node
     SokResume* const rst = sok_rs_state(rsp);
     const int rs_limit = sok_rs_limit(rsp);
     const bool resumed = RS && rst->iterations > 0;
@@ -159,7 +164,7 @@ PCGRL_D bool md_search_fast(const MdLevel& L, const MdFastLevel& F, MdFastNode* 
     }
     ret_key = n0.key; ret_h = root.h; ret_depth = 0;
 #if defined(__HIPCC__)
-    if (duo && k >= 0) {
+    if (!TRC && duo && k >= 0) {
         // the search wavefront of a two-wavefront A* search (sokoban_fast.h, SokDuoBox): the heap belongs to the block's heap
         // server, which appends the children of a pop, publishes the new top and removes / repairs for it while this
         // wavefront expands it.  Same operations in the same order as the loop below.
@@ -258,6 +263,7 @@ if (cmin != SOK_DUO_NONE && (nxt == SOK_DUO_NONE || sok_lt(cmin, nxt))) nxt = cm
             const uint32_t last = heap[--heapn];
             const int cur = (int)(ent & 0x7FFFu);
             const bool live = !(ent & MDF_FLAG);
+            if (TRC) tr_cur = cur;
             if (live && cur != ahead_idx) {
                 if ((unsigned)(cur - cache_base) < (unsigned)cache_n) nd = cache[cur - cache_base];
                 else nd = pool[cur];
@@ -271,6 +277,7 @@ if (cmin != SOK_DUO_NONE && (nxt == SOK_DUO_NONE || sok_lt(cmin, nxt))) nxt = cm
         } else {
             ent = heap[head++];
             const int cur = (int)(ent & 0x7FFFu);
+            if (TRC) tr_cur = cur;
             if (!(ent & MDF_FLAG) && cur != ahead_idx) nd = pool[cur];
             ahead_idx = -1;
             if (head < heapn) {
@@ -284,13 +291,14 @@ if (cmin != SOK_DUO_NONE && (nxt == SOK_DUO_NONE || sok_lt(cmin, nxt))) nxt = cm
         const uint64_t alive = key & MDF_ALIVE_MASK;
         const int node_player = (int)((key >> 48) & 0xFF), node_health = (int)(key >> 56);
         const int node_h = (int)(nd.hd & 0xFFFFu) - MD_PRIO_BIAS, node_depth = (int)(nd.hd >> 16);
-        if (node_player == L.door) { win = true; ret_key = key; ret_h = node_h; ret_depth = node_depth; break; }   // checkWin
+        if (node_player == L.door) { win = true; ret_key = key; ret_h = node_h; ret_depth = node_depth; if (TRC) tr_ret = tr_cur; break; }   // checkWin
         uint32_t slot;
         if (mdf_lookup(table, table_mask, key, slot)) continue;
         table[slot] = key;
         cache_base = npool; cache_n = 0;
         if (!have_best || node_h < best_h || (node_h == best_h && node_depth < best_depth)) {
             have_best = true; best_h = node_h; best_depth = node_depth; best_key = key;
+            if (TRC) tr_best = tr_cur;
         }
         MDP(1);
         MdChild kid[4];                         // Node.getChildren: L, R, U, D -- always four
@@ -303,8 +311,10 @@ if (cmin != SOK_DUO_NONE && (nxt == SOK_DUO_NONE || sok_lt(cmin, nxt))) nxt = cm
             uint32_t ent_c = MDF_FLAG;
             if (!kid[d].drop) {
                 MdFastNode c;
-                c.key = kid[d].key; c.hd = (uint32_t)(kid[d].h + MD_PRIO_BIAS) | ((uint32_t)(node_depth + 1) << 16); c.pad = 0;
+                c.key = kid[d].key; c.hd = (uint32_t)(kid[d].h + MD_PRIO_BIAS) | ((uint32_t)(node_depth + 1) << 16);
+                c.pad = play_tr_pad(trp, tr_cur, d);           // 0 unless traced in the node
                 pool[npool] = c;
+                if (TRC) play_tr_child(trp, npool, tr_cur, d);
                 if (k >= 0) cache[cache_n++] = c;
                 ent_c = (uint32_t)npool;
                 npool++;
@@ -326,9 +336,29 @@ if (cmin != SOK_DUO_NONE && (nxt == SOK_DUO_NONE || sok_lt(cmin, nxt))) nxt = cm
         rst->best_h = best_h; rst->best_depth = best_depth; rst->have_best = have_best ? 1 : 0; rst->best_key = best_key;
     }
     if (!win && have_best) { ret_key = best_key; ret_h = best_h; ret_depth = best_depth; }
+    if (TRC) play_tr_node(trp, win ? tr_ret : (have_best ? tr_best : 0));
     out_iters = iterations;
     out_exhausted = !win && !aborted && !suspended && !(k >= 0 ? heapn > 0 : head < heapn);
     return win;
+}
+
+// The traced search: the one-wavefront loop, never suspended.  Its trace word (parent | move << 30) travels in the node's free `pad`,
+// inside the 16-byte store that files the child: no store of its own, no array beside the pool.
+template <class HP, class TP, class Hook, class Kids>
+PCGRL_D bool md_search_fast_traced(const MdLevel& L, const MdFastLevel& F, MdFastNode* pool, HP heap, TP table, int table_mask, MdFastNode* cache,
+                                   const MdNode& root, int k, int power, uint64_t& ret_key, int& ret_h, int& ret_depth, int& out_iters,
+                                   bool& out_exhausted, Hook hook, Kids kids, PlayTraceInNode tr) {
+    return md_search_fast(L, F, pool, heap, table, table_mask, cache, root, k, power, ret_key, ret_h, ret_depth, out_iters, out_exhausted, hook, kids,
+                          (SokDuoBox*)nullptr, SokNoResume(), tr);
+}
+// play_walk_back (mdungeon_solver.h) for the pool of a traced compact search; `cap`: the pool's nodes
+PCGRL_D void mdf_walk_back(const MdFastNode* pool, int cap, int node, int depth, int8_t* out, int max_len) {
+    for (int i = depth - 1; i >= 0; i--) {
+        if ((unsigned)node >= (unsigned)cap) break;
+        const uint32_t t = pool[node].pad;
+        if (i < max_len) out[i] = (int8_t)(t >> 30);
+        node = (int)(t & 0x3FFFFFFFu);
+    }
 }
 
 // The five values _run_game hands to get_stats, from the key a search returned.

@@ -105,6 +105,43 @@ PCGRL_D void md_store(MdNode* p, const MdRaw& r) {
     d[0] = r.q[0]; d[1] = r.q[1]; d[2] = r.q[2]; d[3] = r.q[3]; d[4] = r.q[4];
 }
 
+// The play behind the statistics (pcgrl_get_playthrough, kernels_playthrough.h).  The reference's Node keeps its parent and the
+// action that made it (engine.py:22-49) and getSolution returns node.getActions(); _run_game keeps only len(sol).  A search handed
+// `PlayTrace{trace, &node}` records for every child it files into the pool one word in the array beside the pool: trace[child] =
+// parent's pool index | child number << 30 -- the child number is the move, the children are made in the order of the engine's
+// `directions` (mdungeon: left, right, up, down; ddave: stay, left, right, jump) -- and leaves in *node the pool index of the node it
+// returns: the winner, or its best node.  The moves are read off the parent chain from there (play_walk_back).  Nothing else
+// changes: same pops in the same order, same counts, same results; node layouts, hashes and key comparisons are what they were.
+// PlayNoTrace (the default) compiles every trace of this away, like SokNoTrace.  Shared by the four searches of mdungeon_solver.h,
+// mdungeon_fast.h, ddave_solver.h and ddave_fast.h.
+struct PlayTrace { uint32_t* trace; int* node; };
+struct PlayNoTrace {};
+template <class TRP> struct PlayTr { static constexpr bool on = false; };
+template <> struct PlayTr<PlayTrace> { static constexpr bool on = true; };
+PCGRL_D void play_tr_child(const PlayTrace& t, int child, int parent, int d) { t.trace[child] = (uint32_t)parent | ((uint32_t)d << 30); }
+PCGRL_D void play_tr_child(const PlayNoTrace&, int, int, int) {}
+PCGRL_D void play_tr_node(const PlayTrace& t, int idx) { *t.node = idx; }
+PCGRL_D void play_tr_node(const PlayNoTrace&, int) {}
+// (MdFastNode has a free word: md_search_fast keeps the same trace word there -- PlayTraceInNode, mdungeon_fast.h -- and stores nothing else)
+struct PlayTraceInNode { int* node; };
+template <> struct PlayTr<PlayTraceInNode> { static constexpr bool on = true; };
+PCGRL_D void play_tr_child(const PlayTraceInNode&, int, int, int) {}
+PCGRL_D void play_tr_node(const PlayTraceInNode& t, int idx) { *t.node = idx; }
+PCGRL_D uint32_t play_tr_pad(const PlayTraceInNode&, int parent, int d) { return (uint32_t)parent | ((uint32_t)d << 30); }
+PCGRL_D uint32_t play_tr_pad(const PlayTrace&, int, int) { return 0u; }
+PCGRL_D uint32_t play_tr_pad(const PlayNoTrace&, int, int) { return 0u; }
+// Node.getActions (engine.py:43-49) from a traced search's array: move i of the `depth` moves that lead to pool node `node` goes to
+// out[i] for i < max_len; nothing is written outside out[0 .. min(depth, max_len)).  `cap`: the array's words (an index beyond it
+// ends the walk: it cannot come from a search that filed its children there).
+PCGRL_D void play_walk_back(const uint32_t* trace, int cap, int node, int depth, int8_t* out, int max_len) {
+    for (int i = depth - 1; i >= 0; i--) {
+        if ((unsigned)node >= (unsigned)cap) break;
+        const uint32_t t = trace[node];
+        if (i < max_len) out[i] = (int8_t)(t >> 30);
+        node = (int)(t & 0x3FFFFFFFu);
+    }
+}
+
 // One search (one lane).  k < 0: BFSAgent, else AStarAgent with integer weight k in {2,1,0}.  `w` is the node
 // workspace (LDS on the device).  On return `w` holds the returned node (winner, or best node) and the function
 // value is the win flag; out_exhausted: the queue ran empty without a win and without reaching the cap.
@@ -113,9 +150,9 @@ PCGRL_D void md_store(MdNode* p, const MdRaw& r) {
 // The node that will be popped next is fetched from the pool one iteration ahead whenever it is already known (BFS:
 // the next queue entry; A*: the heap top after the repair), which takes the global-memory latency of the pop off the
 // serial chain.
-template <class HP, class TP, class Hook>
+template <class HP, class TP, class Hook, class TRP = PlayNoTrace>
 PCGRL_D bool md_search(const MdLevel& L, MdNode* pool, HP heap, TP table, int table_mask, MdNode& w, const MdNode& root, int k,
-                       int power, int& out_iters, bool& out_exhausted, Hook hook) {
+                       int power, int& out_iters, bool& out_exhausted, Hook hook, TRP trp = TRP()) {
     int npool = 0, head = 0, heapn = 0, iterations = 0, best = -1, best_h = 0, best_depth = 0;
     md_copy(pool, &root);
     npool = 1;
@@ -177,6 +214,7 @@ PCGRL_D bool md_search(const MdLevel& L, MdNode* pool, HP heap, TP table, int ta
             w.player = (uint8_t)np; w.health = (uint8_t)health; w.treasures = (uint8_t)tr;
             w.h = (int16_t)md_heuristic(L, np, health, tr);
             md_copy(pool + npool, &w);
+            play_tr_child(trp, npool, cur, d);
             if (k >= 0) {
                 heap[heapn] = ((uint32_t)(2 * w.h + k * w.depth + MD_PRIO_BIAS) << 16) | (uint32_t)npool;
                 heapn++;
@@ -187,6 +225,7 @@ PCGRL_D bool md_search(const MdLevel& L, MdNode* pool, HP heap, TP table, int ta
         }
     }
     if (!win) result = best < 0 ? 0 : best;
+    play_tr_node(trp, result);
     md_copy(&w, pool + result);
     out_iters = iterations;
     out_exhausted = !win && !aborted && !(k >= 0 ? heapn > 0 : head < npool);

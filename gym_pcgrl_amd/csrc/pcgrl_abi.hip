@@ -85,6 +85,7 @@
 #include "kernels_search_async.h"
 #include "kernels_evaluate.h"
 #include "kernels_solution.h"
+#include "kernels_playthrough.h"
 #include "search_big.h"
 #include "kernels_search_big.h"
 #if PCGRL_IN_PART(PART_CORE)
@@ -262,6 +263,8 @@ static size_t sok_pool_bytes(const pcgrl_config* c) {           // (rounded to w
         nodes = (SMB_MAX_WAVES * smb_wave_arena_bytes(c->solver_power) + sizeof(SokNode) - 1) / sizeof(SokNode);
     return align_up(nodes * sizeof(SokNode), 256);
 }
+// pcgrl_get_playthrough: the trace words beside one block's pool, one per node the pool can hold in 40-byte nodes (rounded to 256 bytes)
+static int play_trace_words(const pcgrl_config* c) { return (int)(align_up(sok_pool_bytes(c) / sizeof(SokNode) * 4, 256) / 4); }
 static_assert(SS_SMALL_NODES >= 4 * SS_SMALL_POPS + 4, "a small-tier search pushes up to four nodes per pop");
 // rows of the champion component per environment (binary: the row-bitboard maps, and maps beyond 64 x 64 of up to 256 per side with at
 // most 32 768 environments -- see below): the incremental statistics path
@@ -628,6 +631,7 @@ PCGRL_LOCAL int launch_step_solver(pcgrl_env* h, const int32_t* actions, hipStre
 PCGRL_LOCAL int launch_get_stats(pcgrl_env* h, const uint8_t* maps, int count, int32_t* rows_out, int32_t* head, int32_t* jobs, hipStream_t st);
 PCGRL_LOCAL int launch_get_stats_search(pcgrl_env* h, const uint8_t* maps, int32_t* rows_out, int32_t* head, const int32_t* jobs, SokNode* pools, int blocks, hipStream_t st);
 PCGRL_LOCAL int launch_get_solution(pcgrl_env* h, const uint8_t* maps, int32_t* rows_out, const SolOut& out, int32_t* head, const int32_t* jobs, SokNode* pools, int blocks, hipStream_t st);
+PCGRL_LOCAL int launch_get_playthrough(pcgrl_env* h, const uint8_t* maps, int32_t* rows_out, const SolOut& out, int32_t* head, const int32_t* jobs, SokNode* pools, uint32_t* traces, int blocks, hipStream_t st);
 PCGRL_LOCAL int launch_search_async(pcgrl_env* h, int32_t* tickets, int list_a, int mode_a, int list_b, int mode_b, int parity, int rst_list, int clr, int budget, int resume, int small, hipStream_t st);
 // A launch with more than 64 KB of dynamic LDS needs the kernel's cap raised first.  That is a driver call (about a microsecond of
 // host time -- a fifth of what issuing a step costs), so it is made only when this process has not yet raised the cap of this kernel
@@ -1010,6 +1014,13 @@ PCGRL_LOCAL int launch_get_stats_search(pcgrl_env* h, const uint8_t* maps, int32
 // (kernels_solution.h: k_get_stats_search's shape with the traced sokoban searches)
 PCGRL_LOCAL int launch_get_solution(pcgrl_env* h, const uint8_t* maps, int32_t* rows_out, const SolOut& out, int32_t* head, const int32_t* jobs, SokNode* pools, int blocks, hipStream_t st) {
     return launch<k_get_solution<0>>(h, blocks, SS_THREADS, sok_lds_bytes(), st, h->P, search_devbufs(h), maps, rows_out, out, head, jobs, pools, search_pool_stride(h));
+}
+// (kernels_playthrough.h: the same shape with the traced mdungeon / ddave searches; a block's trace words are as many as its pool's nodes)
+PCGRL_LOCAL int launch_get_playthrough(pcgrl_env* h, const uint8_t* maps, int32_t* rows_out, const SolOut& out, int32_t* head, const int32_t* jobs, SokNode* pools, uint32_t* traces, int blocks, hipStream_t st) {
+    return with_prob<PCGRL_PROB_MDUNGEON, PCGRL_PROB_DDAVE>(h->P.prob, [&](auto prob) {
+        return launch<k_get_playthrough<prob()>>(h, blocks, SS_THREADS, sok_lds_bytes(), st, h->P, search_devbufs(h), maps, rows_out, out, head, jobs, pools,
+                                                 search_pool_stride(h), traces, play_trace_words(&h->cfg));
+    });
 }
 
 #endif  // PART_STEP_SOLVER
@@ -1726,6 +1737,48 @@ int pcgrl_get_solution(pcgrl_env* h, const uint8_t* maps, int32_t count, int32_t
     if (rc) return rc;
     const SolOut out = {moves_out, length_out, agent_out, max_len};
     return launch_get_solution(h, maps, rows, out, head, at<int32_t>(w, S.E.jobs), at<SokNode>(w, S.E.pools), S.E.blocks, st);
+}
+
+// ---- pcgrl_get_playthrough (kernels_playthrough.h): the play behind the mdungeon / ddave statistics ---------------------------------
+// The workspace, cut from one plan like pcgrl_get_solution's: pcgrl_get_stats' three regions, rows for a caller that wants none, and
+// per persistent block the trace words beside its node pool.
+struct PlayPlan { EvalPlan E; Region rows, traces; size_t total; };
+static PlayPlan play_plan(const pcgrl_config* c, int count) {
+    PlayPlan S = {};
+    S.E = eval_plan(c, count);
+    Bump b = {S.E.total};
+    S.rows = b.take(align_up((size_t)count * 8 * 4, 256));
+    S.traces = b.take((size_t)S.E.blocks * play_trace_words(c) * 4);
+    S.total = b.off;
+    return S;
+}
+size_t pcgrl_get_playthrough_bytes(const pcgrl_config* c, int32_t count, int32_t max_len) {
+    if (!c || (c->prob != PCGRL_MDUNGEON && c->prob != PCGRL_DDAVE) || max_len < 1 || pcgrl_get_stats_bytes(c, count) == 0) return 0;
+    pcgrl_config one = *c;
+    one.num_envs = 1;
+    return play_plan(&one, count).total;
+}
+int pcgrl_get_playthrough(pcgrl_env* h, const uint8_t* maps, int32_t count, int32_t max_len, int8_t* moves_out, int32_t* length_out, int8_t* agent_out,
+                          int32_t* rows_out, void* work, size_t work_bytes, void* stream) {
+    if (!h || !h->bound) return PCGRL_ESTATE;
+    if (!maps || !moves_out || !length_out || !work || count < 1 || max_len < 1 || ((uintptr_t)work & 255) != 0) return PCGRL_EINVAL;
+    const size_t need = pcgrl_get_playthrough_bytes(&h->cfg, count, max_len);
+    if (need == 0 || work_bytes < need) return PCGRL_EINVAL;
+    DeviceGuard guard(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    const PlayPlan S = play_plan(&h->cfg, count);
+    uint8_t* w = (uint8_t*)work;
+    int32_t* head = at<int32_t>(w, S.E.head);
+    int32_t* rows = rows_out ? rows_out : at<int32_t>(w, S.rows);
+    HIPCHK(hipMemsetAsync(head, 0, S.E.head.bytes, st));
+    // what a level keeps when its planner does not run: an all -1 row, length 0, agent -2 (k_get_playthrough: -1 when nobody won)
+    HIPCHK(hipMemsetAsync(moves_out, 0xFF, (size_t)count * (size_t)max_len, st));
+    HIPCHK(hipMemsetAsync(length_out, 0, (size_t)count * 4, st));
+    if (agent_out) { HIPCHK(hipMemsetAsync(agent_out, 0xFE, (size_t)count, st)); }
+    int rc = launch_get_stats(h, maps, count, rows, head, at<int32_t>(w, S.E.jobs), st);
+    if (rc) return rc;
+    const SolOut out = {moves_out, length_out, agent_out, max_len};
+    return launch_get_playthrough(h, maps, rows, out, head, at<int32_t>(w, S.E.jobs), at<SokNode>(w, S.E.pools), at<uint32_t>(w, S.traces), S.E.blocks, st);
 }
 
 }  // extern "C"

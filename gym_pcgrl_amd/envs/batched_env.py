@@ -76,6 +76,25 @@ class Solutions:
         return self.length > self.moves.shape[1]
 
 
+class Playthroughs:
+    """What BatchedPcgrlEnv.playthrough() returns: `moves` int8 [M, max_len] (mdungeon 0..3 = left, right, up, down; ddave 0..3 =
+    stay, left, right, jump; -1 beyond the play), `length` int32 [M] (the depth of the node the statistics come from, also beyond
+    max_len), `agent` int8 [M] (-2 the planner did not run, -1 no agent won, 0..3 = A*(1), A*(0.5), A*(0), BFS), `rows` / `stats` as
+    in an Evaluation; `truncated` bool [M]: the row holds only a prefix; `won` bool [M]: an agent won."""
+    __slots__ = ("moves", "length", "agent", "rows", "stats")
+
+    def __init__(self, moves, length, agent, rows, stats):
+        self.moves, self.length, self.agent, self.rows, self.stats = moves, length, agent, rows, stats
+
+    @property
+    def truncated(self):
+        return self.length > self.moves.shape[1]
+
+    @property
+    def won(self):
+        return self.agent >= 0
+
+
 class BatchedPcgrlEnv:
     metadata = {"render.modes": []}
 
@@ -738,7 +757,8 @@ class BatchedPcgrlEnv:
         the library has no one-call form: there is no scratch-environment route for the moves."""
         torch = self._torch
         if self._prob.name != "sokoban":
-            raise NotImplementedError("solve(): only sokoban's get_stats returns its planner's moves (problem %r keeps at most their number)" % (self._prob.name,))
+            raise NotImplementedError("solve(): only sokoban's get_stats returns its planner's moves (problem %r keeps at most their number%s)"
+                                      % (self._prob.name, "; playthrough() returns the play behind its statistics" if self._prob.name in ("mdungeon", "ddave") else ""))
         if maps is None:
             if self._handle is None or not self._was_reset or self._needs_reset:
                 raise RuntimeError("solve() without maps reads the environment's current levels: call reset() first")
@@ -780,6 +800,64 @@ class BatchedPcgrlEnv:
                                                 C.c_void_p(length.data_ptr()), C.c_void_p(agent.data_ptr()), C.c_void_p(rows.data_ptr()),
                                                 C.c_void_p(self._eval_work.data_ptr()), self._eval_work.numel(), self._stream()), "pcgrl_get_solution")
         return Solutions(moves, length, agent, rows, self._prob.decode_rows(rows))
+
+    # ---- the play that _run_game scores, mdungeon and ddave (pcgrl_get_playthrough)
+    def playthrough(self, maps=None, max_len=None):
+        """The play behind the planner's statistics for `maps` -- array-like uint8 [M, H, W] as for evaluate(); None: this
+        environment's current levels (after a reset(); the handle's own map buffer is read in place) -- with the parameters in
+        force: the moves of the first agent of _run_game that wins, or, when none wins, the moves that lead to the BFS agent's best
+        node -- the state `col-*` / `num-jumps` / `dist-win` describe.  `max_len`: columns of the move rows, by default
+        min(solver_power, 255).  Returns Playthroughs (moves, length, agent, rows, stats), all on the device.  `length` is not
+        `sol-length`: with agent == -1 the row holds the BFS agent's best node's moves while stats["sol-length"] is 0.
+        A pure function like evaluate(): episodes, random streams and pending asynchronous searches are not touched, a tile id >=
+        get_num_tiles() is clamped on the way and reported by check_status(), nothing is waited for; the workspace is evaluate()'s
+        (the same one-stream rule).  NotImplementedError for the other problems (sokoban: solve()) and where the library has no
+        one-call form: there is no scratch-environment route for the moves."""
+        torch = self._torch
+        if self._prob.name not in ("mdungeon", "ddave"):
+            raise NotImplementedError("playthrough(): the plays of mdungeon and ddave only, not problem %r%s"
+                                      % (self._prob.name, " (solve() returns sokoban's solution)" if self._prob.name == "sokoban" else ""))
+        if maps is None:
+            if self._handle is None or not self._was_reset or self._needs_reset:
+                raise RuntimeError("playthrough() without maps reads the environment's current levels: call reset() first")
+        dims = (self._prob._width, self._prob._height)
+        if self._handle is None or (not self._was_reset and (self._realloc or dims != self._alloc_dims)):
+            self._allocate()               # (as in evaluate(): bound, not reset)
+            self._realloc = False
+        if self._realloc:
+            raise NotImplementedError("playthrough(): an adjust_param() that this handle could not take in place waits for the next reset(); "
+                                      "the handle still plans with the old parameters")
+        w, h = self._alloc_dims
+        if maps is None:
+            m = self._bufs["map"]
+        else:
+            m = maps if torch.is_tensor(maps) else torch.as_tensor(np.asarray(maps))
+            if m.dim() != 3:
+                raise ValueError("playthrough(): maps must be [M, H, W], got shape %s" % (tuple(m.shape),))
+            if tuple(m.shape[1:]) != (h, w) or m.shape[0] < 1:
+                raise ValueError("playthrough(): maps of shape %s for an environment of %d rows x %d columns (at least one map)" % (tuple(m.shape), h, w))
+            m = m.to(device=self.device, dtype=torch.uint8).contiguous()
+        M = int(m.shape[0])
+        power = int(self._prob._solver_power)
+        max_len = min(power, 255) if max_len is None else int(max_len)
+        if max_len < 1:
+            raise ValueError("playthrough(): max_len must be at least 1, got %d" % max_len)
+        cfg = self._config(self._alloc_dims)
+        need = int(self._lib.pcgrl_get_playthrough_bytes(C.byref(cfg), M, max_len))
+        if not need:
+            raise NotImplementedError("playthrough(): no one-call form for this configuration (levels of %d x %d = %d bordered cells, solver_power %d): "
+                                      "the traced searches are the ones that run in LDS -- at most 256 bordered cells and solver_power <= 5000"
+                                      % (h + 2, w + 2, (h + 2) * (w + 2), power))
+        moves = torch.empty((M, max_len), dtype=torch.int8, device=self.device)
+        length = torch.empty((M,), dtype=torch.int32, device=self.device)
+        agent = torch.empty((M,), dtype=torch.int8, device=self.device)
+        rows = torch.empty((M, 8), dtype=torch.int32, device=self.device)
+        if self._eval_work is None or self._eval_work.numel() < need:
+            self._eval_work = torch.empty((need,), dtype=torch.uint8, device=self.device)
+        _lib.check(self._lib.pcgrl_get_playthrough(self._handle, C.c_void_p(m.data_ptr()), M, max_len, C.c_void_p(moves.data_ptr()),
+                                                   C.c_void_p(length.data_ptr()), C.c_void_p(agent.data_ptr()), C.c_void_p(rows.data_ptr()),
+                                                   C.c_void_p(self._eval_work.data_ptr()), self._eval_work.numel(), self._stream()), "pcgrl_get_playthrough")
+        return Playthroughs(moves, length, agent, rows, self._prob.decode_rows(rows))
 
     def _evaluate_by_set_maps(self, m, rows, chunk):
         """evaluate() where pcgrl_get_stats_bytes is 0: a scratch environment of this problem (wide representation, the same

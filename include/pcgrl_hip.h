@@ -18,6 +18,7 @@
  *   pcgrl_set_maps                   direct assignment of Representation._map (tests, curriculum loaders)
  *   pcgrl_get_stats / pcgrl_get_reward   Problem.get_stats / get_reward / get_episode_over called on any level, outside an episode
  *   pcgrl_get_solution               SokobanProblem.get_stats(map)["solution"] sokoban_prob.py:133-145: the planner's moves
+ *   pcgrl_get_playthrough            the moves of the play _run_game scores, mdungeon_prob.py:100-138 / ddave_prob.py:92-127
  *
  * Conventions: plain pointers and sizes only; every function returns 0 on success or a negative
  * PCGRL_E* code (no exceptions cross the ABI); all device buffers are OWNED BY THE CALLER (hipMalloc,
@@ -46,7 +47,9 @@ extern "C" {
  *     Still 15: + pcgrl_render_desc / pcgrl_render -- additive in the same way; a caller detects it by the symbol pcgrl_render.
  *     Still 15: + pcgrl_get_stats_bytes / pcgrl_get_stats / pcgrl_get_reward -- additive in the same way (three entry points, no struct);
  *     a caller detects them by the symbol pcgrl_get_stats.
- *     Still 15: + pcgrl_get_solution_bytes / pcgrl_get_solution -- additive in the same way; detected by the symbol pcgrl_get_solution. */
+ *     Still 15: + pcgrl_get_solution_bytes / pcgrl_get_solution -- additive in the same way; detected by the symbol pcgrl_get_solution.
+ *     Still 15: + pcgrl_get_playthrough_bytes / pcgrl_get_playthrough -- additive in the same way; detected by the symbol
+ *     pcgrl_get_playthrough. */
 #define PCGRL_ABI_VERSION 15
 #define PCGRL_OK 0
 #define PCGRL_EINVAL (-1)   /* bad argument / unsupported configuration */
@@ -344,6 +347,30 @@ size_t pcgrl_get_solution_bytes(const pcgrl_config* cfg, int32_t count, int32_t 
 int    pcgrl_get_solution(pcgrl_env* env, const uint8_t* maps, int32_t count, int32_t max_len,
                           int8_t* moves_out, int32_t* length_out, int8_t* agent_out, int32_t* rows_out,
                           void* work, size_t work_bytes, void* stream);
+/* The play behind the MiniDungeons and Dangerous Dave statistics.  _run_game (mdungeon_prob.py:100-138, ddave_prob.py:92-127) runs
+ * AStarAgent with balance 1, 0.5, 0 and then BFSAgent; each getSolution returns node.getActions() (mdungeon/engine.py:43-49) of the
+ * node it ends on, and _run_game keeps only len(sol) and the game status of that node's state.  This entry returns the moves: those of
+ * the first agent whose node wins, or -- when no agent wins -- those that lead to the BFS agent's best node, the state the `col-*` /
+ * `num-jumps` / `dist-win` columns are taken from.  Same contract as pcgrl_get_solution: a bound handle, no reset needed, no episode
+ * state read or written, of the handle only the sticky status word written, asynchronous.
+ *   maps        DEVICE u8 [count,H,W], read only.
+ *   max_len     columns of a row of moves_out, >= 1.
+ *   moves_out   DEVICE i8 [count,max_len]: move i as the index into the engine's `directions` -- mdungeon 0..3 = left, right, up,
+ *               down; ddave 0..3 = stay, left, right, jump -- for i < min(length, max_len); -1 from there to the end of the row.
+ *   length_out  DEVICE i32 [count]: the depth of the returned node, also when it is > max_len (the row then holds the first max_len
+ *               moves).  NOT `sol-length`: when no agent won the row holds the moves to the BFS agent's best node and sol-length is 0.
+ *   agent_out   DEVICE i8 [count] or NULL: -2 = the planner did not run (length 0, an all -1 row), -1 = no agent won, else the agent
+ *               of _run_game that won: 0..2 = AStarAgent with balance 1, 0.5, 0, 3 = BFSAgent.
+ *   rows_out    DEVICE i32 [count,8] or NULL: exactly what pcgrl_get_stats writes for these maps.
+ *   work        DEVICE, 256-byte aligned, at least pcgrl_get_playthrough_bytes(cfg, count, max_len) bytes; the call's own.
+ *   PCGRL_EINVAL: a NULL maps / moves_out / length_out / work, count < 1, max_len < 1, work not 256-byte aligned or too small, or a
+ *   configuration for which pcgrl_get_playthrough_bytes is 0.
+ * pcgrl_get_playthrough_bytes: from the configuration alone.  Non-zero exactly for mdungeon and ddave where pcgrl_get_stats_bytes is
+ *   non-zero (at most 256 bordered cells, the searches that run in LDS) and max_len >= 1; then >= 256. */
+size_t pcgrl_get_playthrough_bytes(const pcgrl_config* cfg, int32_t count, int32_t max_len);
+int    pcgrl_get_playthrough(pcgrl_env* env, const uint8_t* maps, int32_t count, int32_t max_len,
+                             int8_t* moves_out, int32_t* length_out, int8_t* agent_out, int32_t* rows_out,
+                             void* work, size_t work_bytes, void* stream);
 /* ActionMap.step for the wide representation (wrappers.py:139-154): flat DEVICE i32 [N] index into
  * (H, W, tiles) -> xyv DEVICE i32 [N,3] = (x, y, tile), the action pcgrl_step takes. */
 int pcgrl_action_map(pcgrl_env* env, const int32_t* flat, int32_t* xyv, void* stream);

@@ -1,0 +1,396 @@
+"""BatchedPcgrlEnv.playthrough() / pcgrl_get_playthrough on the GPU: the play behind the mdungeon / ddave planner statistics, bit for
+bit against the reference's agents (tests/golden/playthroughs.npz), replayed by the games' rules (replay_mdungeon, replay_ddave), and
+without a trace on the handle that computed it.  Every fixture case uses a handle of THREE environments and another number of levels."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+HERE = os.path.dirname(os.path.abspath(__file__))
+G = os.path.join(HERE, "golden")
+FILES = {
+    "mdungeon": ["1x6_p5000", "5x5_p5000", "6x9_p300", "7x11_p5000", "11x7_p1200", "11x7_p5000", "14x14_p5000"],
+    "ddave": ["1x5_p5000", "2x6_p5000", "5x5_p5000", "6x9_p150", "7x11_p600", "7x11_p5000", "11x7_p5000", "14x14_p5000"],
+}
+CASES = [(p, f) for p in ("mdungeon", "ddave") for f in FILES[p]]
+N_ENVS = 3
+NHAND = 3
+CSRC = os.path.join(os.path.dirname(HERE), "gym_pcgrl_amd", "csrc")
+SMALL_POPS = int(re.search(r"#define SS_SMALL_POPS (\d+)", open(os.path.join(CSRC, "kernels_step_solver.h")).read()).group(1))
+# columns of a decoded statistics row (the stats fixtures' keys): dist-win, sol-length, and what the replays count
+DIST, SOLLEN = 9, 10
+
+
+def _torch():
+    import torch
+    assert torch.cuda.is_available(), "these tests need the MI355X"
+    return torch
+
+
+def _make(prob, h, w, power=None, tuning=None, rep="wide", seed=1000, num_envs=N_ENVS):
+    from gym_pcgrl_amd.envs import BatchedPcgrlEnv
+    env = BatchedPcgrlEnv(prob=prob, rep=rep, num_envs=num_envs, seed=seed, tuning=tuning)
+    kw = dict(width=w, height=h)
+    if power is not None:
+        kw["solver_power"] = int(power)
+    env.adjust_param(**kw)
+    return env
+
+
+_CACHE = {}
+
+
+def _fixture(prob, name):
+    """(maps, stats, agents, power, moves, length) of one file: loaded once; the tests copy what they change."""
+    if (prob, name) not in _CACHE:
+        d = np.load(os.path.join(G, "stats_%s_%s.npz" % (prob, name)))
+        s = np.load(os.path.join(G, "playthroughs.npz"))
+        _CACHE[prob, name] = (d["maps"], d["stats"], d["agents"], int(d["solver_power"]), s["moves_%s_%s" % (prob, name)], s["length_%s_%s" % (prob, name)])
+    return _CACHE[prob, name]
+
+
+def _padded(want, max_len):
+    out = np.full((want.shape[0], max_len), -1, np.int8)
+    k = min(max_len, want.shape[1])
+    out[:, :k] = want[:, :k]
+    return out
+
+
+def _check(env, maps, stats, agents, want, wlen, max_len=None):
+    """playthrough(maps) against the fixture rows of the same levels; returns the Playthroughs."""
+    torch = _torch()
+    pt = env.playthrough(maps, max_len=max_len)
+    M, ml = maps.shape[0], pt.moves.shape[1]
+    assert pt.moves.dtype == torch.int8 and pt.length.dtype == torch.int32 and pt.agent.dtype == torch.int8
+    assert tuple(pt.moves.shape) == (M, ml) and tuple(pt.length.shape) == (M,) and tuple(pt.agent.shape) == (M,) and tuple(pt.rows.shape) == (M, 8)
+    moves, length, agent = pt.moves.cpu().numpy(), pt.length.cpu().numpy(), pt.agent.cpu().numpy()
+    assert env.check_status() == 0
+    assert np.array_equal(length, wlen), np.nonzero(length != wlen)[0][:5]
+    assert np.array_equal(agent, agents[:, 4]), np.nonzero(agent != agents[:, 4])[0][:5]
+    exp = _padded(want, ml)
+    bad = np.nonzero((moves != exp).any(1))[0]
+    assert bad.size == 0, (bad[:5], moves[bad[:1]], exp[bad[:1]])
+    assert np.array_equal(pt.truncated.cpu().numpy(), wlen > ml) and np.array_equal(pt.won.cpu().numpy(), agents[:, 4] >= 0)
+    assert np.array_equal(pt.stats.cpu().numpy().astype(np.int64), stats)
+    return pt
+
+
+def _replay_all(prob, maps, moves, length, agent, stats):
+    """What the issue asks of every level, with no fixture of moves: a level whose planner ran is replayed on the host."""
+    from gym_pcgrl_amd import replay_ddave, replay_mdungeon
+    ran = 0
+    for i in range(maps.shape[0]):
+        if agent[i] == -2:
+            assert length[i] == 0 and (moves[i] == -1).all(), i
+            continue
+        assert length[i] <= moves.shape[1] and int((moves[i] >= 0).sum()) == length[i] and (moves[i, :length[i]] >= 0).all(), i
+        st = stats[i]
+        if prob == "mdungeon":
+            r = replay_mdungeon(maps[i], moves[i])
+            assert (r.potions[-1], r.treasures[-1], r.enemies[-1]) == (st[6], st[7], st[8]), (i, st)
+            short = replay_mdungeon(maps[i], moves[i, :length[i] - 1]) if length[i] else None
+        else:
+            r = replay_ddave(maps[i], moves[i])
+            assert (r.jumps[-1], r.diamonds[-1]) == (st[7], st[8]), (i, st)
+            short = replay_ddave(maps[i], moves[i, :length[i] - 1]) if length[i] else None
+        assert r.player.shape[0] == length[i] + 1 and not r.dead, i
+        assert (agent[i] >= 0) == r.won, (i, agent[i])
+        if agent[i] >= 0:
+            assert length[i] == st[SOLLEN] > 0 and st[DIST] == 0 and not short.won, (i, st)
+        else:
+            assert st[SOLLEN] == 0 and r.heuristic == st[DIST], (i, st, r.heuristic)
+        ran += 1
+    return ran
+
+
+# ------------------------------------------------------------------ every fixture level
+@pytest.mark.parametrize("tuning", [None, {"sok_generic": 1}], ids=["default", "generic"])
+@pytest.mark.parametrize("prob,name", CASES, ids=["%s_%s" % c for c in CASES])
+def test_fixture_plays(prob, name, tuning):
+    torch = _torch()
+    maps, stats, agents, power, want, wlen = _fixture(prob, name)
+    assert maps.shape[0] != N_ENVS and maps.shape[0] <= 422
+    env = _make(prob, maps.shape[1], maps.shape[2], power, tuning=tuning)
+    pt = _check(env, maps, stats, agents, want, wlen, max_len=want.shape[1])
+    assert torch.equal(pt.rows, env.evaluate(maps).rows)
+    assert _replay_all(prob, maps, pt.moves.cpu().numpy(), wlen, agents[:, 4], stats) == int((agents[:, 4] > -2).sum()) > 0
+    env.close()
+
+
+def test_fixture_reaches_all_three_ends_of_a_try():
+    """What the sizes are for: games that are final in the small region (6x9_p150: the power is below SS_SMALL_POPS), games the
+    reduced limit stopped and wavefront 0 redid (an agent popped more than SS_SMALL_POPS), and games the real cap stopped."""
+    for prob, name in (("ddave", "6x9_p150"),):
+        assert _fixture(prob, name)[3] < SMALL_POPS
+    redo = capped = 0
+    for prob, name in (("mdungeon", "6x9_p300"), ("ddave", "7x11_p600"), ("mdungeon", "11x7_p1200")):
+        _, _, agents, power, _, _ = _fixture(prob, name)
+        assert power > SMALL_POPS
+        redo += int((agents[:, :4].max(1) > SMALL_POPS).sum())
+        capped += int((agents[:, :4].max(1) >= power).sum())
+    assert redo > 0 and capped > 0
+    # (no ddave level of these files is won by BFS; its no-win rows walk the BFS agent's pool all the same)
+    assert all(int((_fixture("ddave", f)[2][:, 4] == 3).sum()) == 0 for f in FILES["ddave"])
+
+
+@pytest.mark.parametrize("prob", ["mdungeon", "ddave"])
+def test_hand_made_levels_reach_the_generic_search(prob):
+    _torch()
+    limit = int(re.search(r"#define %s (\d+)" % ("MDF_MAXI" if prob == "mdungeon" else "DDF_MAXD"),
+                          open(os.path.join(CSRC, "mdungeon_fast.h" if prob == "mdungeon" else "ddave_fast.h")).read()).group(1))
+    s = np.load(os.path.join(G, "playthroughs.npz"))
+    won = []
+    for i in range(NHAND):
+        m, power = s["hand_%s_map_%d" % (prob, i)], int(s["hand_%s_power" % prob][i])
+        assert int((m >= 4).sum() if prob == "mdungeon" else (m == 4).sum()) > limit          # more than the compact search takes
+        st, ag = s["hand_%s_stats" % prob][i:i + 1], s["hand_%s_agents" % prob][i:i + 1]
+        want, wlen = s["hand_%s_moves" % prob][i:i + 1], s["hand_%s_length" % prob][i:i + 1]
+        env = _make(prob, m.shape[0], m.shape[1], power)                                        # default tuning
+        pt = _check(env, m[None], st, ag, want, wlen, max_len=want.shape[1])
+        assert _replay_all(prob, m[None], pt.moves.cpu().numpy(), wlen, ag[:, 4], st) == 1
+        won.append(int(ag[0, 4]))
+        env.close()
+    assert max(won) >= 0 and min(won) == -1
+
+
+@pytest.mark.parametrize("prob", ["mdungeon", "ddave"])
+def test_chunk_and_pool_reuse(prob):
+    """EVAL_CHUNK = 64 jobs a ticket, one pool and one set of trace words per persistent block: the 5x5 levels stacked to counts around
+    the chunk and far beyond it, in shuffled order -- every level's result is the same as alone in its file's order."""
+    _torch()
+    maps, stats, agents, power, want, wlen = _fixture(prob, "5x5_p5000")
+    env = _make(prob, 5, 5, power)
+    rs = np.random.RandomState(5)
+    for count in (1, 63, 64, 65, 129, 1000):
+        order = np.resize(rs.permutation(maps.shape[0]), count)
+        if count == 1:
+            order = np.nonzero(wlen > 0)[0][:1]
+        else:
+            rs.shuffle(order)
+            assert (agents[order, 4] == -2).any() and (agents[order, 4] == -1).any() and (agents[order, 4] >= 0).any()
+        pt = _check(env, maps[order], stats[order], agents[order], want[order], wlen[order])
+        assert pt.moves.shape[1] == 255                                                 # the default: min(solver_power, 255)
+    env.close()
+
+
+# ------------------------------------------------------------------ without a fixture
+def _random_levels(prob, count, h, w, seed):
+    """Seeded random levels with exactly one player and one exit (ddave: and one key) on a sparse floor."""
+    rs = np.random.RandomState(seed)
+    if prob == "mdungeon":
+        m = rs.choice(8, size=(count, h, w), p=[0.62, 0.2, 0, 0, 0.04, 0.06, 0.05, 0.03]).astype(np.uint8)
+        singles = (2, 3)
+    else:
+        m = rs.choice(7, size=(count, h, w), p=[0.68, 0.2, 0, 0, 0.06, 0, 0.06]).astype(np.uint8)
+        singles = (2, 3, 5)
+    for i in range(count):
+        cells = rs.choice(h * w, size=len(singles), replace=False)
+        for c, t in zip(cells, singles):
+            m[i, c // w, c % w] = t
+    return m
+
+
+@pytest.mark.parametrize("prob", ["mdungeon", "ddave"])
+def test_replayed_without_a_fixture(prob):
+    """A 4096-environment handle's own levels after reset() (maps=None), and 4096 seeded random levels of the same size: every play is
+    checked by the game's rules on the host against the statistics row it belongs to."""
+    torch = _torch()
+    from gym_pcgrl_amd.envs import BatchedPcgrlEnv
+    env = BatchedPcgrlEnv(prob=prob, rep="narrow", num_envs=4096, seed=31)
+    env.adjust_param(width=11, height=7)
+    env.reset()
+    own = env.playthrough()
+    assert own.moves.shape == (4096, 255) and torch.equal(own.rows, env.evaluate(env._bufs["map"]).rows)
+    maps = env._bufs["map"].cpu().numpy()
+    ran_own = _replay_all(prob, maps, own.moves.cpu().numpy(), own.length.cpu().numpy(), own.agent.cpu().numpy(), own.stats.cpu().numpy().astype(np.int64))
+    print("%s: planner ran on %d of the handle's 4096 levels" % (prob, ran_own))
+    levels = _random_levels(prob, 4096, 7, 11, 77)
+    pt = env.playthrough(levels)
+    assert torch.equal(pt.rows, env.evaluate(levels).rows)
+    agent = pt.agent.cpu().numpy()
+    ran = _replay_all(prob, levels, pt.moves.cpu().numpy(), pt.length.cpu().numpy(), agent, pt.stats.cpu().numpy().astype(np.int64))
+    print("%s: planner ran on %d of 4096 random levels, %d won, %d not" % (prob, ran, int((agent >= 0).sum()), int((agent == -1).sum())))
+    assert ran > 100 and (agent >= 0).any() and (agent == -1).any() and (agent == -2).any()
+    assert env.check_status() == 0
+    env.close()
+
+
+# ------------------------------------------------------------------ the handle is left alone
+@pytest.mark.parametrize("prob", ["mdungeon", "ddave"])
+def test_handle_in_the_middle_of_its_episodes(prob):
+    torch = _torch()
+    from gym_pcgrl_amd.envs import BatchedPcgrlEnv
+    maps, stats, agents, power, want, wlen = _fixture(prob, "7x11_p5000")
+    env, twin = (BatchedPcgrlEnv(prob=prob, rep="narrow", num_envs=N_ENVS, seed=77) for _ in range(2))
+    nt = env.get_num_tiles()
+    acts = np.random.RandomState(3).randint(0, nt + 1, size=(40, N_ENVS)).astype(np.int32)
+    with pytest.raises(RuntimeError):
+        env.playthrough()                                         # its own levels: only after a reset()
+    for e in (env, twin):
+        e.adjust_param(width=11, height=7)
+        e.reset()
+        for t in range(20):
+            e.step(acts[t])
+    before = env.state_dict()
+    bufs = {k: v.clone() for k, v in env._bufs.items() if v is not None}      # every device buffer of the handle, scratch included
+    own = env.playthrough()                                       # the handle's own map buffer, read in place
+    again = env.playthrough(env._bufs["map"].clone())
+    for a, b in ((own.moves, again.moves), (own.length, again.length), (own.agent, again.agent), (own.rows, again.rows)):
+        assert torch.equal(a, b)
+    assert own.moves.shape == (N_ENVS, 255)
+    _check(env, maps[:40], stats[:40], agents[:40], want[:40], wlen[:40])       # ... and other levels in between
+    torch.cuda.synchronize()
+    for k, v in bufs.items():
+        assert torch.equal(env._bufs[k], v), k
+    after = env.state_dict()
+    assert before.keys() == after.keys()
+    for k in before:
+        assert (before[k] is None and after[k] is None) or torch.equal(before[k], after[k]), k
+    for t in range(20, 40):                                       # the episodes go on as if nothing had happened
+        x, y = env.step(acts[t]), twin.step(acts[t])
+        if t % 5 == 0:
+            env.playthrough()
+        assert torch.equal(x[0]["map"], y[0]["map"]) and torch.equal(x[1], y[1]) and torch.equal(x[2], y[2]), t
+    assert env.check_status() == 0
+    for e in (env, twin):
+        e.close()
+
+
+@pytest.mark.parametrize("prob", ["mdungeon", "ddave"])
+def test_pending_searches_are_left_alone(prob):
+    """Twin environments take a tick with a one-pop budget, which leaves their searches suspended; one of them calls playthrough()
+    then: its pending flags and counters are what they were, the suspended steps complete, and both step identically for 20 steps."""
+    torch = _torch()
+    maps, stats, agents, power, want, wlen = _fixture(prob, "7x11_p5000")
+    # the levels whose planner pops most among those with a wall cell: turning it into floor keeps the planner running
+    heavy = [i for i in np.argsort(-agents[:, :4].sum(1)) if (maps[i] == 1).any()][:N_ENVS]
+    assert (agents[heavy, :4].sum(1) > 40).all()
+    first = np.array([[int(np.nonzero(maps[i] == 1)[1][0]), int(np.nonzero(maps[i] == 1)[0][0]), 0] for i in heavy], np.int32)      # (x, y, empty)
+    envs = [_make(prob, 7, 11, power, seed=11) for _ in range(2)]
+    env, twin = envs
+    rs = np.random.RandomState(9)
+    acts = np.stack([rs.randint(0, 11, size=(20, N_ENVS)), rs.randint(0, 7, size=(20, N_ENVS)), rs.randint(0, 4, size=(20, N_ENVS))], -1).astype(np.int32)
+    for e in envs:
+        assert e.enable_async(nslots=8)
+        e.reset()
+        e.set_maps(maps[heavy])
+    outs = [e.tick(first, pop_budget=1) for e in envs]             # one pop: every search is suspended
+    before_p, before_c = outs[0][4].clone(), env._async["counters"].clone()
+    pt = env.playthrough(maps[:40])                                 # ... with the tick's searches in flight
+    torch.cuda.synchronize()
+    assert before_p.any() and env.async_counters()["suspended"] > 0
+    assert np.array_equal(pt.moves.cpu().numpy(), _padded(want[:40], 255)) and np.array_equal(pt.length.cpu().numpy(), wlen[:40])
+    assert torch.equal(env._async["pending"], before_p) and torch.equal(env._async["counters"], before_c)
+    for e in envs:
+        e.flush()                                                   # the suspended steps complete
+    for k in ("map", "stats", "reward", "done"):
+        assert torch.equal(env._bufs[k], twin._bufs[k]), k
+    for t in range(20):
+        x, y = env.step(acts[t]), twin.step(acts[t])
+        assert torch.equal(x[0]["map"], y[0]["map"]) and torch.equal(x[1], y[1]) and torch.equal(x[2], y[2]), t
+    assert env.check_status() == 0
+    for e in envs:
+        e.close()
+
+
+# ------------------------------------------------------------------ the C entry point
+@pytest.mark.parametrize("max_len", [1, 4, 56])
+def test_raw_abi_row_bounds_and_refusals(max_len):
+    """Through the C entry point nothing is written outside the four outputs -- guard elements of a known value on both sides stay
+    intact --, the optional outputs may be NULL, a short row holds the prefix and the full length, and a misaligned or short
+    workspace is refused."""
+    torch = _torch()
+    maps, stats, agents, power, want, wlen = _fixture("mdungeon", "11x7_p5000")
+    assert int(wlen.max()) == 56
+    env = _make("mdungeon", 11, 7, power)
+    pt = _check(env, maps, stats, agents, want, wlen, max_len=max_len)
+    assert pt.truncated.any().item() == (max_len < 56)
+    M, guard = maps.shape[0], 64
+    dev = env.device
+    mv = torch.full((guard + M * max_len + guard,), 0x5A, dtype=torch.int8, device=dev)
+    ln = torch.full((guard + M + guard,), 0x5A5A5A5A, dtype=torch.int32, device=dev)
+    ag = torch.full((guard + M + guard,), 0x5A, dtype=torch.int8, device=dev)
+    rw = torch.full((guard + M * 8 + guard,), 0x5A5A5A5A, dtype=torch.int32, device=dev)
+    m = torch.as_tensor(np.ascontiguousarray(maps)).to(dev)
+    cfg = env._config()
+    lib = env._lib
+    need = int(lib.pcgrl_get_playthrough_bytes(C.byref(cfg), M, max_len))
+    assert need >= 256
+    work = torch.empty((need + 256,), dtype=torch.uint8, device=dev)
+    assert work.data_ptr() % 256 == 0
+    p = lambda t, off=0: C.c_void_p(t.data_ptr() + off)
+    assert lib.pcgrl_get_playthrough(env._handle, p(m), M, max_len, p(mv, guard), p(ln, 4 * guard), p(ag, guard), p(rw, 4 * guard), p(work), need, env._stream()) == 0
+    torch.cuda.synchronize()
+    for t, fill in ((mv, 0x5A), (ln, 0x5A5A5A5A), (ag, 0x5A), (rw, 0x5A5A5A5A)):
+        assert (t[:guard] == fill).all().item() and (t[-guard:] == fill).all().item()
+    assert torch.equal(mv[guard:-guard].view(M, max_len), pt.moves) and torch.equal(ln[guard:-guard], pt.length) and torch.equal(ag[guard:-guard], pt.agent)
+    assert torch.equal(rw[guard:-guard].view(M, 8), pt.rows)
+    # the optional outputs NULL: moves and lengths are the same
+    mv2, ln2 = torch.full_like(mv, 0x5A), torch.full_like(ln, 0x5A5A5A5A)
+    assert lib.pcgrl_get_playthrough(env._handle, p(m), M, max_len, p(mv2, guard), p(ln2, 4 * guard), None, None, p(work), need, env._stream()) == 0
+    torch.cuda.synchronize()
+    assert torch.equal(mv2, mv) and torch.equal(ln2, ln)
+    # refusals: a workspace one byte short, a misaligned one, max_len 0, count 0
+    args = (p(mv2, guard), p(ln2, 4 * guard), None, None)
+    assert lib.pcgrl_get_playthrough(env._handle, p(m), M, max_len, *args, p(work), need - 1, env._stream()) == -1
+    assert lib.pcgrl_get_playthrough(env._handle, p(m), M, max_len, *args, p(work, 128), need, env._stream()) == -1
+    assert lib.pcgrl_get_playthrough(env._handle, p(m), M, 0, *args, p(work), need, env._stream()) == -1
+    assert lib.pcgrl_get_playthrough(env._handle, p(m), 0, max_len, *args, p(work), need, env._stream()) == -1
+    torch.cuda.synchronize()
+    assert torch.equal(mv2, mv) and torch.equal(ln2, ln)               # a refused call writes nothing
+    env.close()
+
+
+@pytest.mark.parametrize("prob", ["mdungeon", "ddave"])
+def test_bad_tile_is_clamped_and_reported(prob):
+    torch = _torch()
+    maps, stats, agents, power, want, wlen = _fixture(prob, "5x5_p5000")
+    env = _make(prob, 5, 5, power)
+    nt = env.get_num_tiles()
+    bad, clamped = maps[:40].copy(), maps[:40].copy()
+    for i in range(5):
+        bad[i, i % 5, (2 * i) % 5] = 200
+        clamped[i, i % 5, (2 * i) % 5] = nt - 1
+    ref = env.playthrough(clamped)
+    assert env.check_status() == 0
+    given = torch.as_tensor(bad).to(env.device)
+    got = env.playthrough(given)
+    for a, b in ((got.moves, ref.moves), (got.length, ref.length), (got.agent, ref.agent), (got.rows, ref.rows)):
+        assert torch.equal(a, b)
+    with pytest.raises(ValueError):
+        env.check_status()
+    assert np.array_equal(given.cpu().numpy(), bad) and (given == 200).sum().item() == 5     # the caller's tensor still holds 200
+    env.close()
+
+
+def test_configurations_without_the_form():
+    _torch()
+    import gym_pcgrl_amd
+    for kw in (dict(prob="binary", h=5, w=5), dict(prob="zelda", h=5, w=5), dict(prob="smb", h=5, w=5), dict(prob="sokoban", h=5, w=5),
+               dict(prob="mdungeon", h=16, w=24, power=2500), dict(prob="ddave", h=16, w=24, power=2500), dict(prob="mdungeon", h=5, w=5, power=5001),
+               dict(prob="ddave", h=5, w=5, power=5001)):
+        env = _make(**kw)
+        with pytest.raises(NotImplementedError) as info:
+            env.playthrough(np.zeros((2, kw["h"], kw["w"]), np.uint8))
+        if kw["prob"] == "sokoban":
+            assert "solve()" in str(info.value)
+        env.close()
+    env = _make("mdungeon", 5, 5)
+    with pytest.raises(ValueError):
+        env.playthrough(np.zeros((2, 5, 6), np.uint8))
+    with pytest.raises(ValueError):
+        env.playthrough(np.zeros((5, 5), np.uint8))
+    with pytest.raises(ValueError):
+        env.playthrough(np.zeros((2, 5, 5), np.uint8), max_len=0)
+    with pytest.raises(NotImplementedError) as info:
+        env.solve(np.zeros((2, 5, 5), np.uint8))
+    assert "playthrough()" in str(info.value)
+    env.close()
+    for prob, name in (("mdungeon", "6x9_p300"), ("ddave", "6x9_p150")):          # the one-call form, with adjust_param's keys
+        maps, stats, agents, power, want, wlen = _fixture(prob, name)
+        pt = gym_pcgrl_amd.playthrough_levels(prob, maps, solver_power=power, max_len=want.shape[1])
+        assert np.array_equal(pt.moves.cpu().numpy(), want) and np.array_equal(pt.length.cpu().numpy(), wlen)
+        assert np.array_equal(pt.agent.cpu().numpy(), agents[:, 4])
