@@ -846,7 +846,7 @@ __device__ __forceinline__ bool big_item_stats(const PcgrlParams& P, const DevBu
         return cnt[0] == 1 && cnt[1] == 1 && regions == 1;
     }
     // ddave_prob.py:141-161 without the planner (row layout: dd_pack).  The three counts that share slot 0 have eight bits each:
-    // a map with more than 255 player, exit or key tiles is reported through the status word instead of being packed wrongly.
+    // a map with more than 255 player, exit or key tiles is reported through the status word and packed saturated at 255.
     if (cnt[0] > 255 || cnt[1] > 255 || cnt[2] > 255) { if (lane == 0) atomicOr(B.status, PCGRL_STATUS_TOO_MANY_CRATES); }
     for (int i = lane; i < NW; i += 64) {
         const int r = big_row(G, i), k = i - r * G.KW;
@@ -855,7 +855,7 @@ __device__ __forceinline__ bool big_item_stats(const PcgrlParams& P, const DevBu
         a5[i] = ~b2 & ~b1 & b0 & v;                                                      // solid
     }
     big_sync();
-    s[0] = (cnt[0] & 255) | ((cnt[1] & 255) << 8) | ((cnt[2] & 255) << 16);
+    s[0] = pcgrl_sat255(cnt[0]) | (pcgrl_sat255(cnt[1]) << 8) | (pcgrl_sat255(cnt[2]) << 16);
     s[1] = big_floor_dist(a4, a5, a3, a6, G, lane);
     s[2] = cnt[3]; s[3] = cnt[4]; s[4] = regions; s[5] = 0;
     s[6] = P.prob_width * P.prob_height; s[7] = 0;

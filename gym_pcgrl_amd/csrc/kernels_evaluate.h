@@ -49,7 +49,7 @@ __global__ __launch_bounds__(PCGRL_BLOCK) void k_get_stats(PcgrlParams P, const 
         __builtin_amdgcn_wave_barrier();                                // (the stage is free for the next round)
         int32_t s[PCGRL_MAX_STATS] = {0, 0, 0, 0, 0, 0, 0, 0};
         bool need_solver = false;
-        if (have) need_solver = compute_item_stats<PROB>(g, P, b0, b1, b2, rowmask, s);
+        if (have) need_solver = compute_item_stats<PROB>(g, P, b0, b1, b2, rowmask, s, status);
         if (g.lane == 0 && have) {
             int32_t* row = rows_out + (size_t)m * 8;
 #pragma unroll

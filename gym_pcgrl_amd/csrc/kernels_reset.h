@@ -26,7 +26,7 @@ __global__ __launch_bounds__(PCGRL_BLOCK) void k_reset(PcgrlParams P, DevBufs B,
         const MaskT valid = (lane < G) ? row_valid<MaskT>(g.lane, W, H) : (MaskT)0;
         int32_t st[PCGRL_MAX_STATS] = {0, 0, 0, 0, 0, 0, 0, 0};
         MaskT champ;
-        const bool need_solver = compute_item_stats<PROB>(g, P, b0, b1, b2, valid, st, champ);
+        const bool need_solver = compute_item_stats<PROB>(g, P, b0, b1, b2, valid, st, B.status, champ);
         if (PROB == PCGRL_PROB_BINARY && B.champ && lane < G) reinterpret_cast<MaskT*>(B.champ)[(size_t)e * G + lane] = champ;
         if (lane == 0) finish_or_park<PROB>(P, B, e, st, need_solver, MODE_START, parity, item & (WL_NSHARD - 1), true, park_list);
         __builtin_amdgcn_wave_barrier();

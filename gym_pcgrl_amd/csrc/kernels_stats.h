@@ -54,9 +54,10 @@ __device__ __forceinline__ bool finalize_item(const PcgrlParams& P, const DevBuf
 // when the Sokoban solver has to finish the job.
 // Binary: `champ` receives the rows of the champion component (pcgrl_algos.h) and s[2] says whether there is one --
 // a slot of the stats row the binary problem does not use otherwise; k_update reads it to route the next change.
+// `status`: the sticky status word (DevBufs::status) -- Dave: a count beyond the eight bits it has in slot 0 is reported there.
 template <int PROB, class G, class MaskT>
 __device__ __forceinline__ bool compute_item_stats(G& g, const PcgrlParams& P, MaskT b0, MaskT b1, MaskT b2, MaskT valid, int32_t* s,
-                                                   MaskT& champ, bool tight = true) {
+                                                   int32_t* status, MaskT& champ, bool tight = true) {
     champ = 0;
     if (PROB == PCGRL_PROB_BINARY) {
         int regions, path;
@@ -72,14 +73,19 @@ __device__ __forceinline__ bool compute_item_stats(G& g, const PcgrlParams& P, M
     }
     if (PROB == PCGRL_PROB_ZELDA) { zelda_stats(g, P, b0, b1, b2, valid, s); return false; }
     if (PROB == PCGRL_PROB_MDUNGEON) return mdungeon_stats(g, P, b0, b1, b2, valid, s);
-    if (PROB == PCGRL_PROB_DDAVE) return ddave_stats(g, P, b0, b1, b2, valid, s);
+    if (PROB == PCGRL_PROB_DDAVE) {
+        bool overflow = false;
+        const bool ns = ddave_stats(g, P, b0, b1, b2, valid, s, &overflow);
+        if (overflow && g.lane == 0) atomicOr(status, PCGRL_STATUS_TOO_MANY_CRATES);
+        return ns;
+    }
     if (PROB == PCGRL_PROB_SMB) return true;      // no bit planes: everything is computed by k_smb (kernels_smb.h) on the byte map
     return sokoban_stats(g, P, b0, b1, b2, valid, s);
 }
 template <int PROB, class G, class MaskT>
-__device__ __forceinline__ bool compute_item_stats(G& g, const PcgrlParams& P, MaskT b0, MaskT b1, MaskT b2, MaskT valid, int32_t* s) {
+__device__ __forceinline__ bool compute_item_stats(G& g, const PcgrlParams& P, MaskT b0, MaskT b1, MaskT b2, MaskT valid, int32_t* s, int32_t* status) {
     MaskT champ;
-    return compute_item_stats<PROB>(g, P, b0, b1, b2, valid, s, champ);
+    return compute_item_stats<PROB>(g, P, b0, b1, b2, valid, s, status, champ);
 }
 
 // Lane 0 of the group: hand the item to the solver or finish it.
@@ -191,7 +197,7 @@ __device__ __forceinline__ void stats_wave_task(const PcgrlParams& P, const DevB
         int32_t sl[PCGRL_MAX_STATS] = {0, 0, 0, 0, 0, 0, 0, 0};
         MaskT champ_l = 0;
         bool ns = false;
-        if (act) ns = compute_item_stats<PROB>(g, P, b0, b1, b2, rowmask, sl, champ_l, (B.step_tight & 2) != 0);
+        if (act) ns = compute_item_stats<PROB>(g, P, b0, b1, b2, rowmask, sl, B.status, champ_l, (B.step_tight & 2) != 0);
         TL(10);
         constexpr bool kLaneReward = PROB == PCGRL_PROB_ZELDA && G == 16;
         double rpre = 0.0;
@@ -270,7 +276,7 @@ __device__ __forceinline__ void stats_wave_task(const PcgrlParams& P, const DevB
                 full = false;
             }
         }
-        if (full) need_solver = compute_item_stats<PROB>(g, P, b0, b1, b2, rowmask, s, champ, (B.step_tight & 1) != 0);      // (also what binary_touch gave up on)
+        if (full) need_solver = compute_item_stats<PROB>(g, P, b0, b1, b2, rowmask, s, B.status, champ, (B.step_tight & 1) != 0);      // (also what binary_touch gave up on)
     }
     if (kInc && compute && champ_base) champ_base[(size_t)e * G + g.lane] = champ;
     TL(10);
@@ -321,7 +327,7 @@ __device__ __forceinline__ void stats_wave_task(const PcgrlParams& P, const DevB
             // start stats of the regenerated maps (pcgrl_env.py:70-71, problem.py:45-46)
             if (mine) {
                 int32_t st[PCGRL_MAX_STATS] = {0, 0, 0, 0, 0, 0, 0, 0};
-                const bool ns = compute_item_stats<PROB>(g, P, b0, b1, b2, rowmask, st, champ, (B.step_tight & 2) != 0);
+                const bool ns = compute_item_stats<PROB>(g, P, b0, b1, b2, rowmask, st, B.status, champ, (B.step_tight & 2) != 0);
                 if (kInc && champ_base) champ_base[(size_t)e * G + g.lane] = champ;
                 if (g.lane == 0) finish_or_park<PROB>(P, B, e, st, ns, MODE_START, parity, shard);
             }
@@ -486,7 +492,7 @@ __device__ __forceinline__ void wave_incremental_item(const PcgrlParams& P, cons
         MaskT n0, n1, n2;
         reset_rows_to_planes<MaskT>(P, planes_e, lane, rr.m0, rr.m1, rr.m2, n0, n1, n2);
         int32_t st[PCGRL_MAX_STATS] = {0, 0, 0, 0, 0, 0, 0, 0};
-        compute_item_stats<PCGRL_PROB_BINARY>(g, P, n0, n1, n2, rowmask, st, champ);
+        compute_item_stats<PCGRL_PROB_BINARY>(g, P, n0, n1, n2, rowmask, st, B.status, champ);
         champ_e[lane] = champ;
         if (lane == 0) finalize_item<PCGRL_PROB_BINARY>(P, B, e, st, MODE_START, parity, e & (WL_NSHARD - 1));
     }

@@ -98,7 +98,7 @@ __global__ __launch_bounds__(SS_THREADS) void k_step_solver(PcgrlParams P, DevBu
                     const MaskT valid = (lane64 < G) ? rowmask : (MaskT)0;
                     int32_t st[PCGRL_MAX_STATS] = {0, 0, 0, 0, 0, 0, 0, 0};
                     MaskT champ;
-                    const bool need_solver = compute_item_stats<PROB>(g, P, b0, b1, b2, valid, st, champ);
+                    const bool need_solver = compute_item_stats<PROB>(g, P, b0, b1, b2, valid, st, B.status, champ);
                     if (lane64 == 0) finish_or_park<PROB>(P, B, e, st, need_solver, MODE_START, 0, 0, true, park_list);
                     __builtin_amdgcn_wave_barrier();
                 }

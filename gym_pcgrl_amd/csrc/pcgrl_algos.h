@@ -86,7 +86,10 @@ PCGRL_HD int range_reward_i(int nv, int ov, int lo, int hi) {
 // this library have eight 32-bit slots, so the planner's five results share two of them:
 //   s[0..5] = player, exit, potions, treasures, enemies, regions
 //   s[6]    = sol-length if the planner won, else dist-win
-//   s[7]    = col-potions | col-treasures << 8 | col-enemies << 16 | won << 24    (a solvable level has < 256 things)
+//   s[7]    = col-potions | col-treasures << 8 | col-enemies << 16 | won << 24
+// A count that shares a slot has eight bits and is stored saturated at 255 (pcgrl_sat255): a level with 257 of a thing never reads
+// as a level with one.  Whoever packs a count beyond 255 also raises PCGRL_STATUS_TOO_MANY_CRATES (include/pcgrl_hip.h).
+PCGRL_HD int pcgrl_sat255(int n) { return n > 255 ? 255 : n; }
 // (dist-win is 0 when the planner won and sol-length is 0 when it did not, mdungeon_prob.py:112-126.)
 PCGRL_HD int md_won(const int32_t* s) { return (s[7] >> 24) & 1; }
 PCGRL_HD int md_dist_win(const int32_t* s) { return md_won(s) ? 0 : s[6]; }
@@ -97,10 +100,10 @@ PCGRL_HD int md_col_enemies(const int32_t* s) { return (s[7] >> 16) & 255; }
 PCGRL_HD void md_pack(int32_t* s, const int* out5) {   // out5 = dist-win, sol-length, col-potions, col-treasures, col-enemies
     const int won = out5[1] > 0 ? 1 : 0;              // the exit is never under the player at depth 0
     s[6] = won ? out5[1] : out5[0];
-    s[7] = (out5[2] & 255) | ((out5[3] & 255) << 8) | ((out5[4] & 255) << 16) | (won << 24);
+    s[7] = pcgrl_sat255(out5[2]) | (pcgrl_sat255(out5[3]) << 8) | (pcgrl_sat255(out5[4]) << 16) | (won << 24);
 }
 
-// The ddave row (ddave_prob.py:141-161 has eleven values too; a level the planner accepts has fewer than 256 cells):
+// The ddave row (ddave_prob.py:141-161 has eleven values too; the four counts that share a slot are saturated at 255 like mdungeon's):
 //   s[0] = player | exit << 8 | key << 16, s[1] = dist-floor, s[2] = diamonds, s[3] = spikes, s[4] = regions,
 //   s[5] = num-jumps, s[6] = sol-length if the planner won else dist-win, s[7] = col-diamonds | won << 24
 PCGRL_HD int dd_player(const int32_t* s) { return s[0] & 255; }
@@ -110,7 +113,7 @@ PCGRL_HD void dd_pack(int32_t* s, const int* out4) {   // out4 = dist-win, sol-l
     const int won = out4[1] > 0 ? 1 : 0;              // the player never starts on the exit holding the key
     s[5] = out4[2];
     s[6] = won ? out4[1] : out4[0];
-    s[7] = (out4[3] & 255) | (won << 24);
+    s[7] = pcgrl_sat255(out4[3]) | (won << 24);
 }
 
 // binary_prob.py:98-106 | zelda_prob.py:124-142 | sokoban_prob.py:157-175 (same summation order; the
@@ -977,10 +980,11 @@ PCGRL_D int floor_dist(B& g, typename B::mask_t player, typename B::mask_t solid
 }
 
 // ddave_prob.py:141-161 without the planner.  out: the packed row described at dd_pack (dist-win default W*H, no jumps,
-// nothing collected).  Returns true when the planner precondition (ddave_prob.py:156-157) holds.
+// nothing collected).  Returns true when the planner precondition (ddave_prob.py:156-157) holds.  `*overflow` (when asked for): the map has
+// more than 255 player, exit or key tiles -- slot 0 holds the saturated counts and the device callers report PCGRL_STATUS_TOO_MANY_CRATES.
 template <class B>
 PCGRL_D bool ddave_stats(B& g, const PcgrlParams& P, typename B::mask_t b0, typename B::mask_t b1,
-                         typename B::mask_t b2, typename B::mask_t valid, int32_t* out) {
+                         typename B::mask_t b2, typename B::mask_t valid, int32_t* out, bool* overflow = nullptr) {
     typedef typename B::mask_t M;
     // ids: 0 empty 1 solid 2 player 3 exit 4 diamond 5 key 6 spike (ddave_prob.py:48-49)
     M solid = ~b2 & ~b1 & b0 & valid;
@@ -990,7 +994,8 @@ PCGRL_D bool ddave_stats(B& g, const PcgrlParams& P, typename B::mask_t b0, type
     M key = b2 & ~b1 & b0 & valid;
     M spike = b2 & b1 & ~b0 & valid;
     const int np_ = g.popcount_sum(player), nx = g.popcount_sum(exitm), nk = g.popcount_sum(key);
-    out[0] = (np_ & 255) | ((nx & 255) << 8) | ((nk & 255) << 16);
+    if (overflow) *overflow = np_ > 255 || nx > 255 || nk > 255;
+    out[0] = pcgrl_sat255(np_) | (pcgrl_sat255(nx) << 8) | (pcgrl_sat255(nk) << 16);
     out[1] = floor_dist(g, player, solid, valid, P.height);
     out[2] = g.popcount_sum(diamond);
     out[3] = g.popcount_sum(spike);

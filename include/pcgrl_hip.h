@@ -427,7 +427,10 @@ int pcgrl_selftest_step_pool(int32_t count, int32_t calls, int32_t fail_at, int3
 int pcgrl_selftest_range_reward(const int32_t* rows, int32_t n, int32_t* out, void* stream);
 /* Sticky device status word, 0 = fine.  Bit 0 (1): a level was outside a search kernel's limits -- a Sokoban level with more crates
  * than the search takes (32 in the compact searches, 256 in the general ones of csrc/search_big.h), or more than 255 tiles / collected
- * things of one kind in a packed statistics row (Dave, MiniDungeons on large maps): the statistics of that level are then not exact.
+ * things of one kind in a packed statistics row: Dave's player, exit and key tiles and collected diamonds, MiniDungeons' collected potions,
+ * treasures and enemies, on a map of any size and on every route that computes statistics (reset, step, rollout, asynchronous ticks,
+ * pcgrl_set_maps, pcgrl_get_stats).  Such a count is stored saturated at 255 -- a level with 257 players never reads as a level with
+ * one -- so the statistics of that level, and the rewards computed from them, are not exact; the columns that own a whole slot are.
  * Bit 1 (2): an action outside the action space was clamped into it (the reference raises IndexError or writes the
  * bad value: narrow_rep.py:101-103, wide_rep.py:68-69, turtle_rep.py:101-129, wrappers.py:139-154).  Bit 2 (4):
  * pcgrl_set_maps was handed a tile id >= the number of tiles (clamped).  Synchronises the stream. */

@@ -17,6 +17,7 @@ Fixture families:
   adjust_param.npz  the adjust_param ordering quirk (Q9) and spaces
   traj_*.npz       full env trajectories (obs map/pos/heatmap, reward, done, info) with auto-reset
   noreset.npz      stepping past done with no reset; one cell's heat count past 2^16
+  extremes_*.npz   levels with 254 .. 257 and more tiles of one kind at the smallest shapes that hold them (gen_extremes)
 """
 import argparse
 import os
@@ -1088,6 +1089,105 @@ def gen_noreset():
     print("noreset", heat.max(), "%.0f s" % (time.time() - t0))
 
 
+# ----------------------------------------------------------------------------- tile counts at 255 / 256
+# The library keeps some counts of the ddave and mdungeon rows in eight bits (csrc/pcgrl_algos.h, md_pack / dd_pack): levels at the
+# smallest shapes at which a count can pass 255.  The tiles a level must have exactly one of, per problem:
+ONCE_ONLY = {"ddave": ["player", "exit", "key"], "mdungeon": ["player", "exit"], "zelda": ["player", "key", "door"], "sokoban": ["player"]}
+# ... and the tiles a level may have any number of, whose counts own a whole slot of the row ("unpacked counts past 255")
+FILLERS = {"ddave": ["diamond", "spike"], "mdungeon": ["potion", "treasure", "goblin", "ogre"]}
+EXTREME_SHAPES = {      # (h, w): the problems; A 16 x 16, B 13 x 20 and 8 x 33, C 4 x 65 (a side above 64)
+    (16, 16): ["ddave", "mdungeon", "zelda", "sokoban"], (13, 20): ["ddave", "mdungeon", "zelda", "sokoban"],
+    (8, 33): ["ddave", "mdungeon", "zelda", "sokoban"], (4, 65): ["ddave", "mdungeon"],
+}
+EXTREME_POWER, SERPENTINE_POWER = 100, 1000
+
+
+def extreme_levels(tiles, pname, h, w):
+    """(names, maps) of one problem at one shape: every tile alone; 254 .. 257 of each once-only tile on the first and on the last
+    cells in row-major order, the rest empty; one of each once-only tile on the first cells and everything else one filler tile."""
+    names, maps = [], []
+    for t, tile in enumerate(tiles):
+        names.append("all-" + tile); maps.append(np.full((h, w), t, np.uint8))
+    for tile in ONCE_ONLY[pname]:
+        for n in (254, 255, 256, 257):
+            if n > h * w:
+                continue
+            for where in ("first", "last"):
+                m = np.zeros(h * w, np.uint8)
+                if where == "first":
+                    m[:n] = tiles.index(tile)
+                else:
+                    m[h * w - n:] = tiles.index(tile)
+                names.append("%s-%s-%d" % (where, tile, n)); maps.append(m.reshape(h, w))
+    for tile in FILLERS.get(pname, []):
+        m = np.full(h * w, tiles.index(tile), np.uint8)
+        for k, once in enumerate(ONCE_ONLY[pname]):
+            m[k] = tiles.index(once)
+        names.append("fill-" + tile); maps.append(m.reshape(h, w))
+    return names, maps
+
+
+def serpentine_levels(tiles, w):
+    """3 x w: treasure in rows 0 and 2, row 1 solid but for its last cell, the player at (0, 0) and the exit at (2, 0) -- one way
+    through, 2 w - 1 treasures on it; the second level has one treasure fewer, the third two."""
+    m = np.zeros((3, w), np.uint8)
+    m[0], m[2], m[1] = tiles.index("treasure"), tiles.index("treasure"), tiles.index("solid")
+    m[1, w - 1] = tiles.index("treasure")
+    m[0, 0], m[2, 0] = tiles.index("player"), tiles.index("exit")
+    less = m.copy()
+    less[0, w // 2] = tiles.index("empty")
+    less2 = less.copy()
+    less2[2, w // 2] = tiles.index("empty")
+    return ["serpentine", "serpentine-less-one", "serpentine-less-two"], [m, less, less2]
+
+
+def dave_serpentine_levels(tiles, w):
+    """3 x w for Dave: diamonds in rows 0 and 2, row 1 solid but for its last cell, the player at (0, 0), the exit at (2, 0) and
+    the key next to it.  Under a ceiling nobody jumps and the walk is forced: along row 0, down the gap -- the step into the last
+    column falls in the same move, so the diamond of (0, w - 1) stays -- and back along row 2: 2 w - 3 diamonds collected.  The
+    second level has one diamond fewer on the way, the third two."""
+    m = np.zeros((3, w), np.uint8)
+    m[0], m[2], m[1] = tiles.index("diamond"), tiles.index("diamond"), tiles.index("solid")
+    m[1, w - 1] = tiles.index("diamond")
+    m[0, 0], m[2, 0], m[2, 1] = tiles.index("player"), tiles.index("exit"), tiles.index("key")
+    less = m.copy()
+    less[0, w // 2] = tiles.index("empty")
+    less2 = less.copy()
+    less2[2, w // 2] = tiles.index("empty")
+    return ["serpentine", "serpentine-less-one", "serpentine-less-two"], [m, less, less2]
+
+
+def gen_extremes():
+    """extremes_<prob>_<H>x<W>.npz: maps, stats (STAT_KEYS order), names, keys, solver_power.  Not stats_*: the tests that glob for
+    those demand status 0 of every level."""
+    def write(pname, h, w, power, names, maps):
+        prob = PROBLEMS[pname]()
+        prob._width, prob._height = w, h
+        if hasattr(prob, "_solver_power"):
+            prob._solver_power = power
+        t0 = time.time()
+        res = []
+        for m in maps:
+            st = stats_of(prob, m)
+            res.append([len(st["solution"]) if (pname == "sokoban" and k == "sol-length") else int(st[k]) for k in STAT_KEYS[pname]])
+        res = np.array(res, dtype=np.int64)
+        print("  %s %dx%d power %d: %d maps, largest count %d, %.1fs" % (pname, h, w, power, len(maps), int(res.max()), time.time() - t0))
+        save("extremes_%s_%dx%d" % (pname, h, w), maps=np.array(maps), stats=res, names=np.array(names), keys=np.array(STAT_KEYS[pname]),
+             solver_power=np.array(power))
+    for (h, w), probs in EXTREME_SHAPES.items():
+        for pname in probs:
+            tiles = PROBLEMS[pname]().get_tile_types()
+            names, maps = extreme_levels(tiles, pname, h, w)
+            write(pname, h, w, EXTREME_POWER, names, maps)
+    tiles = PROBLEMS["mdungeon"]().get_tile_types()
+    for w in (128, 129):
+        names, maps = serpentine_levels(tiles, w)
+        n = 3 if w == 129 else 1
+        write("mdungeon", 3, w, SERPENTINE_POWER, names[:n], maps[:n])
+    names, maps = dave_serpentine_levels(PROBLEMS["ddave"]().get_tile_types(), 130)
+    write("ddave", 3, 130, SERPENTINE_POWER, names, maps)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default=None)
@@ -1096,7 +1196,7 @@ def main():
         "rng": gen_rng, "stats_binary": gen_stats_binary, "stats_zelda": gen_stats_zelda,
         "stats_sokoban": gen_stats_sokoban, "stats_mdungeon": gen_stats_mdungeon, "stats_ddave": gen_stats_ddave, "stats_smb": gen_stats_smb, "range_reward": gen_range_reward, "adjust_param": gen_adjust_param,
         "wrappers": gen_wrappers, "stats_big": gen_stats_big, "stats_big_search": gen_stats_big_search, "stats_huge_search": gen_stats_huge_search, "heat_boundary": gen_heat_boundary,
-        "noreset": gen_noreset,
+        "noreset": gen_noreset, "extremes": gen_extremes,
     }
     for k, fn in jobs.items():
         if a.only in (None, k):

@@ -117,7 +117,7 @@ struct SimGroup {
 };
 
 template <int G, class T>
-static void run(int prob, const uint8_t* map, int h, int w, int pw, int ph, int32_t* out, int* need_solver) {
+static void run(int prob, const uint8_t* map, int h, int w, int pw, int ph, int32_t* out, int* need_solver, int* overflow = nullptr) {
     typedef SimGroup<G, T> Gp;
     typedef typename Gp::mask_t M;
     Gp g;
@@ -140,7 +140,9 @@ static void run(int prob, const uint8_t* map, int h, int w, int pw, int ph, int3
     } else if (prob == PCGRL_PROB_ZELDA) {
         zelda_stats(g, P, b0, b1, b2, valid, out);
     } else if (prob == PCGRL_PROB_DDAVE) {
-        *need_solver = ddave_stats(g, P, b0, b1, b2, valid, out) ? 1 : 0;
+        bool over = false;
+        *need_solver = ddave_stats(g, P, b0, b1, b2, valid, out, &over) ? 1 : 0;
+        if (overflow) *overflow = over ? 1 : 0;
     } else if (prob == PCGRL_PROB_MDUNGEON) {
         *need_solver = mdungeon_stats(g, P, b0, b1, b2, valid, out) ? 1 : 0;
     } else {
@@ -465,6 +467,16 @@ int sim_stats(int prob, const uint8_t* map, int h, int w, int pw, int ph, int va
     else if (!g64) run<16, uint64_t>(prob, map, h, w, pw, ph, out, need_solver);
     else if (!m64) run<64, uint32_t>(prob, map, h, w, pw, ph, out, need_solver);
     else run<64, uint64_t>(prob, map, h, w, pw, ph, out, need_solver);
+    return 0;
+}
+// ... and whether a count overflowed the eight bits it has in a shared slot (ddave_stats: the device callers turn it into status bit 0)
+int sim_stats_overflow(int prob, const uint8_t* map, int h, int w, int pw, int ph, int variant, int32_t* out, int* need_solver, int* overflow) {
+    bool g64 = h > 16 || (variant & 1), m64 = w > 32 || (variant & 2);
+    *overflow = 0;
+    if (!g64 && !m64) run<16, uint32_t>(prob, map, h, w, pw, ph, out, need_solver, overflow);
+    else if (!g64) run<16, uint64_t>(prob, map, h, w, pw, ph, out, need_solver, overflow);
+    else if (!m64) run<64, uint32_t>(prob, map, h, w, pw, ph, out, need_solver, overflow);
+    else run<64, uint64_t>(prob, map, h, w, pw, ph, out, need_solver, overflow);
     return 0;
 }
 double sim_range_reward(double n, double o, double lo, double hi) { return range_reward(n, o, lo, hi); }
