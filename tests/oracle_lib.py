@@ -95,6 +95,9 @@ def lib(big=False):
         L.orc_rng_key.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.orc_rng_mixed.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.orc_build_cdf_export.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.orc_set_solver_power.argtypes = [C.c_void_p, C.c_int]
+        L.orc_smb_trace.argtypes = [C.c_void_p]
+        L.orc_smb_expanded.argtypes = [C.c_void_p, C.c_int]
         _libs[big] = L
     return _libs[big]
 
@@ -112,7 +115,13 @@ def needs_big(prob, w, h):
     return prob in ("sokoban", "mdungeon", "ddave") and (w + 2) * (h + 2) > 256
 
 
-def get_stats(prob, m, pw=None, ph=None, solver_power=5000, with_iters=False, big=None):
+SMB_TRACE_KEYS = ("pops0", "queue0", "expansions0", "pops1", "queue1", "expansions1", "x", "prev_jump_x", "max_gap", "won")
+
+
+def get_stats(prob, m, pw=None, ph=None, solver_power=5000, with_iters=False, big=None, with_trace=False):
+    """with_trace (smb): also the trace of the play-through, a dict over SMB_TRACE_KEYS -- per agent (0: balance 1, 1: balance 0, zeros
+    if it did not run) the pops, the longest queue (the heap's length after an expansion's four pushes) and the expansions; the result
+    node's engine column, its last jump column and widest gap, whether it won, and `expanded`: the expanded states' cells."""
     m = np.ascontiguousarray(m, dtype=np.uint8)
     h, w = m.shape
     big = needs_big(prob, w, h) if big is None else big
@@ -120,7 +129,17 @@ def get_stats(prob, m, pw=None, ph=None, solver_power=5000, with_iters=False, bi
     it = np.zeros(4, np.int32)
     lib(big).orc_get_stats(PROBS[prob], _p(m), w, h, pw or w, ph or h, solver_power, _p(out), _p(it))
     res = out[:NSTATS[prob]].copy()
-    return (res, it) if with_iters else res
+    ret = (res, it) if with_iters else (res,)
+    if with_trace:
+        assert prob == "smb"
+        tr = np.zeros(len(SMB_TRACE_KEYS), np.int32)
+        lib(big).orc_smb_trace(_p(tr))
+        tr = dict(zip(SMB_TRACE_KEYS, (int(v) for v in tr)))
+        # per column of the engine's grid (map column + 3) the rows with an expanded state, either agent: bit y + 8 = row y
+        tr["expanded"] = np.zeros(w + 6, np.uint64)
+        lib(big).orc_smb_expanded(_p(tr["expanded"]), w + 6)
+        ret += (tr,)
+    return ret if len(ret) > 1 else res
 
 
 class OracleEnv:
@@ -174,6 +193,11 @@ class OracleEnv:
             elif k in ADJ_KEYS:
                 L.orc_adjust_set(self._h, ADJ_KEYS[k], float(v))
         L.orc_adjust_commit(self._h)
+
+    def set_solver_power(self, power):
+        """prob._solver_power = power: how smb's solver_power is set (smb_prob.py:40-53 leaves it out of adjust_param; the other search
+        problems take it through adjust_param too).  The next computed statistics are played with it; nothing is recomputed."""
+        lib(self._big).orc_set_solver_power(self._h, int(power))
 
     width = property(lambda s: lib(s._big).orc_width(s._h))
     height = property(lambda s: lib(s._big).orc_height(s._h))

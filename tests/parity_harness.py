@@ -429,6 +429,94 @@ def flip_tape(maps, cells):
     return start, acts
 
 
+def write_tape(maps, cells, tiles):
+    """flip_tape for any write: for levels `maps` [N, H, W], one cell (x, y) and one other tile per level, the neighbours M' (that cell
+    holding the tile) and the wide actions [4, N, 3] that write the cell back to its value in M, to the tile again, and both once more
+    -- steps 1 and 3 compute M, steps 2 and 4 M'."""
+    maps = np.ascontiguousarray(maps, dtype=np.uint8)
+    n = len(maps)
+    x, y = np.asarray(cells)[:, 0], np.asarray(cells)[:, 1]
+    v = maps[np.arange(n), y, x]
+    tiles = np.asarray(tiles).astype(np.uint8)
+    assert tiles.shape == (n,) and (tiles != v).all()
+    start = maps.copy()
+    start[np.arange(n), y, x] = tiles
+    acts = np.stack([np.stack([x, y, v if t % 2 == 0 else tiles], 1) for t in range(4)]).astype(np.int32)
+    return start, acts
+
+
+def smb_game_expected(w, h, power, maps, cells, tiles, seed0=7000, auto_reset=True):
+    """What the oracle says of smb_game_case's four steps -> dict(start, acts, reward [4, N], done, info [4, N, keys], maps [4, N, H, W]).
+    The oracle's solver_power is set the way smb's is (OracleEnv.set_solver_power), before the reset."""
+    start, acts = write_tape(maps, cells, tiles)
+    exp = []
+    for i in range(len(maps)):
+        o = ol.OracleEnv("smb", "wide")
+        o.adjust_param(width=w, height=h)
+        o.adjust_param(change_percentage=1.0)
+        o.set_solver_power(power)
+        o.seed(seed0 + i)
+        o.reset()
+        o.set_map(start[i])
+        exp.append(o.rollout(acts[:, i], want_heat=False) if auto_reset else oracle_noreset(o, acts[:, i]))
+    return dict(start=start, acts=acts, reward=np.stack([x["reward"] for x in exp], 1), done=np.stack([x["done"] for x in exp], 1),
+                info=np.stack([x["info"] for x in exp], 1), maps=np.stack([x["maps"] for x in exp], 1))
+
+
+def smb_game_case(w, h, power, maps, cells, tiles, route, tuning=None, auto_reset=True, seed0=7000, labels=None, expected=None):
+    """search_game_case for smb (tests/test_gpu_smb_games.py): chosen levels through a stepping route against the oracle.  One handle of
+    N wide environments, change_percentage 1.0, solver_power set as smb's is (prob._solver_power, then adjust_param()); set_maps() puts
+    every environment one write away from its level (write_tape: the cell holds `tiles[i]`), four actions write the level's tile, the
+    other one, and both again.  route: "step" -- step() four times; "rollout" -- the four actions as one rollout() (smb has no
+    asynchronous form).  Reward, done, every info column (iterations and changes too) of every step and the map must equal the
+    oracle's (smb_game_expected: seeded seed0 + i, reset(), set_map(), the four steps, with auto-reset or -- auto_reset=False -- on past
+    done); check_status() must be 0.  expected: smb_game_expected of the same arguments, computed before."""
+    import torch
+    from gym_pcgrl_amd.envs import BatchedPcgrlEnv
+    n = len(maps)
+    E = expected if expected is not None else smb_game_expected(w, h, power, maps, cells, tiles, seed0, auto_reset)
+    start, acts = E["start"], E["acts"]
+
+    def check(what, got, want, t):
+        got, want = np.asarray(got), np.asarray(want)
+        bad = np.nonzero((got != want).reshape(n, -1).any(1))[0]
+        if bad.size:
+            i = int(bad[0])
+            raise AssertionError("%s differs at step %d (route %s, smb %dx%d power %d, tuning %s) for %d levels: %s; level %d, cell %s, tiles %d <-> %d: got %s, the oracle %s"
+                                 % (what, t, route, w, h, power, tuning, bad.size, [(int(j), labels[j] if labels else "") for j in bad[:8]],
+                                    i, tuple(int(v) for v in acts[0, i, :2]), acts[0, i, 2], acts[1, i, 2], got[i].tolist(), want[i].tolist()))
+
+    env = BatchedPcgrlEnv(prob="smb", rep="wide", num_envs=n, seed=seed0, tuning=tuning, auto_reset=auto_reset)
+    try:
+        env.adjust_param(width=w, height=h)
+        env.adjust_param(change_percentage=1.0)
+        env._prob._solver_power = int(power)
+        env.adjust_param()
+        env.reset()
+        keys = list(env._prob.info_keys) + ["iterations", "changes"]
+        env.set_maps(start)
+        if route == "step":
+            for t in range(4):
+                obs, rew, done, info = env.step(acts[t])
+                check("done", done.cpu().numpy(), E["done"][t], t)
+                check("info", np.stack([info[k].cpu().numpy() for k in keys], 1).astype(np.int64), E["info"][t], t)
+                check("reward", rew.cpu().numpy(), E["reward"][t], t)
+                check("map", obs["map"].cpu().numpy(), E["maps"][t], t)
+        elif route == "rollout":
+            rew, done, info = env.rollout(torch.as_tensor(acts, device=env.device))
+            got_info = np.stack([info[k].view(4, n).cpu().numpy() for k in keys], 2).astype(np.int64)
+            for t in range(4):
+                check("done", done[t].cpu().numpy(), E["done"][t], t)
+                check("info", got_info[t], E["info"][t], t)
+                check("reward", rew[t].cpu().numpy(), E["reward"][t], t)
+            check("map", env._bufs["map"].cpu().numpy(), E["maps"][3], 3)
+        else:
+            raise ValueError(route)
+        assert env.check_status() == 0
+    finally:
+        env.close()
+
+
 def search_game_case(prob, w, h, power, maps, cells, route, seed0=7000, tuning=None, pop_budget=4, nslots=8, labels=None):
     """Chosen levels through one stepping route of a search problem against the oracle (tests/test_gpu_search_games.py).  One handle
     of N wide environments with change_percentage 1.0; set_maps() puts every environment one write away from its level (flip_tape)
