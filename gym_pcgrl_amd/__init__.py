@@ -319,5 +319,97 @@ def replay_ddave(level, moves):
                        bool(alive and has_key and pos == door), bool(not alive), int(heuristic))
 
 
+def playthrough_smb_levels(maps, device=None, max_len=None, **params):
+    """The play behind smb's jumps / jumps-dist / dist-win of a stack of levels in one call, next to playthrough_levels(): `maps`
+    array-like uint8 [M, H, W], `params` as for adjust_param plus solver_power (set as an attribute: smb_prob.py:40-53 has no such
+    key).  Returns BatchedPcgrlEnv.playthrough_smb()'s Playthroughs (moves, length, agent, rows, stats)."""
+    import numpy as np
+    from .envs import BatchedPcgrlEnv
+    shape = tuple(maps.shape) if hasattr(maps, "shape") else np.asarray(maps).shape
+    if len(shape) != 3:
+        raise ValueError("playthrough_smb_levels(): maps must be [M, H, W], got shape %s" % (shape,))
+    env = BatchedPcgrlEnv(prob="smb", rep="wide", num_envs=1, device=device, seed=0, auto_reset=False)
+    try:
+        power = params.pop("solver_power", None)
+        if power is not None:
+            env._prob._solver_power = int(power)
+        env.adjust_param(width=int(shape[2]), height=int(shape[1]), **params)
+        return env.playthrough_smb(maps, max_len=max_len)
+    finally:
+        env.close()
+
+
+class SmbReplay:
+    """What replay_smb() returns: `player` int [T+1, 2] -- (x, y) per frame in the engine's padded grid (x = map column + 3; y = map
+    row, negative above the screen), frame 0 the start, frame t after move t -- and per frame `air` (air time left) and `jumps` int
+    [T+1]; `jump_cols` (the engine column of every jump, in order); of the last frame `won` (x at the pole's column), `lost` (fallen
+    below the screen) and `dist_win` (columns left to the pole; SMBProblem reports 0 for a won play)."""
+    __slots__ = ("player", "air", "jumps", "jump_cols", "won", "lost", "dist_win")
+
+    def __init__(self, player, air, jumps, jump_cols, won, lost, dist_win):
+        self.player, self.air, self.jumps, self.jump_cols, self.won, self.lost, self.dist_win = player, air, jumps, jump_cols, won, lost, dist_win
+
+
+def replay_smb(level, moves):
+    """Play `moves` (0 stay, 1 right, 2 jump, 3 right + jump; a negative entry ends the list, like the -1 padding of
+    Playthroughs.moves) on one smb level [H, W] of tile ids (0 empty, 1 solid, 2 enemy, 3 brick, 4 question, 5 coin, 6 tube) by the
+    game's rules.  The grid is the level with three columns added on either side, solid in the last two rows; solid, brick, question
+    and tube block.  The player starts at (1, H - 3); the pole stands in column W + 4 on a block at row H - 3, and reaching that
+    column wins.  Left of column 0, right of the grid and below it nothing can be entered; above the screen everything is free.  A move
+    to the right steps into a free cell.  A jump starts only with a blocked cell below (which the rows above the screen and the last
+    row never have) and a free cell above the cell the player has moved to: air time 5, +1 jump, the column before the move is noted.
+    A move without jump cuts a running jump to air time 1.  Then, with air time above 1 it drops by one and the player rises one cell
+    (a blocked cell above leaves air time 1 instead), with air time 1 the player hovers (air time 0), else the player falls one
+    cell if the cell below can be entered.  Once the player has won or stands below the screen (lost) nothing moves any more.  A
+    level of height 3 has no pole: the start already counts as won.  Host side, numpy.  Returns a SmbReplay."""
+    import numpy as np
+    lv = np.asarray(level)
+    if lv.ndim != 2:
+        raise ValueError("replay_smb(): level must be [H, W], got shape %s" % (lv.shape,))
+    H, W = lv.shape
+    if H < 3:
+        raise ValueError("replay_smb(): a level has at least 3 rows, got %d" % H)
+    if lv.size and int(lv.max()) > 6:
+        raise ValueError("replay_smb(): tile id %d is not one of 0..6" % int(lv.max()))
+    GW = W + 6
+    grid = np.zeros((H, GW), bool)
+    grid[H - 2:, :3] = grid[H - 2:, W + 3:] = True
+    grid[H - 3, W + 4] = True
+    grid[:, 3:W + 3] = np.isin(lv, (1, 3, 4, 6))
+    exit_x = W + 4 if H > 3 else -1
+
+    def free(x, y):
+        return y < 0 or (0 <= x < GW and y < H and not grid[y, x])
+
+    x, y, air, jumps, cols = 1, H - 3, 0, 0, []
+    frames = [(x, y, air, jumps)]
+    for mv in _replay_moves("replay_smb", moves):
+        if x < exit_x and y < H:
+            ground = -1 <= y < H - 1 and bool(grid[y + 1, x])
+            nx = x + 1 if (mv & 1) and free(x + 1, y) else x
+            if mv & 2:
+                if ground and free(nx, y - 1):
+                    air, jumps = 5, jumps + 1
+                    cols.append(x)
+            elif air > 0:
+                air = 1
+            ny = y
+            if air > 1:
+                air -= 1
+                if free(nx, y - 1):
+                    ny = y - 1
+                else:
+                    air = 1
+            elif air == 1:
+                air = 0
+            elif free(nx, y + 1):
+                ny = y + 1
+            x, y = nx, ny
+        frames.append((x, y, air, jumps))
+    col = lambda k: np.array([f[k] for f in frames], np.int64)
+    return SmbReplay(np.array([(f[0], f[1]) for f in frames], np.int64).reshape(-1, 2), col(2), col(3), np.array(cols, np.int64),
+                     bool(x >= exit_x), bool(y >= H), int(exit_x - x))
+
+
 register_with_gym()      # no-op without a gym of the reference's era (none is on the MI355X image)
 register_with_gymnasium()   # likewise for gymnasium / gym >= 0.26 (five-tuple adapter)

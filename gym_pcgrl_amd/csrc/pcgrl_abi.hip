@@ -86,6 +86,7 @@
 #include "kernels_evaluate.h"
 #include "kernels_solution.h"
 #include "kernels_playthrough.h"
+#include "kernels_smb_play.h"     // (after kernels_solution.h: SolOut)
 #include "search_big.h"
 #include "kernels_search_big.h"
 #if PCGRL_IN_PART(PART_CORE)
@@ -632,6 +633,7 @@ PCGRL_LOCAL int launch_get_stats(pcgrl_env* h, const uint8_t* maps, int count, i
 PCGRL_LOCAL int launch_get_stats_search(pcgrl_env* h, const uint8_t* maps, int32_t* rows_out, int32_t* head, const int32_t* jobs, SokNode* pools, int blocks, hipStream_t st);
 PCGRL_LOCAL int launch_get_solution(pcgrl_env* h, const uint8_t* maps, int32_t* rows_out, const SolOut& out, int32_t* head, const int32_t* jobs, SokNode* pools, int blocks, hipStream_t st);
 PCGRL_LOCAL int launch_get_playthrough(pcgrl_env* h, const uint8_t* maps, int32_t* rows_out, const SolOut& out, int32_t* head, const int32_t* jobs, SokNode* pools, uint32_t* traces, int blocks, hipStream_t st);
+PCGRL_LOCAL int launch_smb_play(pcgrl_env* h, const uint8_t* maps, int count, int32_t* rows_out, const SolOut& out, int32_t* ticket, uint8_t* arenas, int slots, hipStream_t st);
 PCGRL_LOCAL int launch_search_async(pcgrl_env* h, int32_t* tickets, int list_a, int mode_a, int list_b, int mode_b, int parity, int rst_list, int clr, int budget, int resume, int small, hipStream_t st);
 // A launch with more than 64 KB of dynamic LDS needs the kernel's cap raised first.  That is a driver call (about a microsecond of
 // host time -- a fifth of what issuing a step costs), so it is made only when this process has not yet raised the cap of this kernel
@@ -859,9 +861,11 @@ static int action_width(int rep) {   // int32 values per environment and step
 // One solver launch: the jobs of list_a (mode_a) and, if list_b >= 0, of list_b (mode_b).  `slot` selects the
 // scheduling words (two launches per step), zeroed here.  Episodes the solver ends go to rst_list.
 #define SMB_LDS_BUDGET (160 * 1024 - 2048)   /* dynamic LDS of a k_smb block: the attribute set at pcgrl_bind and the launch size both come from here */
+static size_t smb_play_wave_bytes(int power) { return smb_wave_arena_bytes(power) + smb_play_log_bytes(power); }   // pcgrl_get_smb_play: one wavefront's arena, then its log
 #if PCGRL_IN_PART(PART_SMB)
 PCGRL_LOCAL int smb_device_setup(pcgrl_env*) {
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_smb<0>), hipFuncAttributeMaxDynamicSharedMemorySize, SMB_LDS_BUDGET));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_smb_play<0>), hipFuncAttributeMaxDynamicSharedMemorySize, SMB_LDS_BUDGET));
     return PCGRL_OK;
 }
 PCGRL_LOCAL int launch_smb(pcgrl_env* h, int32_t* sync, int list_a, int mode_a, int list_b, int mode_b, int parity, int rst_list, int clr, hipStream_t st, int inline_reset) {
@@ -878,6 +882,22 @@ PCGRL_LOCAL int launch_smb(pcgrl_env* h, int32_t* sync, int list_a, int mode_a, 
     // (a step's changed levels come on two lists: WL_INC = the ones expected to take long, first; see k_update)
     return launch_fn(k_smb<0>, SOK_BLOCKS, nw * 64, nw * per_wave, st, h->P, h->B, (list_a == WL_CHG && mode_a == MODE_STEP) ? (int)WL_INC : -1,
                      list_a, mode_a, list_b, mode_b, parity, rst_list, sync, clr, heap_n, inline_reset, gen_flag(h));
+}
+// pcgrl_get_smb_play (kernels_smb_play.h): k_smb's blocks -- the same split of the LDS budget, without the in-kernel reset's staging
+// area -- on `count` levels; `slots` wavefront arenas of smb_play_wave_bytes each are the caller's (SmbPlayPlan)
+PCGRL_LOCAL int launch_smb_play(pcgrl_env* h, const uint8_t* maps, int count, int32_t* rows_out, const SolOut& out, int32_t* ticket, uint8_t* arenas, int slots, hipStream_t st) {
+    const int heap_n = 4 * h->P.solver_power + 4 < h->smb_heap ? ((4 * h->P.solver_power + 4 + 3) & ~3) : h->smb_heap;
+    const size_t vis_words = ((size_t)((h->P.width + 6) * (h->P.height + SMB_YOFF + 1) * 5 + 31) / 32 + 3) & ~(size_t)3;
+    const size_t per_wave = ((size_t)heap_n + vis_words) * 4;
+    int nw = (int)(SMB_LDS_BUDGET / per_wave);
+    nw = nw > SMB_MAX_WAVES ? SMB_MAX_WAVES : (nw < 1 ? 1 : nw);
+    if ((size_t)nw * per_wave > SMB_LDS_BUDGET) return PCGRL_EINVAL;      // one search does not fit a compute unit's LDS
+    if (nw > count) nw = count;
+    int blocks = (count + nw - 1) / nw;
+    blocks = blocks > SOK_BLOCKS ? SOK_BLOCKS : blocks;
+    if ((long long)blocks * nw > slots) return PCGRL_EINVAL;              // (the plan holds count + SMB_MAX_WAVES - 1 arenas, or all of them)
+    return launch_fn(k_smb_play<0>, blocks, nw * 64, nw * per_wave, st, h->P, maps, count, rows_out, out, h->B.status, ticket, arenas,
+                     smb_play_wave_bytes(h->P.solver_power), nw, heap_n);
 }
 #endif  // PART_SMB
 #if PCGRL_IN_PART(PART_SEARCH)
@@ -1779,6 +1799,46 @@ int pcgrl_get_playthrough(pcgrl_env* h, const uint8_t* maps, int32_t count, int3
     if (rc) return rc;
     const SolOut out = {moves_out, length_out, agent_out, max_len};
     return launch_get_playthrough(h, maps, rows, out, head, at<int32_t>(w, S.E.jobs), at<SokNode>(w, S.E.pools), at<uint32_t>(w, S.traces), S.E.blocks, st);
+}
+
+// ---- pcgrl_get_smb_play (kernels_smb_play.h): the play behind smb's jumps / jumps-dist / dist-win ---------------------------------
+// The workspace, cut from one plan: the ticket, rows for a caller that wants none, and one arena + expansion log per wavefront that
+// can run -- the launch takes blocks of at most SMB_MAX_WAVES wavefronts, never more wavefronts than count + SMB_MAX_WAVES - 1.
+struct SmbPlayPlan { Region head, rows, arenas; int slots; size_t total; };
+static SmbPlayPlan smb_play_plan(const pcgrl_config* c, int count) {
+    SmbPlayPlan S = {};
+    Bump b = {0};
+    S.head = b.take(256);
+    S.rows = b.take(align_up((size_t)count * 8 * 4, 256));
+    const long long want = (long long)count + SMB_MAX_WAVES - 1, all = (long long)SOK_BLOCKS * SMB_MAX_WAVES;
+    S.slots = (int)(want < all ? want : all);
+    S.arenas = b.take((size_t)S.slots * smb_play_wave_bytes(c->solver_power));
+    S.total = b.off;
+    return S;
+}
+size_t pcgrl_get_smb_play_bytes(const pcgrl_config* c, int32_t count, int32_t max_len) {
+    if (!c || c->prob != PCGRL_SMB || count < 1 || max_len < 1) return 0;
+    pcgrl_config one = *c;
+    one.num_envs = 1;                    // (the workspace does not depend on the handle's batch)
+    if (validate_config(&one) != PCGRL_OK) return 0;
+    return smb_play_plan(&one, count).total;
+}
+int pcgrl_get_smb_play(pcgrl_env* h, const uint8_t* maps, int32_t count, int32_t max_len, int8_t* moves_out, int32_t* length_out, int8_t* agent_out,
+                       int32_t* rows_out, void* work, size_t work_bytes, void* stream) {
+    if (!h || !h->bound) return PCGRL_ESTATE;
+    if (!maps || !moves_out || !length_out || !work || count < 1 || max_len < 1 || ((uintptr_t)work & 255) != 0) return PCGRL_EINVAL;
+    const size_t need = pcgrl_get_smb_play_bytes(&h->cfg, count, max_len);
+    if (need == 0 || work_bytes < need) return PCGRL_EINVAL;
+    DeviceGuard guard(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    const SmbPlayPlan S = smb_play_plan(&h->cfg, count);
+    uint8_t* w = (uint8_t*)work;
+    int32_t* head = at<int32_t>(w, S.head);
+    int32_t* rows = rows_out ? rows_out : at<int32_t>(w, S.rows);
+    HIPCHK(hipMemsetAsync(head, 0, S.head.bytes, st));
+    HIPCHK(hipMemsetAsync(moves_out, 0xFF, (size_t)count * (size_t)max_len, st));      // -1 beyond the play: the kernel stores the moves only
+    const SolOut out = {moves_out, length_out, agent_out, max_len};
+    return launch_smb_play(h, maps, count, rows, out, head, at<uint8_t>(w, S.arenas), S.slots, st);
 }
 
 }  // extern "C"

@@ -77,10 +77,11 @@ class Solutions:
 
 
 class Playthroughs:
-    """What BatchedPcgrlEnv.playthrough() returns: `moves` int8 [M, max_len] (mdungeon 0..3 = left, right, up, down; ddave 0..3 =
-    stay, left, right, jump; -1 beyond the play), `length` int32 [M] (the depth of the node the statistics come from, also beyond
-    max_len), `agent` int8 [M] (-2 the planner did not run, -1 no agent won, 0..3 = A*(1), A*(0.5), A*(0), BFS), `rows` / `stats` as
-    in an Evaluation; `truncated` bool [M]: the row holds only a prefix; `won` bool [M]: an agent won."""
+    """What BatchedPcgrlEnv.playthrough() and playthrough_smb() return: `moves` int8 [M, max_len] (mdungeon 0..3 = left, right, up,
+    down; ddave 0..3 = stay, left, right, jump; smb 0..3 = stay, right, jump, right + jump; -1 beyond the play), `length` int32 [M]
+    (the depth of the node the statistics come from, also beyond max_len), `agent` int8 [M] (-2 the planner did not run, -1 no agent
+    won, 0..3 = A*(1), A*(0.5), A*(0), BFS; smb: -1 nobody won, 0 = A*(1), 1 = A*(0), never -2), `rows` / `stats` as in an
+    Evaluation; `truncated` bool [M]: the row holds only a prefix; `won` bool [M]: an agent won."""
     __slots__ = ("moves", "length", "agent", "rows", "stats")
 
     def __init__(self, moves, length, agent, rows, stats):
@@ -816,7 +817,8 @@ class BatchedPcgrlEnv:
         torch = self._torch
         if self._prob.name not in ("mdungeon", "ddave"):
             raise NotImplementedError("playthrough(): the plays of mdungeon and ddave only, not problem %r%s"
-                                      % (self._prob.name, " (solve() returns sokoban's solution)" if self._prob.name == "sokoban" else ""))
+                                      % (self._prob.name, " (solve() returns sokoban's solution)" if self._prob.name == "sokoban" else
+                                         " (playthrough_smb() returns smb's play)" if self._prob.name == "smb" else ""))
         if maps is None:
             if self._handle is None or not self._was_reset or self._needs_reset:
                 raise RuntimeError("playthrough() without maps reads the environment's current levels: call reset() first")
@@ -857,6 +859,62 @@ class BatchedPcgrlEnv:
         _lib.check(self._lib.pcgrl_get_playthrough(self._handle, C.c_void_p(m.data_ptr()), M, max_len, C.c_void_p(moves.data_ptr()),
                                                    C.c_void_p(length.data_ptr()), C.c_void_p(agent.data_ptr()), C.c_void_p(rows.data_ptr()),
                                                    C.c_void_p(self._eval_work.data_ptr()), self._eval_work.numel(), self._stream()), "pcgrl_get_playthrough")
+        return Playthroughs(moves, length, agent, rows, self._prob.decode_rows(rows))
+
+    # ---- the play that SMBProblem._run_game scores (pcgrl_get_smb_play)
+    def playthrough_smb(self, maps=None, max_len=None):
+        """The play behind smb's `jumps`, `jumps-dist` and `dist-win` for `maps` -- array-like uint8 [M, H, W] as for evaluate(); None:
+        this environment's current levels (after a reset(); the handle's own map buffer is read in place) -- with the parameters in
+        force: the moves of A*(balance 1) if it wins, else of A*(balance 0) -- to its winning node, or, when nobody wins, to its best
+        node, the state `dist-win` is measured from.  Moves are 0 stay, 1 right, 2 jump, 3 right + jump.  `max_len`: columns of the move
+        rows, by default min(solver_power, 255).  Returns Playthroughs (moves, length, agent, rows, stats), all on the device; agent is
+        0, 1 or -1.  A pure function like evaluate(): episodes, random streams and the kept play-throughs of the step are not touched,
+        a tile id >= get_num_tiles() is clamped on the way and reported by check_status(), nothing is waited for; the workspace is
+        evaluate()'s (the same one-stream rule).  solver_power is smb's attribute (prob._solver_power, then adjust_param()).
+        NotImplementedError for the other problems (mdungeon, ddave: playthrough(); sokoban: solve())."""
+        torch = self._torch
+        if self._prob.name != "smb":
+            raise NotImplementedError("playthrough_smb(): smb's play only, not problem %r%s"
+                                      % (self._prob.name, " (solve() returns sokoban's solution)" if self._prob.name == "sokoban" else
+                                         " (playthrough() returns its play)" if self._prob.name in ("mdungeon", "ddave") else ""))
+        if maps is None:
+            if self._handle is None or not self._was_reset or self._needs_reset:
+                raise RuntimeError("playthrough_smb() without maps reads the environment's current levels: call reset() first")
+        dims = (self._prob._width, self._prob._height)
+        if self._handle is None or (not self._was_reset and (self._realloc or dims != self._alloc_dims)):
+            self._allocate()               # (as in evaluate(): bound, not reset)
+            self._realloc = False
+        if self._realloc:
+            raise NotImplementedError("playthrough_smb(): an adjust_param() that this handle could not take in place waits for the next reset(); "
+                                      "the handle still plans with the old parameters")
+        w, h = self._alloc_dims
+        if maps is None:
+            m = self._bufs["map"]
+        else:
+            m = maps if torch.is_tensor(maps) else torch.as_tensor(np.asarray(maps))
+            if m.dim() != 3:
+                raise ValueError("playthrough_smb(): maps must be [M, H, W], got shape %s" % (tuple(m.shape),))
+            if tuple(m.shape[1:]) != (h, w) or m.shape[0] < 1:
+                raise ValueError("playthrough_smb(): maps of shape %s for an environment of %d rows x %d columns (at least one map)" % (tuple(m.shape), h, w))
+            m = m.to(device=self.device, dtype=torch.uint8).contiguous()
+        M = int(m.shape[0])
+        power = int(self._prob._solver_power)
+        max_len = min(power, 255) if max_len is None else int(max_len)
+        if max_len < 1:
+            raise ValueError("playthrough_smb(): max_len must be at least 1, got %d" % max_len)
+        cfg = self._config(self._alloc_dims)
+        need = int(self._lib.pcgrl_get_smb_play_bytes(C.byref(cfg), M, max_len))
+        if not need:
+            raise NotImplementedError("playthrough_smb(): the library does not take this configuration (width %d, height %d, solver_power %d)" % (w, h, power))
+        moves = torch.empty((M, max_len), dtype=torch.int8, device=self.device)
+        length = torch.empty((M,), dtype=torch.int32, device=self.device)
+        agent = torch.empty((M,), dtype=torch.int8, device=self.device)
+        rows = torch.empty((M, 8), dtype=torch.int32, device=self.device)
+        if self._eval_work is None or self._eval_work.numel() < need:
+            self._eval_work = torch.empty((need,), dtype=torch.uint8, device=self.device)
+        _lib.check(self._lib.pcgrl_get_smb_play(self._handle, C.c_void_p(m.data_ptr()), M, max_len, C.c_void_p(moves.data_ptr()),
+                                                C.c_void_p(length.data_ptr()), C.c_void_p(agent.data_ptr()), C.c_void_p(rows.data_ptr()),
+                                                C.c_void_p(self._eval_work.data_ptr()), self._eval_work.numel(), self._stream()), "pcgrl_get_smb_play")
         return Playthroughs(moves, length, agent, rows, self._prob.decode_rows(rows))
 
     def _evaluate_by_set_maps(self, m, rows, chunk):

@@ -19,6 +19,7 @@
  *   pcgrl_get_stats / pcgrl_get_reward   Problem.get_stats / get_reward / get_episode_over called on any level, outside an episode
  *   pcgrl_get_solution               SokobanProblem.get_stats(map)["solution"] sokoban_prob.py:133-145: the planner's moves
  *   pcgrl_get_playthrough            the moves of the play _run_game scores, mdungeon_prob.py:100-138 / ddave_prob.py:92-127
+ *   pcgrl_get_smb_play               the same for smb's two agents, smb_prob.py:90-124
  *
  * Conventions: plain pointers and sizes only; every function returns 0 on success or a negative
  * PCGRL_E* code (no exceptions cross the ABI); all device buffers are OWNED BY THE CALLER (hipMalloc,
@@ -49,7 +50,8 @@ extern "C" {
  *     a caller detects them by the symbol pcgrl_get_stats.
  *     Still 15: + pcgrl_get_solution_bytes / pcgrl_get_solution -- additive in the same way; detected by the symbol pcgrl_get_solution.
  *     Still 15: + pcgrl_get_playthrough_bytes / pcgrl_get_playthrough -- additive in the same way; detected by the symbol
- *     pcgrl_get_playthrough. */
+ *     pcgrl_get_playthrough.
+ *     Still 15: + pcgrl_get_smb_play_bytes / pcgrl_get_smb_play -- additive in the same way; detected by the symbol pcgrl_get_smb_play. */
 #define PCGRL_ABI_VERSION 15
 #define PCGRL_OK 0
 #define PCGRL_EINVAL (-1)   /* bad argument / unsupported configuration */
@@ -371,6 +373,29 @@ size_t pcgrl_get_playthrough_bytes(const pcgrl_config* cfg, int32_t count, int32
 int    pcgrl_get_playthrough(pcgrl_env* env, const uint8_t* maps, int32_t count, int32_t max_len,
                              int8_t* moves_out, int32_t* length_out, int8_t* agent_out, int32_t* rows_out,
                              void* work, size_t work_bytes, void* stream);
+/* The play behind smb's `jumps`, `jumps-dist` and `dist-win`.  SMBProblem._run_game (smb_prob.py:90-124) runs AStarAgent with balance 1
+ * and, if its node does not win, with balance 0, and takes the statistics from the last node returned; this entry returns that node's
+ * moves, node.getActions() (smb/engine.py:43-49): the winner's, or -- when nobody wins -- those that lead to the second agent's best
+ * node, the state `dist-win` is measured from.  The contract is pcgrl_get_playthrough's: a bound handle, no reset needed, no episode
+ * state read or written, of the handle only the sticky status word written (a tile id >= 7 is clamped on the way), asynchronous.
+ *   maps        DEVICE u8 [count,H,W], read only.
+ *   max_len     columns of a row of moves_out, >= 1.
+ *   moves_out   DEVICE i8 [count,max_len]: move i as the index into the engine's `directions` -- 0 stay, 1 right, 2 jump, 3 right +
+ *               jump -- for i < min(length, max_len); -1 from there to the end of the row.
+ *   length_out  DEVICE i32 [count]: the depth of the returned node, also when it is > max_len (the row then holds the first max_len
+ *               moves).  0 for a level of height 3, where the root already wins.
+ *   agent_out   DEVICE i8 [count] or NULL: 0 = AStarAgent with balance 1 won, 1 = with balance 0, -1 = nobody (never -2: smb's planner
+ *               always runs).
+ *   rows_out    DEVICE i32 [count,8] or NULL: the statistics rows of these maps, as a step or pcgrl_set_maps leaves them in `stats`.
+ *   work        DEVICE, 256-byte aligned, at least pcgrl_get_smb_play_bytes(cfg, count, max_len) bytes; the call's own.
+ *   PCGRL_EINVAL: a NULL maps / moves_out / length_out / work, count < 1, max_len < 1, work not 256-byte aligned or too small, or a
+ *   configuration for which pcgrl_get_smb_play_bytes is 0.
+ * pcgrl_get_smb_play_bytes: from the configuration alone.  Non-zero (then >= 256) exactly for the smb configurations pcgrl_create takes,
+ *   with count >= 1 and max_len >= 1: every width <= 250, height 3..32 and solver_power <= 16383. */
+size_t pcgrl_get_smb_play_bytes(const pcgrl_config* cfg, int32_t count, int32_t max_len);
+int    pcgrl_get_smb_play(pcgrl_env* env, const uint8_t* maps, int32_t count, int32_t max_len,
+                          int8_t* moves_out, int32_t* length_out, int8_t* agent_out, int32_t* rows_out,
+                          void* work, size_t work_bytes, void* stream);
 /* ActionMap.step for the wide representation (wrappers.py:139-154): flat DEVICE i32 [N] index into
  * (H, W, tiles) -> xyv DEVICE i32 [N,3] = (x, y, tile), the action pcgrl_step takes. */
 int pcgrl_action_map(pcgrl_env* env, const int32_t* flat, int32_t* xyv, void* stream);

@@ -1,0 +1,197 @@
+"""smb's play-through moves without a GPU: the host replay replay_smb() on every play of tests/golden/playthroughs_smb.npz (the
+reference's agents' moves) against the statistics rows they belong to, hand cases of the engine's rules, and the host side of
+pcgrl_get_smb_play_bytes / pcgrl_get_smb_play."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+G = os.path.join(HERE, "golden")
+FILES = ["4x9_p200", "6x12_p10000", "8x24_p400", "10x30_p10000", "14x40_p2500", "14x114_p1500", "14x114_p10000"]
+EDGES = ["w123", "w250", "h3", "p16383", "q4095"]
+JUMPS, JDIST, DIST = 5, 6, 7          # columns of a statistics row
+
+
+@pytest.fixture(scope="module")
+def play():
+    return np.load(os.path.join(G, "playthroughs_smb.npz"))
+
+
+def groups(play):
+    """(name, maps, stats, agents, power, moves, length) of every fixture file and every edge group."""
+    for f in FILES:
+        d = np.load(os.path.join(G, "stats_smb_%s.npz" % f))
+        yield f, d["maps"], d["stats"], d["agents"], int(d["solver_power"]), play["moves_" + f], play["length_" + f]
+    for e in EDGES:
+        k = "edge_%s_" % e
+        yield "edge_" + e, play[k + "maps"], play[k + "stats"], play[k + "agents"], int(play[k + "power"]), play[k + "moves"], play[k + "length"]
+
+
+def jumps_dist(cols, width):
+    """smb_prob.py:140-146 on the jump columns."""
+    prev, value = 0, 0
+    for c in cols:
+        value = max(value, int(c) - prev)
+        prev = int(c)
+    return max(value, width - prev)
+
+
+def check_replay(m, moves, length, agent, st):
+    """The moves are legal by the engine's rules and end in the state the statistics row describes."""
+    from gym_pcgrl_amd import replay_smb
+    k = int((moves >= 0).sum())
+    assert k == min(length, moves.shape[0]) and (moves[:k] >= 0).all() and (moves[k:] == -1).all()
+    r = replay_smb(m, moves)
+    H, W = m.shape
+    assert r.player.shape == (k + 1, 2) and r.air.shape == (k + 1,) and r.jumps.shape == (k + 1,)
+    assert r.player[0].tolist() == [1, H - 3] and not r.lost
+    if k < length:
+        return r                                                        # a truncated row: a legal prefix
+    assert r.won == (agent >= 0), (agent, r.player[-1])
+    assert r.jumps[-1] == st[JUMPS] == len(r.jump_cols) and jumps_dist(r.jump_cols, W) == st[JDIST], (st, r.jump_cols)
+    assert (0 if r.won else r.dist_win) == st[DIST], (st, r.player[-1])
+    if r.won and k > 0:
+        assert not replay_smb(m, moves[:k - 1]).won                     # not before the last move
+    return r
+
+
+def test_fixture_shapes_and_tally(play):
+    longest = 0
+    for name, maps, stats, agents, power, moves, length in groups(play):
+        n = maps.shape[0]
+        assert moves.dtype == np.int8 and length.dtype == np.int32 and moves.shape[0] == n == length.shape[0] == stats.shape[0] == agents.shape[0]
+        assert np.array_equal((moves >= 0).sum(1), length) and moves.shape[1] == max(1, int(length.max()))
+        assert set(np.unique(agents[:, 4]).tolist()) <= {-1, 0, 1} and int(moves.max()) <= 3
+        if name == "edge_h3":
+            assert (agents[:, 4] == 0).all() and (length == 0).all()
+        elif name.startswith("edge_"):
+            assert all((agents[:, 4] == a).any() for a in (-1, 0, 1)), name
+        if not name.startswith("edge_"):
+            longest = max(longest, int(length.max()))
+    assert longest == 136
+    assert play["edge_w123_maps"].shape[2] + 6 > 128 and play["edge_w250_maps"].shape[2] == 250 and int(play["edge_p16383_power"]) == 16383
+    assert play["edge_q4095_maps"].shape[2] + 6 == 128 and int(play["edge_q4095_power"]) < 16383
+
+
+def test_replay_smb_of_every_fixture_play(play):
+    n = 0
+    for name, maps, stats, agents, power, moves, length in groups(play):
+        for i in range(maps.shape[0]):
+            check_replay(maps[i], moves[i], int(length[i]), int(agents[i, 4]), stats[i])
+            n += 1
+    assert n == 301 + 6 + 5 + 4 + 5 + 5
+
+
+def test_replay_rules():
+    from gym_pcgrl_amd import replay_smb
+    flat = np.zeros((5, 6), np.uint8)
+    flat[3:] = 1
+    r = replay_smb(flat, [1] * 9)                                       # the pole's block stands in the player's row: the floor ends in front of it
+    assert not r.won and not r.lost and r.player[:, 0].tolist() == list(range(1, 10)) + [9] and (r.player[:, 1] == 2).all() and r.dist_win == 1
+    r = replay_smb(flat, [1] * 8 + [3, 3])                              # ... and a jump from there reaches the pole's column W + 4 = 10
+    assert r.won and r.player[-2:].tolist() == [[9, 1], [10, 0]] and r.jump_cols.tolist() == [9] and r.dist_win == 0
+    assert replay_smb(flat, [1] * 8 + [3, 3, 1, 3]).player[-1].tolist() == [10, 0]    # nothing moves once the game is over
+    assert replay_smb(flat, [1, -1, 1]).player.shape[0] == 2                          # a negative entry ends the list
+    # a wall: right against it is stay; a jump rises four cells, hovers, and comes down again
+    wall = flat.copy()
+    wall[:3, 2] = 1                                                                   # engine column 5, the full height of the screen
+    r = replay_smb(wall, [1, 1, 1, 1, 1])
+    assert r.player[:, 0].tolist() == [1, 2, 3, 4, 4, 4] and not r.won and r.dist_win == 6
+    r = replay_smb(wall, [1, 1, 1, 2, 2, 2, 2, 0, 0])                                 # at the wall: up four (two of them above the screen)
+    assert r.player[3:, 1].tolist() == [2, 1, 0, -1, -2, -2, -1] and r.air[3:].tolist() == [0, 4, 3, 2, 1, 0, 0]
+    assert r.jumps[-1] == 1 and r.jump_cols.tolist() == [4]
+    r = replay_smb(wall, [1, 1, 1, 3, 3, 3, 3, 1, 1])                                 # ... and over the wall from above the screen
+    assert r.player[-1].tolist() == [7, -1] and r.jumps[-1] == 1
+    r = replay_smb(wall, [1, 1, 1, 2, 0])                                             # a move without jump cuts the jump: air time 1, then hover
+    assert r.air.tolist() == [0, 0, 0, 0, 4, 0] and r.player[-1].tolist() == [4, 1]
+    # a jump under a ceiling does not start; a jump into a ceiling ends with air time 1
+    low = flat.copy()
+    low[1, 0] = 3                                                                     # engine column 3, right above the player's row
+    r = replay_smb(low, [1, 1, 2])
+    assert r.jumps[-1] == 0 and r.player[-1].tolist() == [3, 2] and r.air[-1] == 0
+    low2 = flat.copy()
+    low2[0, 0] = 4                                                                    # two cells above
+    r = replay_smb(low2, [1, 1, 2, 2])
+    assert r.jumps[-1] == 1 and r.player[3:, 1].tolist() == [1, 1] and r.air[3:].tolist() == [4, 1]
+    # a pit: the player falls, still moving right, to the last row and stays there (nothing can be entered below the grid, and the
+    # floor's side is a wall), neither won nor lost
+    pit = flat.copy()
+    pit[3:, 1:3] = 0
+    r = replay_smb(pit, [1, 1, 1, 1, 1, 1])
+    assert r.player.tolist() == [[1, 2], [2, 2], [3, 2], [4, 3], [5, 4], [5, 4], [5, 4]] and not r.won and not r.lost and r.dist_win == 5
+    r = replay_smb(pit, [1, 1, 3, 3, 3, 3, 1, 1, 1, 1])                               # ... and is jumped, from its edge onto the pole's block
+    assert r.won and r.player[-1].tolist() == [10, 0] and r.player[:, 1].min() == -2 and r.jump_cols.tolist() == [3]
+    # height 3: no pole, the start counts as won, nothing moves
+    r = replay_smb(np.zeros((3, 4), np.uint8), [1, 1])
+    assert r.won and r.player.tolist() == [[1, 0]] * 3
+    with pytest.raises(ValueError):
+        replay_smb(flat, [4])
+    with pytest.raises(ValueError):
+        replay_smb(np.full((5, 6), 7, np.uint8), [0])
+    with pytest.raises(ValueError):
+        replay_smb(np.zeros((2, 6), np.uint8), [0])
+    with pytest.raises(ValueError):
+        replay_smb(np.zeros(6, np.uint8), [0])
+
+
+# ------------------------------------------------------------------ the ABI, without a device
+def _config(prob, h, w, power=None):
+    from gym_pcgrl_amd.envs import BatchedPcgrlEnv
+    env = BatchedPcgrlEnv(prob=prob, rep="wide", num_envs=1, seed=0)
+    if power is not None:
+        env._prob._solver_power = int(power)
+    env.adjust_param(width=w, height=h)
+    return env._config()
+
+
+def _bytes(cfg, count, max_len):
+    from gym_pcgrl_amd import _lib
+    return int(_lib.load().pcgrl_get_smb_play_bytes(C.byref(cfg), count, max_len))
+
+
+def test_declared_exported_and_mirrored():
+    from gym_pcgrl_amd import _lib
+    hdr = open(os.path.join(ROOT, "include", "pcgrl_hip.h")).read()
+    plain = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    assert re.search(r"\bsize_t\s+pcgrl_get_smb_play_bytes\s*\(\s*const\s+pcgrl_config\s*\*\s*\w+\s*,\s*int32_t\s+\w+\s*,\s*int32_t\s+\w+\s*\)\s*;", plain)
+    assert re.search(r"\bint\s+pcgrl_get_smb_play\s*\(\s*pcgrl_env\s*\*\s*\w+\s*,\s*const\s+uint8_t\s*\*\s*\w+\s*,\s*int32_t\s+\w+\s*,\s*int32_t\s+\w+\s*,"
+                     r"\s*int8_t\s*\*\s*\w+\s*,\s*int32_t\s*\*\s*\w+\s*,\s*int8_t\s*\*\s*\w+\s*,\s*int32_t\s*\*\s*\w+\s*,"
+                     r"\s*void\s*\*\s*\w+\s*,\s*size_t\s+\w+\s*,\s*void\s*\*\s*\w+\s*\)\s*;", plain)
+    for cited in ("smb_prob.py:90-124", "engine.py:43-49", "Still 15: + pcgrl_get_smb_play_bytes / pcgrl_get_smb_play"):
+        assert cited in hdr, cited
+    L = _lib.load()
+    for name in ("pcgrl_get_smb_play_bytes", "pcgrl_get_smb_play"):
+        assert name in _lib.EXPORTS and hasattr(L, name), name
+    assert L.pcgrl_abi_version() == _lib.ABI_VERSION == 15
+    assert L.pcgrl_get_smb_play_bytes.argtypes == [C.POINTER(_lib.Config), C.c_int32, C.c_int32] and L.pcgrl_get_smb_play_bytes.restype == C.c_size_t
+    assert len(L.pcgrl_get_smb_play.argtypes) == 11
+    # refused without a handle, not crashed
+    assert L.pcgrl_get_smb_play(None, None, 1, 1, None, None, None, None, None, 0, None) == _lib.PCGRL_ESTATE
+
+
+def test_workspace_sizes():
+    from gym_pcgrl_amd import _lib
+    L = _lib.load()
+    for other in ("binary", "zelda", "sokoban", "mdungeon", "ddave"):
+        assert _bytes(_config(other, 5, 5), 64, 16) == 0, other
+    assert int(L.pcgrl_get_smb_play_bytes(None, 4, 4)) == 0
+    cfg = _config("smb", 14, 114)
+    assert _bytes(cfg, 64, 0) == 0 and _bytes(cfg, 64, -1) == 0 and _bytes(cfg, 0, 16) == 0 and _bytes(cfg, -3, 16) == 0
+    # every smb configuration the library takes has the form: the smallest, the largest, the largest solver_power
+    for h, w, power in ((3, 1, 1), (3, 1, None), (32, 250, None), (32, 250, 16383), (14, 114, 16383)):
+        assert _bytes(_config("smb", h, w, power), 1, 1) >= 256, (h, w, power)
+    # ... and the other problems' entries keep refusing smb
+    assert int(L.pcgrl_get_playthrough_bytes(C.byref(cfg), 64, 16)) == 0 and int(L.pcgrl_get_stats_bytes(C.byref(cfg), 64)) == 0
+    for cfg in (_config("smb", 4, 9, 200), _config("smb", 14, 114), _config("smb", 32, 250, 16383)):
+        last = 0
+        for count in (1, 15, 16, 17, 63, 64, 65, 4095, 4096, 4097, 65536):
+            sizes = [_bytes(cfg, count, ml) for ml in (1, 4, 72, 255, 5000)]
+            assert sizes[0] >= 256 and sizes[0] % 256 == 0 and sizes == sorted(sizes), (count, sizes)
+            assert sizes[0] >= last
+            last = sizes[0]
+    # a larger solver_power never takes less
+    assert _bytes(_config("smb", 14, 114, 16383), 64, 16) > _bytes(_config("smb", 14, 114, 400), 64, 16)
