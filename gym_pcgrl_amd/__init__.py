@@ -70,41 +70,40 @@ def make_batched(env_id, num_envs, **kwargs):
     return BatchedPcgrlEnv(prob=prob, rep=rep, num_envs=num_envs, **kwargs)
 
 
-def evaluate_levels(prob, maps, device=None, **params):
-    """Problem.get_stats of a stack of levels in one call: `maps` array-like uint8 [M, H, W] (width and height are taken from it),
-    `params` as for adjust_param (smb: solver_power is set as an attribute, smb_prob.py:40-53 has no such key).  Returns
-    BatchedPcgrlEnv.evaluate()'s Evaluation (rows, stats)."""
+def _on_levels(who, prob, maps, device, params, call, smb_power=None):
+    """What the *_levels() functions share: the shape check, a one-environment handle of the levels' width and height with `params`
+    applied (adjust_param), `call(env)`, close().  `smb_power`: where smb's solver_power -- an attribute, smb_prob.py:40-53 has no
+    such key -- is set: "before" or "after" that adjust_param (then followed by one more), None: it stays in `params`."""
     import numpy as np
     from .envs import BatchedPcgrlEnv
     shape = tuple(maps.shape) if hasattr(maps, "shape") else np.asarray(maps).shape
     if len(shape) != 3:
-        raise ValueError("evaluate_levels(): maps must be [M, H, W], got shape %s" % (shape,))
+        raise ValueError("%s(): maps must be [M, H, W], got shape %s" % (who, shape))
     env = BatchedPcgrlEnv(prob=prob, rep="wide", num_envs=1, device=device, seed=0, auto_reset=False)
     try:
-        power = params.pop("solver_power", None) if prob == "smb" else None
+        power = params.pop("solver_power", None) if smb_power and prob == "smb" else None
+        if power is not None and smb_power == "before":
+            env._prob._solver_power = int(power)
         env.adjust_param(width=int(shape[2]), height=int(shape[1]), **params)
-        if power is not None:
+        if power is not None and smb_power == "after":
             env._prob._solver_power = int(power)
             env.adjust_param()
-        return env.evaluate(maps)
+        return call(env)
     finally:
         env.close()
+
+
+def evaluate_levels(prob, maps, device=None, **params):
+    """Problem.get_stats of a stack of levels in one call: `maps` array-like uint8 [M, H, W] (width and height are taken from it),
+    `params` as for adjust_param (smb: solver_power is set as an attribute, smb_prob.py:40-53 has no such key).  Returns
+    BatchedPcgrlEnv.evaluate()'s Evaluation (rows, stats)."""
+    return _on_levels("evaluate_levels", prob, maps, device, params, lambda env: env.evaluate(maps), smb_power="after")
 
 
 def solve_levels(prob, maps, device=None, max_len=None, **params):
     """SokobanProblem.get_stats(map)["solution"] of a stack of levels in one call, next to evaluate_levels(): `maps` array-like uint8
     [M, H, W], `params` as for adjust_param.  Returns BatchedPcgrlEnv.solve()'s Solutions (moves, length, agent, rows, stats)."""
-    import numpy as np
-    from .envs import BatchedPcgrlEnv
-    shape = tuple(maps.shape) if hasattr(maps, "shape") else np.asarray(maps).shape
-    if len(shape) != 3:
-        raise ValueError("solve_levels(): maps must be [M, H, W], got shape %s" % (shape,))
-    env = BatchedPcgrlEnv(prob=prob, rep="wide", num_envs=1, device=device, seed=0, auto_reset=False)
-    try:
-        env.adjust_param(width=int(shape[2]), height=int(shape[1]), **params)
-        return env.solve(maps, max_len=max_len)
-    finally:
-        env.close()
+    return _on_levels("solve_levels", prob, maps, device, params, lambda env: env.solve(maps, max_len=max_len))
 
 
 class SokobanReplay:
@@ -169,17 +168,7 @@ def playthrough_levels(prob, maps, device=None, max_len=None, **params):
     """The play behind the mdungeon / ddave planner statistics of a stack of levels in one call, next to solve_levels(): `maps`
     array-like uint8 [M, H, W], `params` as for adjust_param.  Returns BatchedPcgrlEnv.playthrough()'s Playthroughs (moves, length,
     agent, rows, stats)."""
-    import numpy as np
-    from .envs import BatchedPcgrlEnv
-    shape = tuple(maps.shape) if hasattr(maps, "shape") else np.asarray(maps).shape
-    if len(shape) != 3:
-        raise ValueError("playthrough_levels(): maps must be [M, H, W], got shape %s" % (shape,))
-    env = BatchedPcgrlEnv(prob=prob, rep="wide", num_envs=1, device=device, seed=0, auto_reset=False)
-    try:
-        env.adjust_param(width=int(shape[2]), height=int(shape[1]), **params)
-        return env.playthrough(maps, max_len=max_len)
-    finally:
-        env.close()
+    return _on_levels("playthrough_levels", prob, maps, device, params, lambda env: env.playthrough(maps, max_len=max_len))
 
 
 class MdungeonReplay:
@@ -323,20 +312,7 @@ def playthrough_smb_levels(maps, device=None, max_len=None, **params):
     """The play behind smb's jumps / jumps-dist / dist-win of a stack of levels in one call, next to playthrough_levels(): `maps`
     array-like uint8 [M, H, W], `params` as for adjust_param plus solver_power (set as an attribute: smb_prob.py:40-53 has no such
     key).  Returns BatchedPcgrlEnv.playthrough_smb()'s Playthroughs (moves, length, agent, rows, stats)."""
-    import numpy as np
-    from .envs import BatchedPcgrlEnv
-    shape = tuple(maps.shape) if hasattr(maps, "shape") else np.asarray(maps).shape
-    if len(shape) != 3:
-        raise ValueError("playthrough_smb_levels(): maps must be [M, H, W], got shape %s" % (shape,))
-    env = BatchedPcgrlEnv(prob="smb", rep="wide", num_envs=1, device=device, seed=0, auto_reset=False)
-    try:
-        power = params.pop("solver_power", None)
-        if power is not None:
-            env._prob._solver_power = int(power)
-        env.adjust_param(width=int(shape[2]), height=int(shape[1]), **params)
-        return env.playthrough_smb(maps, max_len=max_len)
-    finally:
-        env.close()
+    return _on_levels("playthrough_smb_levels", "smb", maps, device, params, lambda env: env.playthrough_smb(maps, max_len=max_len), smb_power="before")
 
 
 class SmbReplay:

@@ -207,15 +207,12 @@ def load():
     L.pcgrl_get_stats_bytes.restype = C.c_size_t
     L.pcgrl_get_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     L.pcgrl_get_reward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.pcgrl_get_solution_bytes.argtypes = [C.POINTER(Config), C.c_int32, C.c_int32]
-    L.pcgrl_get_solution_bytes.restype = C.c_size_t
-    L.pcgrl_get_solution.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    L.pcgrl_get_playthrough_bytes.argtypes = [C.POINTER(Config), C.c_int32, C.c_int32]
-    L.pcgrl_get_playthrough_bytes.restype = C.c_size_t
-    L.pcgrl_get_playthrough.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    L.pcgrl_get_smb_play_bytes.argtypes = [C.POINTER(Config), C.c_int32, C.c_int32]
-    L.pcgrl_get_smb_play_bytes.restype = C.c_size_t
-    L.pcgrl_get_smb_play.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    # handle, maps, count, max_len, moves, length, agent, rows, work, work_bytes, stream
+    moves_args = (C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
+    for name in ("pcgrl_get_solution", "pcgrl_get_playthrough", "pcgrl_get_smb_play"):
+        getattr(L, name + "_bytes").argtypes = [C.POINTER(Config), C.c_int32, C.c_int32]
+        getattr(L, name + "_bytes").restype = C.c_size_t
+        getattr(L, name).argtypes = list(moves_args)
     L.pcgrl_action_map.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pcgrl_step_flat.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pcgrl_selftest_heap.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -1,32 +1,78 @@
-// pcgrl_get_playthrough: the play that the MiniDungeons and Dangerous Dave statistics describe.  _run_game (mdungeon_prob.py:100-138,
-// ddave_prob.py:92-127) asks its agents for node.getActions() (mdungeon/engine.py:43-49) and keeps only len(sol) and the game status of
-// the returned state; this kernel keeps the moves: the first winner's, or -- when nobody wins -- those that lead to the BFS agent's
-// best node, the state the statistics row is taken from.  Part of the single translation unit pcgrl_abi.hip.
-// The job list is the one k_get_stats<PROB> makes (kernels_evaluate.h); k_get_playthrough is k_get_stats_search with the traced
-// searches (PlayTrace, mdungeon_solver.h): a chunk ticket, eight wavefronts try the jobs in the small regions, wavefront 0 redoes what
-// the small limit stopped in the full region with the full solver_power.  Beside its node pool every block has as many trace words
-// (parent | move << 30), cut from the caller's workspace and indexed like the pool -- for the three searches whose nodes have no room;
-// the compact mdungeon search keeps the same word in MdFastNode's free `pad` and stores nothing beside the node.  Right after the agent that ends a game returns,
-// while that wavefront's pool and trace words still hold the search, one lane walks the parent chain from the returned node and
-// writes the row.  Only a run whose result is accepted writes: a try that was "not final" leaves row, length and agent as they are.
-// The rows are filled with -1, the lengths with 0 and the agents with -2 before the launch (pcgrl_get_playthrough): a level whose
+// pcgrl_get_solution / pcgrl_get_playthrough: the moves behind the planner's statistics.  Part of the single translation unit
+// pcgrl_abi.hip.
+//   sokoban            SokobanProblem.get_stats(map)["solution"] (sokoban_prob.py:133-145): the moves of the first agent of _run_game
+//                      (:104-122) that wins, Node.getActions (engine.py:38-44).  Nobody wins: nothing is written.
+//   mdungeon / ddave   _run_game (mdungeon_prob.py:100-138, ddave_prob.py:92-127) asks its agents for node.getActions()
+//                      (mdungeon/engine.py:43-49) and keeps only len(sol) and the game status of the returned state; this kernel keeps
+//                      the moves: the first winner's, or -- when nobody wins -- those that lead to the BFS agent's best node, the state
+//                      the statistics row is taken from.
+// The job list is the one k_get_stats<PROB> makes (kernels_evaluate.h); k_get_moves is k_get_stats_search with the traced searches
+// (SokTrace, sokoban_solver.h; PlayTrace, mdungeon_solver.h): a chunk ticket, eight wavefronts try the jobs in the small regions,
+// wavefront 0 redoes what the small limit stopped in the full region with the full solver_power.  Sokoban's searches record parent and
+// move in free bits of their nodes, and so does the compact mdungeon search (MdFastNode's free `pad`).  For the three searches whose
+// nodes have no room every block has, beside its node pool, as many trace words (parent | move << 30), cut from the caller's workspace
+// and indexed like the pool; sokoban is launched without them.  Right after the agent that ends a game returns, while that
+// wavefront's pool and trace words still hold the search, one lane walks the parent chain from the returned node and writes the row.
+// Only a run whose result is accepted writes: a try that was "not final" leaves row, length and agent as they are.
+// The rows are filled with -1, the lengths with 0 and the agents with -2 before the launch (moves_call / get_moves, pcgrl_abi.hip): a level whose
 // planner does not run is never seen here.
 // The trace store is one global store per filed child that nothing waits for before the walk (the __threadfence() in front of it):
 // it is not on the search's chain of dependent pops.
-// playthrough_game_run and k_get_playthrough repeat search_game_run (search_game.h) and k_get_stats_search (kernels_evaluate.h) on
-// purpose, for the reason kernels_solution.h gives: one body with an agent / finish policy changes the machine code of k_step_solver
-// and k_get_stats_search, and those kernels have to stay what they are.  A change to the ticket, the small tries or the redo there
-// has to be made here as well.  The traced searches are instantiated in this kernel only.
+// moves_game_run and k_get_moves repeat search_game_run (search_game.h) and k_get_stats_search (kernels_evaluate.h) on purpose: one
+// body with an agent / finish policy for the untraced side as well was tried and changed the machine code of k_step_solver and
+// k_get_stats_search (the compiler schedules the inlined loop differently), and those kernels have to stay what they are.  So the
+// loop exists twice, there and here: a change to the ticket, the small tries or the redo there has to be made here as well.  The
+// traced searches are instantiated in this kernel only.
 #pragma once
 
+struct SolOut { int8_t* moves; int32_t* length; int8_t* agent; int max_len; };
+
 // The traced agents of SearchGame<PROB> (search_game.h agent_fast / agent_generic): res[] as there; `node`: the returned node's index
-// in the pool and the trace words, `depth`: the number of moves that lead to it.
+// in the pool and the trace words, `depth`: the number of moves that lead to it.  walks_without_winner: whether the agent that ends a
+// game without winning has a node to walk back from (the BFS agent's best node) -- sokoban's searches return one only when they win.
 template <int PROB>
-struct PlayAgents;
+struct TracedAgents;
 
 template <>
-struct PlayAgents<PCGRL_PROB_MDUNGEON> {
+struct TracedAgents<PCGRL_PROB_SOKOBAN> {
+    typedef SearchGame<PCGRL_PROB_SOKOBAN> G;
+    static constexpr bool walks_without_winner = false;
+    // (the trace is in the nodes: `trace` is not used.  The compact search has no `duo` parameter: a traced search is the
+    //  one-wavefront loop.)
+    static __device__ __forceinline__ bool fast(G::Shared& S, int a, void* pool, uint32_t*, uint32_t* lds, int toff, int tsize, int power, int lane, int* res,
+                                                int& it, bool& exhausted, int& node, int& depth) {
+        const SokKidsLanes kids = {lane, sokf_dir(lane & 3, S.L.w)};
+        uint64_t* tab = reinterpret_cast<uint64_t*>(lds + toff);
+        SokFastNode* fp = reinterpret_cast<SokFastNode*>(pool);
+        const SokTrace tr = {&node};
+        int hh = 0, dd = 0;
+        bool w;
+        if (S.L.cells <= 64) w = sok_search_fast_traced<1>(S.L, fp, lds, tab, tsize - 1, S.cache, S.root, G::ks(a), power, hh, dd, it, exhausted, SokNoHook(), kids, tr);
+        else w = sok_search_fast_traced<4>(S.L, fp, lds, tab, tsize - 1, S.cache, S.root, G::ks(a), power, hh, dd, it, exhausted, SokNoHook(), kids, tr);
+        res[0] = w ? 0 : hh; res[1] = w ? dd : 0;
+        depth = res[1];
+        return w;
+    }
+    template <class HP, class TP>
+    static __device__ __forceinline__ bool generic(G::Shared& S, int a, void* pool, uint32_t*, HP heap, TP table, int tsize, int power, int* res, int& it,
+                                                   bool& exhausted, int& node, int& depth) {
+        const SokTrace tr = {&node};
+        int hh = 0, dd = 0;
+        const bool w = sok_search(S.L, reinterpret_cast<SokNode*>(pool), heap, table, tsize - 1, S.work, S.root, G::ks(a), power, hh, dd, it, exhausted, SokNoHook(), tr);
+        res[0] = w ? 0 : hh; res[1] = w ? dd : 0;
+        depth = res[1];
+        return w;
+    }
+    static __device__ __forceinline__ void walk(int fast, const void* pool, const uint32_t*, int, int node, int depth, int8_t* row, int max_len) {
+        if (fast) sokf_walk_back(reinterpret_cast<const SokFastNode*>(pool), node, depth, row, max_len);
+        else sok_walk_back(reinterpret_cast<const SokNode*>(pool), node, depth, row, max_len);
+    }
+};
+
+template <>
+struct TracedAgents<PCGRL_PROB_MDUNGEON> {
     typedef SearchGame<PCGRL_PROB_MDUNGEON> G;
+    static constexpr bool walks_without_winner = true;
     static __device__ __forceinline__ bool fast(G::Shared& S, int a, void* pool, uint32_t* trace, uint32_t* lds, int toff, int tsize, int power, int lane,
                                                 int* res, int& it, bool& exhausted, int& node, int& depth) {
         const MdKidsLanes kids = {lane};
@@ -55,8 +101,9 @@ struct PlayAgents<PCGRL_PROB_MDUNGEON> {
 };
 
 template <>
-struct PlayAgents<PCGRL_PROB_DDAVE> {
+struct TracedAgents<PCGRL_PROB_DDAVE> {
     typedef SearchGame<PCGRL_PROB_DDAVE> G;
+    static constexpr bool walks_without_winner = true;
     static __device__ __forceinline__ bool fast(G::Shared& S, int a, void* pool, uint32_t* trace, uint32_t* lds, int toff, int tsize, int power, int lane,
                                                 int* res, int& it, bool& exhausted, int& node, int& depth) {
         const DdKidsLanes kids = {lane};
@@ -84,14 +131,14 @@ struct PlayAgents<PCGRL_PROB_DDAVE> {
 };
 
 // search_game_run (search_game.h) with traced agents.  res[] as there; `winner` (lane 0): the agent that won, -1 = none; `length`
-// (lane 0): the depth of the node the game's result comes from.  Its moves are in the level's row of `out` when this returns "final".
-// `trace`: `trace_cap` words beside `pool`.
+// (lane 0): the depth of the node whose moves were written, 0 when none were.  The moves are in the level's row of `out` when this
+// returns "final".  `trace`: `trace_cap` words beside `pool`.
 template <int PROB>
-__device__ __forceinline__ bool playthrough_game_run(const PcgrlParams& P, const DevBufs& B, typename SearchGame<PROB>::Shared& S, uint32_t* heap, int table_off,
-                                                     int tsize, int power, void* pool, uint32_t* trace, int trace_cap, int lane, int* res, int& winner,
-                                                     int& length, const SolOut& out, int m) {
+__device__ __forceinline__ bool moves_game_run(const PcgrlParams& P, const DevBufs& B, typename SearchGame<PROB>::Shared& S, uint32_t* heap, int table_off,
+                                               int tsize, int power, void* pool, uint32_t* trace, int trace_cap, int lane, int* res, int& winner, int& length,
+                                               const SolOut& out, int m) {
     typedef SearchGame<PROB> G;
-    typedef PlayAgents<PROB> A;
+    typedef TracedAgents<PROB> A;
     G::build(P, B, B.map, S, lane);
     __threadfence_block();
     const int fast = S.fast;
@@ -110,10 +157,10 @@ __device__ __forceinline__ bool playthrough_game_run(const PcgrlParams& P, const
             if (!w && !exhausted && power < P.solver_power) { final = 0; next = 4; }        // stopped by the reduced limit
             else {
                 next = G::next(a, w, exhausted);
-                if (next == 4) {
-                    // this agent ends the game: a winner, or the BFS agent after nobody won -- res[] is its node's.  (The compact
-                    // search's lanes 0..3 all stored every trace word: what lane 0 reads it wrote itself; the fence orders the
-                    // stores in front of the walk's loads all the same.)
+                if (next == 4 && (w || A::walks_without_winner)) {
+                    // this agent ends the game with a node to walk back from: a winner, or (mdungeon, ddave) the BFS agent after
+                    // nobody won -- res[] is its node's.  (The compact search's lanes 0..3 all stored every node and trace word:
+                    // what lane 0 reads it wrote itself; the fence orders the stores in front of the walk's loads all the same.)
                     __threadfence();
                     if (lane == 0) {
                         winner = w ? a : -1;
@@ -131,17 +178,18 @@ __device__ __forceinline__ bool playthrough_game_run(const PcgrlParams& P, const
 
 // what a finished game leaves: the planner's columns of the statistics row (as k_get_stats_search), the length, the winner
 template <int PROB>
-__device__ __forceinline__ void playthrough_finish(int32_t* rows_out, const SolOut& out, int m, const int* res, int winner, int length) {
+__device__ __forceinline__ void moves_finish(int32_t* rows_out, const SolOut& out, int m, const int* res, int winner, int length) {
     SearchGame<PROB>::pack(rows_out + (size_t)m * 8, res);
     out.length[m] = length;
     if (out.agent) out.agent[m] = (int8_t)winner;
 }
 
-// `traces`: per block `trace_stride` words, indexed like the block's pool (a small try's words start at wv * SS_SMALL_NODES)
+// `traces`: per block `trace_stride` words, indexed like the block's pool (a small try's words start at wv * SS_SMALL_NODES);
+// sokoban: NULL and 0
 template <int PROB>
-__global__ __launch_bounds__(SS_THREADS) void k_get_playthrough(PcgrlParams P, DevBufs Bs, const uint8_t* __restrict__ maps, int32_t* __restrict__ rows_out,
-                                                                 SolOut out, int32_t* head, const int32_t* __restrict__ jobs, SokNode* pools, int pool_stride,
-                                                                 uint32_t* traces, int trace_stride) {
+__global__ __launch_bounds__(SS_THREADS) void k_get_moves(PcgrlParams P, DevBufs Bs, const uint8_t* __restrict__ maps, int32_t* __restrict__ rows_out,
+                                                           SolOut out, int32_t* head, const int32_t* __restrict__ jobs, SokNode* pools, int pool_stride,
+                                                           uint32_t* traces, int trace_stride) {
     extern __shared__ __attribute__((aligned(16))) uint32_t ss_lds[];     // the full search region; the small ones are carved out of it
     typedef SearchGame<PROB> Game;
     typedef typename Game::Shared GameShared;
@@ -172,11 +220,11 @@ __global__ __launch_bounds__(SS_THREADS) void k_get_playthrough(PcgrlParams P, D
                 __threadfence_block();
                 int res[Game::NRES] = {};
                 int winner = -1, length = 0;
-                const bool final = playthrough_game_run<PROB>(P, B, small_games[wv], ss_lds + wv * SS_SMALL_WORDS, SS_SMALL_HEAP, SS_SMALL_TABLE, small_power,
-                                                              pool + (size_t)wv * SS_SMALL_NODES, trace + (size_t)wv * SS_SMALL_NODES, SS_SMALL_NODES, lane64,
-                                                              res, winner, length, out, m);
+                const bool final = moves_game_run<PROB>(P, B, small_games[wv], ss_lds + wv * SS_SMALL_WORDS, SS_SMALL_HEAP, SS_SMALL_TABLE, small_power,
+                                                        pool + (size_t)wv * SS_SMALL_NODES, trace + (size_t)wv * SS_SMALL_NODES, SS_SMALL_NODES, lane64, res,
+                                                        winner, length, out, m);
                 if (lane64 == 0) {
-                    if (final) playthrough_finish<PROB>(rows_out, out, m, res, winner, length);
+                    if (final) moves_finish<PROB>(rows_out, out, m, res, winner, length);
                     else s_big[atomicAdd(&s_nbig, 1)] = m;
                 }
                 __builtin_amdgcn_wave_barrier();
@@ -192,9 +240,9 @@ __global__ __launch_bounds__(SS_THREADS) void k_get_playthrough(PcgrlParams P, D
                 __threadfence_block();
                 int res[Game::NRES] = {};
                 int winner = -1, length = 0;
-                playthrough_game_run<PROB>(P, B, s_game0, ss_lds, SOK_LDS_HEAP, SOK_LDS_TABLE, P.solver_power, pool, trace, trace_stride, lane64, res, winner,
-                                           length, out, m);
-                if (lane64 == 0) playthrough_finish<PROB>(rows_out, out, m, res, winner, length);
+                moves_game_run<PROB>(P, B, s_game0, ss_lds, SOK_LDS_HEAP, SOK_LDS_TABLE, P.solver_power, pool, trace, trace_stride, lane64, res, winner, length,
+                                     out, m);
+                if (lane64 == 0) moves_finish<PROB>(rows_out, out, m, res, winner, length);
                 __builtin_amdgcn_wave_barrier();
             }
         }

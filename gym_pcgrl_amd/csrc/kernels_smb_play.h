@@ -15,7 +15,7 @@
 //  * smb_search: the children of expansion k are pool nodes 1 + 4k .. 4 + 4k, so node i was made by move (i - 1) & 3 of expansion
 //    (i - 1) >> 2; what is missing is that expansion's own node: a log of 16-bit pool indices (a heap word holds no more) beside
 //    the arena, and the pool index of the best node.
-// The two search bodies repeat smb_search_two_label and smb_search on purpose, for the reason kernels_playthrough.h gives: k_smb sits
+// The two search bodies repeat smb_search_two_label and smb_search on purpose, for the reason kernels_moves.h gives: k_smb sits
 // at its register limit, and one body with a trace policy does not leave its machine code alone.  A change to the searches there has
 // to be made here as well.  The traced searches are instantiated in this kernel only.
 #pragma once

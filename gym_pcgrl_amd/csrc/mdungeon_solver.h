@@ -105,7 +105,7 @@ PCGRL_D void md_store(MdNode* p, const MdRaw& r) {
     d[0] = r.q[0]; d[1] = r.q[1]; d[2] = r.q[2]; d[3] = r.q[3]; d[4] = r.q[4];
 }
 
-// The play behind the statistics (pcgrl_get_playthrough, kernels_playthrough.h).  The reference's Node keeps its parent and the
+// The play behind the statistics (pcgrl_get_playthrough, kernels_moves.h).  The reference's Node keeps its parent and the
 // action that made it (engine.py:22-49) and getSolution returns node.getActions(); _run_game keeps only len(sol).  A search handed
 // `PlayTrace{trace, &node}` records for every child it files into the pool one word in the array beside the pool: trace[child] =
 // parent's pool index | child number << 30 -- the child number is the move, the children are made in the order of the engine's

@@ -84,9 +84,8 @@
 #include "kernels_step_solver.h"
 #include "kernels_search_async.h"
 #include "kernels_evaluate.h"
-#include "kernels_solution.h"
-#include "kernels_playthrough.h"
-#include "kernels_smb_play.h"     // (after kernels_solution.h: SolOut)
+#include "kernels_moves.h"
+#include "kernels_smb_play.h"     // (after kernels_moves.h: SolOut)
 #include "search_big.h"
 #include "kernels_search_big.h"
 #if PCGRL_IN_PART(PART_CORE)
@@ -631,8 +630,7 @@ PCGRL_LOCAL int launch_smb(pcgrl_env* h, int32_t* sync, int list_a, int mode_a, 
 PCGRL_LOCAL int launch_step_solver(pcgrl_env* h, const int32_t* actions, hipStream_t st, const RolloutArgs& R, int epb);
 PCGRL_LOCAL int launch_get_stats(pcgrl_env* h, const uint8_t* maps, int count, int32_t* rows_out, int32_t* head, int32_t* jobs, hipStream_t st);
 PCGRL_LOCAL int launch_get_stats_search(pcgrl_env* h, const uint8_t* maps, int32_t* rows_out, int32_t* head, const int32_t* jobs, SokNode* pools, int blocks, hipStream_t st);
-PCGRL_LOCAL int launch_get_solution(pcgrl_env* h, const uint8_t* maps, int32_t* rows_out, const SolOut& out, int32_t* head, const int32_t* jobs, SokNode* pools, int blocks, hipStream_t st);
-PCGRL_LOCAL int launch_get_playthrough(pcgrl_env* h, const uint8_t* maps, int32_t* rows_out, const SolOut& out, int32_t* head, const int32_t* jobs, SokNode* pools, uint32_t* traces, int blocks, hipStream_t st);
+PCGRL_LOCAL int launch_get_moves(pcgrl_env* h, const uint8_t* maps, int32_t* rows_out, const SolOut& out, int32_t* head, const int32_t* jobs, SokNode* pools, uint32_t* traces, int blocks, hipStream_t st);
 PCGRL_LOCAL int launch_smb_play(pcgrl_env* h, const uint8_t* maps, int count, int32_t* rows_out, const SolOut& out, int32_t* ticket, uint8_t* arenas, int slots, hipStream_t st);
 PCGRL_LOCAL int launch_search_async(pcgrl_env* h, int32_t* tickets, int list_a, int mode_a, int list_b, int mode_b, int parity, int rst_list, int clr, int budget, int resume, int small, hipStream_t st);
 // A launch with more than 64 KB of dynamic LDS needs the kernel's cap raised first.  That is a driver call (about a microsecond of
@@ -1016,7 +1014,7 @@ PCGRL_LOCAL int launch_step_solver(pcgrl_env* h, const int32_t* actions, hipStre
     });
 }
 
-// The second launches of pcgrl_get_stats and pcgrl_get_solution: the parked maps' searches on `blocks` persistent blocks, each with a
+// The second launches of pcgrl_get_stats, pcgrl_get_solution and pcgrl_get_playthrough: the parked maps' searches on `blocks` persistent blocks, each with a
 // node pool of its own in the caller's workspace.  Of DevBufs these kernels read the three fields SearchGame<PROB>::build looks at.
 static DevBufs search_devbufs(const pcgrl_env* h) {
     DevBufs Bs;
@@ -1031,15 +1029,12 @@ PCGRL_LOCAL int launch_get_stats_search(pcgrl_env* h, const uint8_t* maps, int32
         return launch<k_get_stats_search<prob()>>(h, blocks, SS_THREADS, sok_lds_bytes(), st, h->P, search_devbufs(h), maps, rows_out, head, jobs, pools, search_pool_stride(h));
     });
 }
-// (kernels_solution.h: k_get_stats_search's shape with the traced sokoban searches)
-PCGRL_LOCAL int launch_get_solution(pcgrl_env* h, const uint8_t* maps, int32_t* rows_out, const SolOut& out, int32_t* head, const int32_t* jobs, SokNode* pools, int blocks, hipStream_t st) {
-    return launch<k_get_solution<0>>(h, blocks, SS_THREADS, sok_lds_bytes(), st, h->P, search_devbufs(h), maps, rows_out, out, head, jobs, pools, search_pool_stride(h));
-}
-// (kernels_playthrough.h: the same shape with the traced mdungeon / ddave searches; a block's trace words are as many as its pool's nodes)
-PCGRL_LOCAL int launch_get_playthrough(pcgrl_env* h, const uint8_t* maps, int32_t* rows_out, const SolOut& out, int32_t* head, const int32_t* jobs, SokNode* pools, uint32_t* traces, int blocks, hipStream_t st) {
-    return with_prob<PCGRL_PROB_MDUNGEON, PCGRL_PROB_DDAVE>(h->P.prob, [&](auto prob) {
-        return launch<k_get_playthrough<prob()>>(h, blocks, SS_THREADS, sok_lds_bytes(), st, h->P, search_devbufs(h), maps, rows_out, out, head, jobs, pools,
-                                                 search_pool_stride(h), traces, play_trace_words(&h->cfg));
+// (kernels_moves.h: k_get_stats_search's shape with the traced searches; `traces`: as many words per block as its pool has nodes --
+//  mdungeon, ddave --, or NULL -- sokoban, whose trace is in the nodes)
+PCGRL_LOCAL int launch_get_moves(pcgrl_env* h, const uint8_t* maps, int32_t* rows_out, const SolOut& out, int32_t* head, const int32_t* jobs, SokNode* pools, uint32_t* traces, int blocks, hipStream_t st) {
+    return with_prob<PCGRL_PROB_SOKOBAN, PCGRL_PROB_MDUNGEON, PCGRL_PROB_DDAVE>(h->P.prob, [&](auto prob) {
+        return launch<k_get_moves<prob()>>(h, blocks, SS_THREADS, sok_lds_bytes(), st, h->P, search_devbufs(h), maps, rows_out, out, head, jobs, pools,
+                                           search_pool_stride(h), traces, traces ? play_trace_words(&h->cfg) : 0);
     });
 }
 
@@ -1719,91 +1714,22 @@ int pcgrl_get_reward(pcgrl_env* h, const int32_t* rows, const int32_t* ref_rows,
     return PCGRL_OK;
 }
 
-// ---- pcgrl_get_solution (kernels_solution.h): the moves behind sokoban's sol-length -----------------------------------------------
-// The workspace, cut from one plan like pcgrl_get_stats': its three regions, and rows for a caller that wants none.
-struct SolPlan { EvalPlan E; Region rows; size_t total; };
-static SolPlan sol_plan(const pcgrl_config* c, int count) {
-    SolPlan S = {};
+// ---- pcgrl_get_solution / pcgrl_get_playthrough (kernels_moves.h), pcgrl_get_smb_play (kernels_smb_play.h): the planner's moves -----
+// The workspace of the first two, cut from one plan like pcgrl_get_stats': its three regions, rows for a caller that wants none, and
+// -- mdungeon, ddave -- per persistent block the trace words beside its node pool (sokoban's trace is in the nodes: no region).
+struct MovesPlan { EvalPlan E; Region rows, traces; size_t total; };
+static MovesPlan moves_plan(const pcgrl_config* c, int count) {
+    MovesPlan S = {};
     S.E = eval_plan(c, count);
     Bump b = {S.E.total};
     S.rows = b.take(align_up((size_t)count * 8 * 4, 256));
+    if (c->prob != PCGRL_SOKOBAN) S.traces = b.take((size_t)S.E.blocks * play_trace_words(c) * 4);
     S.total = b.off;
     return S;
 }
-size_t pcgrl_get_solution_bytes(const pcgrl_config* c, int32_t count, int32_t max_len) {
-    if (!c || c->prob != PCGRL_SOKOBAN || max_len < 1 || pcgrl_get_stats_bytes(c, count) == 0) return 0;
-    pcgrl_config one = *c;
-    one.num_envs = 1;
-    return sol_plan(&one, count).total;
-}
-int pcgrl_get_solution(pcgrl_env* h, const uint8_t* maps, int32_t count, int32_t max_len, int8_t* moves_out, int32_t* length_out, int8_t* agent_out,
-                       int32_t* rows_out, void* work, size_t work_bytes, void* stream) {
-    if (!h || !h->bound) return PCGRL_ESTATE;
-    if (!maps || !moves_out || !length_out || !work || count < 1 || max_len < 1 || ((uintptr_t)work & 255) != 0) return PCGRL_EINVAL;
-    const size_t need = pcgrl_get_solution_bytes(&h->cfg, count, max_len);
-    if (need == 0 || work_bytes < need) return PCGRL_EINVAL;
-    DeviceGuard guard(h->device);
-    hipStream_t st = (hipStream_t)stream;
-    const SolPlan S = sol_plan(&h->cfg, count);
-    uint8_t* w = (uint8_t*)work;
-    int32_t* head = at<int32_t>(w, S.E.head);
-    int32_t* rows = rows_out ? rows_out : at<int32_t>(w, S.rows);
-    HIPCHK(hipMemsetAsync(head, 0, S.E.head.bytes, st));
-    // what a level keeps when its planner does not run or nobody wins: an all -1 row, length 0, agent -2 (k_get_solution: -1)
-    HIPCHK(hipMemsetAsync(moves_out, 0xFF, (size_t)count * (size_t)max_len, st));
-    HIPCHK(hipMemsetAsync(length_out, 0, (size_t)count * 4, st));
-    if (agent_out) { HIPCHK(hipMemsetAsync(agent_out, 0xFE, (size_t)count, st)); }
-    int rc = launch_get_stats(h, maps, count, rows, head, at<int32_t>(w, S.E.jobs), st);
-    if (rc) return rc;
-    const SolOut out = {moves_out, length_out, agent_out, max_len};
-    return launch_get_solution(h, maps, rows, out, head, at<int32_t>(w, S.E.jobs), at<SokNode>(w, S.E.pools), S.E.blocks, st);
-}
-
-// ---- pcgrl_get_playthrough (kernels_playthrough.h): the play behind the mdungeon / ddave statistics ---------------------------------
-// The workspace, cut from one plan like pcgrl_get_solution's: pcgrl_get_stats' three regions, rows for a caller that wants none, and
-// per persistent block the trace words beside its node pool.
-struct PlayPlan { EvalPlan E; Region rows, traces; size_t total; };
-static PlayPlan play_plan(const pcgrl_config* c, int count) {
-    PlayPlan S = {};
-    S.E = eval_plan(c, count);
-    Bump b = {S.E.total};
-    S.rows = b.take(align_up((size_t)count * 8 * 4, 256));
-    S.traces = b.take((size_t)S.E.blocks * play_trace_words(c) * 4);
-    S.total = b.off;
-    return S;
-}
-size_t pcgrl_get_playthrough_bytes(const pcgrl_config* c, int32_t count, int32_t max_len) {
-    if (!c || (c->prob != PCGRL_MDUNGEON && c->prob != PCGRL_DDAVE) || max_len < 1 || pcgrl_get_stats_bytes(c, count) == 0) return 0;
-    pcgrl_config one = *c;
-    one.num_envs = 1;
-    return play_plan(&one, count).total;
-}
-int pcgrl_get_playthrough(pcgrl_env* h, const uint8_t* maps, int32_t count, int32_t max_len, int8_t* moves_out, int32_t* length_out, int8_t* agent_out,
-                          int32_t* rows_out, void* work, size_t work_bytes, void* stream) {
-    if (!h || !h->bound) return PCGRL_ESTATE;
-    if (!maps || !moves_out || !length_out || !work || count < 1 || max_len < 1 || ((uintptr_t)work & 255) != 0) return PCGRL_EINVAL;
-    const size_t need = pcgrl_get_playthrough_bytes(&h->cfg, count, max_len);
-    if (need == 0 || work_bytes < need) return PCGRL_EINVAL;
-    DeviceGuard guard(h->device);
-    hipStream_t st = (hipStream_t)stream;
-    const PlayPlan S = play_plan(&h->cfg, count);
-    uint8_t* w = (uint8_t*)work;
-    int32_t* head = at<int32_t>(w, S.E.head);
-    int32_t* rows = rows_out ? rows_out : at<int32_t>(w, S.rows);
-    HIPCHK(hipMemsetAsync(head, 0, S.E.head.bytes, st));
-    // what a level keeps when its planner does not run: an all -1 row, length 0, agent -2 (k_get_playthrough: -1 when nobody won)
-    HIPCHK(hipMemsetAsync(moves_out, 0xFF, (size_t)count * (size_t)max_len, st));
-    HIPCHK(hipMemsetAsync(length_out, 0, (size_t)count * 4, st));
-    if (agent_out) { HIPCHK(hipMemsetAsync(agent_out, 0xFE, (size_t)count, st)); }
-    int rc = launch_get_stats(h, maps, count, rows, head, at<int32_t>(w, S.E.jobs), st);
-    if (rc) return rc;
-    const SolOut out = {moves_out, length_out, agent_out, max_len};
-    return launch_get_playthrough(h, maps, rows, out, head, at<int32_t>(w, S.E.jobs), at<SokNode>(w, S.E.pools), at<uint32_t>(w, S.traces), S.E.blocks, st);
-}
-
-// ---- pcgrl_get_smb_play (kernels_smb_play.h): the play behind smb's jumps / jumps-dist / dist-win ---------------------------------
-// The workspace, cut from one plan: the ticket, rows for a caller that wants none, and one arena + expansion log per wavefront that
-// can run -- the launch takes blocks of at most SMB_MAX_WAVES wavefronts, never more wavefronts than count + SMB_MAX_WAVES - 1.
+static Region plan_head(const MovesPlan& S) { return S.E.head; }
+// smb's, cut from one plan: the ticket, rows for a caller that wants none, and one arena + expansion log per wavefront that can run --
+// the launch takes blocks of at most SMB_MAX_WAVES wavefronts, never more wavefronts than count + SMB_MAX_WAVES - 1.
 struct SmbPlayPlan { Region head, rows, arenas; int slots; size_t total; };
 static SmbPlayPlan smb_play_plan(const pcgrl_config* c, int count) {
     SmbPlayPlan S = {};
@@ -1816,6 +1742,19 @@ static SmbPlayPlan smb_play_plan(const pcgrl_config* c, int count) {
     S.total = b.off;
     return S;
 }
+static Region plan_head(const SmbPlayPlan& S) { return S.head; }
+static size_t moves_bytes(const pcgrl_config* c, int32_t count, int32_t max_len, bool right_problem) {
+    if (!c || !right_problem || max_len < 1 || pcgrl_get_stats_bytes(c, count) == 0) return 0;
+    pcgrl_config one = *c;
+    one.num_envs = 1;
+    return moves_plan(&one, count).total;
+}
+size_t pcgrl_get_solution_bytes(const pcgrl_config* c, int32_t count, int32_t max_len) {
+    return moves_bytes(c, count, max_len, c && c->prob == PCGRL_SOKOBAN);
+}
+size_t pcgrl_get_playthrough_bytes(const pcgrl_config* c, int32_t count, int32_t max_len) {
+    return moves_bytes(c, count, max_len, c && (c->prob == PCGRL_MDUNGEON || c->prob == PCGRL_DDAVE));
+}
 size_t pcgrl_get_smb_play_bytes(const pcgrl_config* c, int32_t count, int32_t max_len) {
     if (!c || c->prob != PCGRL_SMB || count < 1 || max_len < 1) return 0;
     pcgrl_config one = *c;
@@ -1823,22 +1762,56 @@ size_t pcgrl_get_smb_play_bytes(const pcgrl_config* c, int32_t count, int32_t ma
     if (validate_config(&one) != PCGRL_OK) return 0;
     return smb_play_plan(&one, count).total;
 }
-int pcgrl_get_smb_play(pcgrl_env* h, const uint8_t* maps, int32_t count, int32_t max_len, int8_t* moves_out, int32_t* length_out, int8_t* agent_out,
-                       int32_t* rows_out, void* work, size_t work_bytes, void* stream) {
+// What the three calls do before their launches: the checks (`bytes`: the call's own *_bytes, 0 for another problem), the workspace
+// cut by `plan`, its head cleared, the move rows filled with -1 -- the kernels store the moves only.  `launch` issues the rest.
+extern "C++" {
+template <class Plan, class Launch>
+static int moves_call(pcgrl_env* h, const uint8_t* maps, int32_t count, int32_t max_len, int8_t* moves_out, int32_t* length_out, int8_t* agent_out,
+                      int32_t* rows_out, void* work, size_t work_bytes, void* stream, size_t (*bytes)(const pcgrl_config*, int32_t, int32_t),
+                      Plan (*plan)(const pcgrl_config*, int), Launch launch) {
     if (!h || !h->bound) return PCGRL_ESTATE;
     if (!maps || !moves_out || !length_out || !work || count < 1 || max_len < 1 || ((uintptr_t)work & 255) != 0) return PCGRL_EINVAL;
-    const size_t need = pcgrl_get_smb_play_bytes(&h->cfg, count, max_len);
+    const size_t need = bytes(&h->cfg, count, max_len);
     if (need == 0 || work_bytes < need) return PCGRL_EINVAL;
     DeviceGuard guard(h->device);
     hipStream_t st = (hipStream_t)stream;
-    const SmbPlayPlan S = smb_play_plan(&h->cfg, count);
+    const Plan S = plan(&h->cfg, count);
     uint8_t* w = (uint8_t*)work;
-    int32_t* head = at<int32_t>(w, S.head);
-    int32_t* rows = rows_out ? rows_out : at<int32_t>(w, S.rows);
-    HIPCHK(hipMemsetAsync(head, 0, S.head.bytes, st));
-    HIPCHK(hipMemsetAsync(moves_out, 0xFF, (size_t)count * (size_t)max_len, st));      // -1 beyond the play: the kernel stores the moves only
+    int32_t* head = at<int32_t>(w, plan_head(S));
+    HIPCHK(hipMemsetAsync(head, 0, plan_head(S).bytes, st));
+    HIPCHK(hipMemsetAsync(moves_out, 0xFF, (size_t)count * (size_t)max_len, st));
     const SolOut out = {moves_out, length_out, agent_out, max_len};
-    return launch_smb_play(h, maps, count, rows, out, head, at<uint8_t>(w, S.arenas), S.slots, st);
+    return launch(S, w, head, rows_out ? rows_out : at<int32_t>(w, S.rows), out, st);
+}
+}
+// pcgrl_get_solution and pcgrl_get_playthrough: pcgrl_get_stats' two launches, the second one with the traced searches
+static int get_moves(pcgrl_env* h, const uint8_t* maps, int32_t count, int32_t max_len, int8_t* moves_out, int32_t* length_out, int8_t* agent_out,
+                     int32_t* rows_out, void* work, size_t work_bytes, void* stream, size_t (*bytes)(const pcgrl_config*, int32_t, int32_t)) {
+    return moves_call(h, maps, count, max_len, moves_out, length_out, agent_out, rows_out, work, work_bytes, stream, bytes, moves_plan,
+                      [&](const MovesPlan& S, uint8_t* w, int32_t* head, int32_t* rows, const SolOut& out, hipStream_t st) -> int {
+        // what a level keeps when its planner does not run: (an all -1 row,) length 0, agent -2 (k_get_moves: -1 when nobody won)
+        HIPCHK(hipMemsetAsync(length_out, 0, (size_t)count * 4, st));
+        if (agent_out) { HIPCHK(hipMemsetAsync(agent_out, 0xFE, (size_t)count, st)); }
+        int rc = launch_get_stats(h, maps, count, rows, head, at<int32_t>(w, S.E.jobs), st);
+        if (rc) return rc;
+        return launch_get_moves(h, maps, rows, out, head, at<int32_t>(w, S.E.jobs), at<SokNode>(w, S.E.pools), at<uint32_t>(w, S.traces), S.E.blocks, st);
+    });
+}
+int pcgrl_get_solution(pcgrl_env* h, const uint8_t* maps, int32_t count, int32_t max_len, int8_t* moves_out, int32_t* length_out, int8_t* agent_out,
+                       int32_t* rows_out, void* work, size_t work_bytes, void* stream) {
+    return get_moves(h, maps, count, max_len, moves_out, length_out, agent_out, rows_out, work, work_bytes, stream, pcgrl_get_solution_bytes);
+}
+int pcgrl_get_playthrough(pcgrl_env* h, const uint8_t* maps, int32_t count, int32_t max_len, int8_t* moves_out, int32_t* length_out, int8_t* agent_out,
+                          int32_t* rows_out, void* work, size_t work_bytes, void* stream) {
+    return get_moves(h, maps, count, max_len, moves_out, length_out, agent_out, rows_out, work, work_bytes, stream, pcgrl_get_playthrough_bytes);
+}
+// (length and agent are not pre-filled: k_smb_play writes every level's)
+int pcgrl_get_smb_play(pcgrl_env* h, const uint8_t* maps, int32_t count, int32_t max_len, int8_t* moves_out, int32_t* length_out, int8_t* agent_out,
+                       int32_t* rows_out, void* work, size_t work_bytes, void* stream) {
+    return moves_call(h, maps, count, max_len, moves_out, length_out, agent_out, rows_out, work, work_bytes, stream, pcgrl_get_smb_play_bytes, smb_play_plan,
+                      [&](const SmbPlayPlan& S, uint8_t* w, int32_t* head, int32_t* rows, const SolOut& out, hipStream_t st) -> int {
+        return launch_smb_play(h, maps, count, rows, out, head, at<uint8_t>(w, S.arenas), S.slots, st);
+    });
 }
 
 }  // extern "C"

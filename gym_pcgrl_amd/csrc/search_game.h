@@ -130,30 +130,7 @@ struct SearchGame<PCGRL_PROB_SOKOBAN> {
         res[0] = w ? 0 : hh; res[1] = w ? dd : 0;
         return w;
     }
-    // the same two agents traced (SokTrace, sokoban_solver.h; k_get_solution): `widx` gets the winning node's pool index.  The compact
-    // one has no `duo` parameter: a traced search is the one-wavefront loop.
-    static __device__ __forceinline__ bool agent_fast_traced(Shared& S, int a, void* pool, uint32_t* lds, int toff, int tsize, int power, int lane, int* res,
-                                                             int& it, bool& exhausted, int& widx) {
-        const SokKidsLanes kids = {lane, sokf_dir(lane & 3, S.L.w)};
-        uint64_t* tab = reinterpret_cast<uint64_t*>(lds + toff);
-        SokFastNode* fp = reinterpret_cast<SokFastNode*>(pool);
-        const SokTrace tr = {&widx};
-        int hh = 0, dd = 0;
-        bool w;
-        if (S.L.cells <= 64) w = sok_search_fast_traced<1>(S.L, fp, lds, tab, tsize - 1, S.cache, S.root, ks(a), power, hh, dd, it, exhausted, SokNoHook(), kids, tr);
-        else w = sok_search_fast_traced<4>(S.L, fp, lds, tab, tsize - 1, S.cache, S.root, ks(a), power, hh, dd, it, exhausted, SokNoHook(), kids, tr);
-        res[0] = w ? 0 : hh; res[1] = w ? dd : 0;
-        return w;
-    }
-    template <class HP, class TP>
-    static __device__ __forceinline__ bool agent_generic_traced(Shared& S, int a, void* pool, HP heap, TP table, int tsize, int power, int* res, int& it,
-                                                                bool& exhausted, int& widx) {
-        const SokTrace tr = {&widx};
-        int hh = 0, dd = 0;
-        const bool w = sok_search(S.L, reinterpret_cast<SokNode*>(pool), heap, table, tsize - 1, S.work, S.root, ks(a), power, hh, dd, it, exhausted, SokNoHook(), tr);
-        res[0] = w ? 0 : hh; res[1] = w ? dd : 0;
-        return w;
-    }
+    // (the same two agents traced: TracedAgents<PCGRL_PROB_SOKOBAN>, kernels_moves.h)
     // first winner, or the exact exhausted-BFS shortcut (sokoban_solver.h)
     static __device__ __forceinline__ int next(int a, bool win, bool exhausted) { return (win || (a == 0 && exhausted) || a == 3) ? 4 : a + 1; }
     static __device__ __forceinline__ void pack(int32_t* s, const int* res) { s[4] = res[0]; s[5] = res[1]; }

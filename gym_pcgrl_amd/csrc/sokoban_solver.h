@@ -222,7 +222,7 @@ PCGRL_D bool sok_same(const SokLevel& L, const SokNode& a, const SokNode& b) {
 // known (BFS: the next queue entry; A*: the heap top after the repair), which takes the global-memory
 // latency of the pop off the serial chain.
 struct SokNoHook { PCGRL_D bool operator()(int) const { return false; } };
-// ---- Traced searches (pcgrl_get_solution, kernels_solution.h): Node.getActions (engine.py:38-44) needs every node's parent and
+// ---- Traced searches (pcgrl_get_solution, kernels_moves.h): Node.getActions (engine.py:38-44) needs every node's parent and
 // action, which the reward path never looks at.  A search handed `SokTrace{&win}` records in every child it writes to the pool the
 // pool index of the node it was expanded from and the direction d = 0..3 (L, R, U, D: engine.py's `directions`) that made it -- in
 // bits that are free (SokNode: pad = move, pad2 = parent; SokFastNode: sokoban_fast.h) -- and, when it wins, stores the winning

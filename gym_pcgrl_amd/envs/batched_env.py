@@ -62,10 +62,8 @@ class Evaluation:
         self.rows, self.stats, self.reward, self.over = rows, stats, reward, over
 
 
-class Solutions:
-    """What BatchedPcgrlEnv.solve() returns: `moves` int8 [M, max_len] (0..3 = left, right, up, down; -1 beyond the solution),
-    `length` int32 [M] (the full len(solution), also beyond max_len), `agent` int8 [M] (-2 the planner did not run, -1 no agent won,
-    0..3 = BFS, A*(1), A*(0.5), A*(0)), `rows` / `stats` as in an Evaluation; `truncated` bool [M]: the row holds only a prefix."""
+class _PlannerMoves:
+    """What Solutions and Playthroughs share: a planner's move rows for a batch of levels."""
     __slots__ = ("moves", "length", "agent", "rows", "stats")
 
     def __init__(self, moves, length, agent, rows, stats):
@@ -76,20 +74,20 @@ class Solutions:
         return self.length > self.moves.shape[1]
 
 
-class Playthroughs:
+class Solutions(_PlannerMoves):
+    """What BatchedPcgrlEnv.solve() returns: `moves` int8 [M, max_len] (0..3 = left, right, up, down; -1 beyond the solution),
+    `length` int32 [M] (the full len(solution), also beyond max_len), `agent` int8 [M] (-2 the planner did not run, -1 no agent won,
+    0..3 = BFS, A*(1), A*(0.5), A*(0)), `rows` / `stats` as in an Evaluation; `truncated` bool [M]: the row holds only a prefix."""
+    __slots__ = ()
+
+
+class Playthroughs(_PlannerMoves):
     """What BatchedPcgrlEnv.playthrough() and playthrough_smb() return: `moves` int8 [M, max_len] (mdungeon 0..3 = left, right, up,
     down; ddave 0..3 = stay, left, right, jump; smb 0..3 = stay, right, jump, right + jump; -1 beyond the play), `length` int32 [M]
     (the depth of the node the statistics come from, also beyond max_len), `agent` int8 [M] (-2 the planner did not run, -1 no agent
     won, 0..3 = A*(1), A*(0.5), A*(0), BFS; smb: -1 nobody won, 0 = A*(1), 1 = A*(0), never -2), `rows` / `stats` as in an
     Evaluation; `truncated` bool [M]: the row holds only a prefix; `won` bool [M]: an agent won."""
-    __slots__ = ("moves", "length", "agent", "rows", "stats")
-
-    def __init__(self, moves, length, agent, rows, stats):
-        self.moves, self.length, self.agent, self.rows, self.stats = moves, length, agent, rows, stats
-
-    @property
-    def truncated(self):
-        return self.length > self.moves.shape[1]
+    __slots__ = ()
 
     @property
     def won(self):
@@ -707,20 +705,9 @@ class BatchedPcgrlEnv:
         The calls on one environment share a cached workspace: issue them on one stream (the current stream of the first call),
         or synchronise between calls made on different streams."""
         torch = self._torch
-        dims = (self._prob._width, self._prob._height)
-        if self._handle is None or (not self._was_reset and (self._realloc or dims != self._alloc_dims)):
-            # no handle yet, or one that was only ever bound for scoring and cannot take the parameters in force: a new one
-            # (bound, not reset: step() and set_maps() still ask for reset())
-            self._allocate()
-            self._realloc = False
+        self._scoring_handle()
         stale = self._realloc              # the handle keeps its episodes and, until the next reset(), the parameters before the refused change
-        m = maps if torch.is_tensor(maps) else torch.as_tensor(np.asarray(maps))
-        if m.dim() != 3:
-            raise ValueError("evaluate(): maps must be [M, H, W], got shape %s" % (tuple(m.shape),))
-        w, h = self._alloc_dims
-        if tuple(m.shape[1:]) != (h, w) or m.shape[0] < 1:
-            raise ValueError("evaluate(): maps of shape %s for an environment of %d rows x %d columns (at least one map)" % (tuple(m.shape), h, w))
-        m = m.to(device=self.device, dtype=torch.uint8).contiguous()
+        m = self._as_maps("evaluate", maps)
         M = int(m.shape[0])
         rows = torch.empty((M, 8), dtype=torch.int32, device=self.device)
         cfg = self._config(self._alloc_dims)
@@ -747,6 +734,59 @@ class BatchedPcgrlEnv:
             over = over.view(torch.bool)
         return Evaluation(rows, self._prob.decode_rows(rows), reward, over)
 
+    # ---- what evaluate(), solve(), playthrough() and playthrough_smb() share
+    def _scoring_handle(self):
+        """A handle that can take the parameters in force: a new one where there is none yet, or one that was only ever bound for
+        scoring and cannot take them (bound, not reset: step() and set_maps() still ask for reset())."""
+        dims = (self._prob._width, self._prob._height)
+        if self._handle is None or (not self._was_reset and (self._realloc or dims != self._alloc_dims)):
+            self._allocate()
+            self._realloc = False
+
+    def _as_maps(self, who, maps):
+        """`maps` (array-like [M, H, W] on any device) as a contiguous uint8 tensor on this environment's device."""
+        torch = self._torch
+        m = maps if torch.is_tensor(maps) else torch.as_tensor(np.asarray(maps))
+        if m.dim() != 3:
+            raise ValueError("%s(): maps must be [M, H, W], got shape %s" % (who, tuple(m.shape)))
+        w, h = self._alloc_dims
+        if tuple(m.shape[1:]) != (h, w) or m.shape[0] < 1:
+            raise ValueError("%s(): maps of shape %s for an environment of %d rows x %d columns (at least one map)" % (who, tuple(m.shape), h, w))
+        return m.to(device=self.device, dtype=torch.uint8).contiguous()
+
+    def _planner_moves(self, who, fn, bytes_fn, result_cls, no_form_message, maps, max_len):
+        """solve(), playthrough() and playthrough_smb() behind their problem checks: library call `fn` with the workspace `bytes_fn`
+        asks for, on `maps` or (None) the handle's own map buffer.  `no_form_message(w, h, power)`: the text where `bytes_fn` gives 0."""
+        torch = self._torch
+        if maps is None:
+            if self._handle is None or not self._was_reset or self._needs_reset:
+                raise RuntimeError("%s() without maps reads the environment's current levels: call reset() first" % who)
+        self._scoring_handle()
+        if self._realloc:
+            raise NotImplementedError("%s(): an adjust_param() that this handle could not take in place waits for the next reset(); "
+                                      "the handle still plans with the old parameters" % who)
+        w, h = self._alloc_dims
+        m = self._bufs["map"] if maps is None else self._as_maps(who, maps)
+        M = int(m.shape[0])
+        power = int(self._prob._solver_power)
+        max_len = min(power, 255) if max_len is None else int(max_len)
+        if max_len < 1:
+            raise ValueError("%s(): max_len must be at least 1, got %d" % (who, max_len))
+        cfg = self._config(self._alloc_dims)
+        need = int(getattr(self._lib, bytes_fn)(C.byref(cfg), M, max_len))
+        if not need:
+            raise NotImplementedError(no_form_message(w, h, power))
+        moves = torch.empty((M, max_len), dtype=torch.int8, device=self.device)
+        length = torch.empty((M,), dtype=torch.int32, device=self.device)
+        agent = torch.empty((M,), dtype=torch.int8, device=self.device)
+        rows = torch.empty((M, 8), dtype=torch.int32, device=self.device)
+        if self._eval_work is None or self._eval_work.numel() < need:
+            self._eval_work = torch.empty((need,), dtype=torch.uint8, device=self.device)
+        _lib.check(getattr(self._lib, fn)(self._handle, C.c_void_p(m.data_ptr()), M, max_len, C.c_void_p(moves.data_ptr()),
+                                          C.c_void_p(length.data_ptr()), C.c_void_p(agent.data_ptr()), C.c_void_p(rows.data_ptr()),
+                                          C.c_void_p(self._eval_work.data_ptr()), self._eval_work.numel(), self._stream()), fn)
+        return result_cls(moves, length, agent, rows, self._prob.decode_rows(rows))
+
     # ---- SokobanProblem.get_stats(map)["solution"] on any level (pcgrl_get_solution)
     def solve(self, maps=None, max_len=None):
         """The planner's moves for `maps` -- array-like uint8 [M, H, W] as for evaluate(); None: this environment's current levels
@@ -756,51 +796,13 @@ class BatchedPcgrlEnv:
         pending asynchronous searches are not touched, a tile id >= get_num_tiles() is clamped on the way and reported by
         check_status(), nothing is waited for; the workspace is evaluate()'s (the same one-stream rule).  NotImplementedError where
         the library has no one-call form: there is no scratch-environment route for the moves."""
-        torch = self._torch
         if self._prob.name != "sokoban":
             raise NotImplementedError("solve(): only sokoban's get_stats returns its planner's moves (problem %r keeps at most their number%s)"
                                       % (self._prob.name, "; playthrough() returns the play behind its statistics" if self._prob.name in ("mdungeon", "ddave") else ""))
-        if maps is None:
-            if self._handle is None or not self._was_reset or self._needs_reset:
-                raise RuntimeError("solve() without maps reads the environment's current levels: call reset() first")
-        dims = (self._prob._width, self._prob._height)
-        if self._handle is None or (not self._was_reset and (self._realloc or dims != self._alloc_dims)):
-            self._allocate()               # (as in evaluate(): bound, not reset)
-            self._realloc = False
-        if self._realloc:
-            raise NotImplementedError("solve(): an adjust_param() that this handle could not take in place waits for the next reset(); "
-                                      "the handle still plans with the old parameters")
-        w, h = self._alloc_dims
-        if maps is None:
-            m = self._bufs["map"]
-        else:
-            m = maps if torch.is_tensor(maps) else torch.as_tensor(np.asarray(maps))
-            if m.dim() != 3:
-                raise ValueError("solve(): maps must be [M, H, W], got shape %s" % (tuple(m.shape),))
-            if tuple(m.shape[1:]) != (h, w) or m.shape[0] < 1:
-                raise ValueError("solve(): maps of shape %s for an environment of %d rows x %d columns (at least one map)" % (tuple(m.shape), h, w))
-            m = m.to(device=self.device, dtype=torch.uint8).contiguous()
-        M = int(m.shape[0])
-        power = int(self._prob._solver_power)
-        max_len = min(power, 255) if max_len is None else int(max_len)
-        if max_len < 1:
-            raise ValueError("solve(): max_len must be at least 1, got %d" % max_len)
-        cfg = self._config(self._alloc_dims)
-        need = int(self._lib.pcgrl_get_solution_bytes(C.byref(cfg), M, max_len))
-        if not need:
-            raise NotImplementedError("solve(): no one-call form for this configuration (levels of %d x %d = %d bordered cells, solver_power %d): "
-                                      "the traced searches are the ones that run in LDS -- at most 256 bordered cells and solver_power <= 5000"
-                                      % (h + 2, w + 2, (h + 2) * (w + 2), power))
-        moves = torch.empty((M, max_len), dtype=torch.int8, device=self.device)
-        length = torch.empty((M,), dtype=torch.int32, device=self.device)
-        agent = torch.empty((M,), dtype=torch.int8, device=self.device)
-        rows = torch.empty((M, 8), dtype=torch.int32, device=self.device)
-        if self._eval_work is None or self._eval_work.numel() < need:
-            self._eval_work = torch.empty((need,), dtype=torch.uint8, device=self.device)
-        _lib.check(self._lib.pcgrl_get_solution(self._handle, C.c_void_p(m.data_ptr()), M, max_len, C.c_void_p(moves.data_ptr()),
-                                                C.c_void_p(length.data_ptr()), C.c_void_p(agent.data_ptr()), C.c_void_p(rows.data_ptr()),
-                                                C.c_void_p(self._eval_work.data_ptr()), self._eval_work.numel(), self._stream()), "pcgrl_get_solution")
-        return Solutions(moves, length, agent, rows, self._prob.decode_rows(rows))
+        return self._planner_moves("solve", "pcgrl_get_solution", "pcgrl_get_solution_bytes", Solutions, lambda w, h, power: (
+            "solve(): no one-call form for this configuration (levels of %d x %d = %d bordered cells, solver_power %d): "
+            "the traced searches are the ones that run in LDS -- at most 256 bordered cells and solver_power <= 5000"
+            % (h + 2, w + 2, (h + 2) * (w + 2), power)), maps, max_len)
 
     # ---- the play that _run_game scores, mdungeon and ddave (pcgrl_get_playthrough)
     def playthrough(self, maps=None, max_len=None):
@@ -814,52 +816,14 @@ class BatchedPcgrlEnv:
         get_num_tiles() is clamped on the way and reported by check_status(), nothing is waited for; the workspace is evaluate()'s
         (the same one-stream rule).  NotImplementedError for the other problems (sokoban: solve()) and where the library has no
         one-call form: there is no scratch-environment route for the moves."""
-        torch = self._torch
         if self._prob.name not in ("mdungeon", "ddave"):
             raise NotImplementedError("playthrough(): the plays of mdungeon and ddave only, not problem %r%s"
                                       % (self._prob.name, " (solve() returns sokoban's solution)" if self._prob.name == "sokoban" else
                                          " (playthrough_smb() returns smb's play)" if self._prob.name == "smb" else ""))
-        if maps is None:
-            if self._handle is None or not self._was_reset or self._needs_reset:
-                raise RuntimeError("playthrough() without maps reads the environment's current levels: call reset() first")
-        dims = (self._prob._width, self._prob._height)
-        if self._handle is None or (not self._was_reset and (self._realloc or dims != self._alloc_dims)):
-            self._allocate()               # (as in evaluate(): bound, not reset)
-            self._realloc = False
-        if self._realloc:
-            raise NotImplementedError("playthrough(): an adjust_param() that this handle could not take in place waits for the next reset(); "
-                                      "the handle still plans with the old parameters")
-        w, h = self._alloc_dims
-        if maps is None:
-            m = self._bufs["map"]
-        else:
-            m = maps if torch.is_tensor(maps) else torch.as_tensor(np.asarray(maps))
-            if m.dim() != 3:
-                raise ValueError("playthrough(): maps must be [M, H, W], got shape %s" % (tuple(m.shape),))
-            if tuple(m.shape[1:]) != (h, w) or m.shape[0] < 1:
-                raise ValueError("playthrough(): maps of shape %s for an environment of %d rows x %d columns (at least one map)" % (tuple(m.shape), h, w))
-            m = m.to(device=self.device, dtype=torch.uint8).contiguous()
-        M = int(m.shape[0])
-        power = int(self._prob._solver_power)
-        max_len = min(power, 255) if max_len is None else int(max_len)
-        if max_len < 1:
-            raise ValueError("playthrough(): max_len must be at least 1, got %d" % max_len)
-        cfg = self._config(self._alloc_dims)
-        need = int(self._lib.pcgrl_get_playthrough_bytes(C.byref(cfg), M, max_len))
-        if not need:
-            raise NotImplementedError("playthrough(): no one-call form for this configuration (levels of %d x %d = %d bordered cells, solver_power %d): "
-                                      "the traced searches are the ones that run in LDS -- at most 256 bordered cells and solver_power <= 5000"
-                                      % (h + 2, w + 2, (h + 2) * (w + 2), power))
-        moves = torch.empty((M, max_len), dtype=torch.int8, device=self.device)
-        length = torch.empty((M,), dtype=torch.int32, device=self.device)
-        agent = torch.empty((M,), dtype=torch.int8, device=self.device)
-        rows = torch.empty((M, 8), dtype=torch.int32, device=self.device)
-        if self._eval_work is None or self._eval_work.numel() < need:
-            self._eval_work = torch.empty((need,), dtype=torch.uint8, device=self.device)
-        _lib.check(self._lib.pcgrl_get_playthrough(self._handle, C.c_void_p(m.data_ptr()), M, max_len, C.c_void_p(moves.data_ptr()),
-                                                   C.c_void_p(length.data_ptr()), C.c_void_p(agent.data_ptr()), C.c_void_p(rows.data_ptr()),
-                                                   C.c_void_p(self._eval_work.data_ptr()), self._eval_work.numel(), self._stream()), "pcgrl_get_playthrough")
-        return Playthroughs(moves, length, agent, rows, self._prob.decode_rows(rows))
+        return self._planner_moves("playthrough", "pcgrl_get_playthrough", "pcgrl_get_playthrough_bytes", Playthroughs, lambda w, h, power: (
+            "playthrough(): no one-call form for this configuration (levels of %d x %d = %d bordered cells, solver_power %d): "
+            "the traced searches are the ones that run in LDS -- at most 256 bordered cells and solver_power <= 5000"
+            % (h + 2, w + 2, (h + 2) * (w + 2), power)), maps, max_len)
 
     # ---- the play that SMBProblem._run_game scores (pcgrl_get_smb_play)
     def playthrough_smb(self, maps=None, max_len=None):
@@ -872,50 +836,12 @@ class BatchedPcgrlEnv:
         a tile id >= get_num_tiles() is clamped on the way and reported by check_status(), nothing is waited for; the workspace is
         evaluate()'s (the same one-stream rule).  solver_power is smb's attribute (prob._solver_power, then adjust_param()).
         NotImplementedError for the other problems (mdungeon, ddave: playthrough(); sokoban: solve())."""
-        torch = self._torch
         if self._prob.name != "smb":
             raise NotImplementedError("playthrough_smb(): smb's play only, not problem %r%s"
                                       % (self._prob.name, " (solve() returns sokoban's solution)" if self._prob.name == "sokoban" else
                                          " (playthrough() returns its play)" if self._prob.name in ("mdungeon", "ddave") else ""))
-        if maps is None:
-            if self._handle is None or not self._was_reset or self._needs_reset:
-                raise RuntimeError("playthrough_smb() without maps reads the environment's current levels: call reset() first")
-        dims = (self._prob._width, self._prob._height)
-        if self._handle is None or (not self._was_reset and (self._realloc or dims != self._alloc_dims)):
-            self._allocate()               # (as in evaluate(): bound, not reset)
-            self._realloc = False
-        if self._realloc:
-            raise NotImplementedError("playthrough_smb(): an adjust_param() that this handle could not take in place waits for the next reset(); "
-                                      "the handle still plans with the old parameters")
-        w, h = self._alloc_dims
-        if maps is None:
-            m = self._bufs["map"]
-        else:
-            m = maps if torch.is_tensor(maps) else torch.as_tensor(np.asarray(maps))
-            if m.dim() != 3:
-                raise ValueError("playthrough_smb(): maps must be [M, H, W], got shape %s" % (tuple(m.shape),))
-            if tuple(m.shape[1:]) != (h, w) or m.shape[0] < 1:
-                raise ValueError("playthrough_smb(): maps of shape %s for an environment of %d rows x %d columns (at least one map)" % (tuple(m.shape), h, w))
-            m = m.to(device=self.device, dtype=torch.uint8).contiguous()
-        M = int(m.shape[0])
-        power = int(self._prob._solver_power)
-        max_len = min(power, 255) if max_len is None else int(max_len)
-        if max_len < 1:
-            raise ValueError("playthrough_smb(): max_len must be at least 1, got %d" % max_len)
-        cfg = self._config(self._alloc_dims)
-        need = int(self._lib.pcgrl_get_smb_play_bytes(C.byref(cfg), M, max_len))
-        if not need:
-            raise NotImplementedError("playthrough_smb(): the library does not take this configuration (width %d, height %d, solver_power %d)" % (w, h, power))
-        moves = torch.empty((M, max_len), dtype=torch.int8, device=self.device)
-        length = torch.empty((M,), dtype=torch.int32, device=self.device)
-        agent = torch.empty((M,), dtype=torch.int8, device=self.device)
-        rows = torch.empty((M, 8), dtype=torch.int32, device=self.device)
-        if self._eval_work is None or self._eval_work.numel() < need:
-            self._eval_work = torch.empty((need,), dtype=torch.uint8, device=self.device)
-        _lib.check(self._lib.pcgrl_get_smb_play(self._handle, C.c_void_p(m.data_ptr()), M, max_len, C.c_void_p(moves.data_ptr()),
-                                                C.c_void_p(length.data_ptr()), C.c_void_p(agent.data_ptr()), C.c_void_p(rows.data_ptr()),
-                                                C.c_void_p(self._eval_work.data_ptr()), self._eval_work.numel(), self._stream()), "pcgrl_get_smb_play")
-        return Playthroughs(moves, length, agent, rows, self._prob.decode_rows(rows))
+        return self._planner_moves("playthrough_smb", "pcgrl_get_smb_play", "pcgrl_get_smb_play_bytes", Playthroughs, lambda w, h, power: (
+            "playthrough_smb(): the library does not take this configuration (width %d, height %d, solver_power %d)" % (w, h, power)), maps, max_len)
 
     def _evaluate_by_set_maps(self, m, rows, chunk):
         """evaluate() where pcgrl_get_stats_bytes is 0: a scratch environment of this problem (wide representation, the same

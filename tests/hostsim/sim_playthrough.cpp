@@ -1,5 +1,5 @@
 // The traced MiniDungeons and Dangerous Dave searches of gym_pcgrl_amd/csrc (PlayTrace: mdungeon_solver.h, mdungeon_fast.h,
-// ddave_solver.h, ddave_fast.h) instantiated on the CPU, with the walk-back that k_get_playthrough does (kernels_playthrough.h): the
+// ddave_solver.h, ddave_fast.h) instantiated on the CPU, with the walk-back that k_get_moves does (kernels_moves.h): the
 // four agents of _run_game in its order, the moves of the first winner or -- when nobody wins -- those to the BFS agent's best node.
 // Built by tests/test_playthrough_host.py:  g++ -O2 -std=c++17 -fPIC -shared -o libsim_playthrough.so sim_playthrough.cpp
 // and, with -DSIM_PLAYTHROUGH_MAIN -fsanitize=address,undefined, as a stand-alone program that runs a few built-in levels through

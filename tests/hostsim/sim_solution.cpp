@@ -1,5 +1,5 @@
 // The traced sokoban searches of gym_pcgrl_amd/csrc (SokTrace: sokoban_solver.h, sokoban_fast.h) instantiated on the CPU, with the
-// walk-back that k_get_solution does (kernels_solution.h): the four agents of _run_game in its order, the moves of the first winner.
+// walk-back that k_get_moves does (kernels_moves.h): the four agents of _run_game in its order, the moves of the first winner.
 // Built by tests/test_solution_host.py:  g++ -O2 -std=c++17 -fPIC -shared -o libsim_solution.so sim_solution.cpp
 #include <stdint.h>
 #include <string.h>

@@ -291,3 +291,8 @@ def test_workspace_sizes(prob):
         assert sizes[0] >= int(L.pcgrl_get_stats_bytes(C.byref(cfg), count))
         last = sizes[0]
     assert _bytes(_config(prob, 14, 14), 10, 10) >= 256              # 16 x 16 = 256 bordered cells: the last size with the form
+    # the exact values (the same for both problems), recorded from the library as it was before solve() and playthrough() came to
+    # share one plan
+    for c in (cfg, _config(prob, 14, 14)):
+        for count, want in zip((1, 63, 64, 65, 129, 4096, 65536), (881152, 882944, 882944, 1763840, 2646528, 56492288, 227737856)):
+            assert _bytes(c, count, 1) == want and _bytes(c, count, 255) == want, (count, want)

@@ -193,5 +193,11 @@ def test_workspace_sizes():
             assert sizes[0] >= 256 and sizes[0] % 256 == 0 and sizes == sorted(sizes), (count, sizes)
             assert sizes[0] >= last
             last = sizes[0]
+    # the exact values, recorded from the library as it was before the three calls for a planner's moves came to share one prologue
+    for cfg, wants in ((_config("smb", 4, 9, 200), (164352, 801024, 811264, 821760, 1479168, 42074368, 44040448)),
+                       (_config("smb", 14, 114), (8008192, 39039744, 39540224, 40040960, 72073728, 2050097408, 2052063488)),
+                       (_config("smb", 32, 250, 16383), (13107712, 63899904, 64719104, 65538560, 117969408, 3355574528, 3357540608))):
+        for count, want in zip((1, 63, 64, 65, 129, 4096, 65536), wants):
+            assert _bytes(cfg, count, 1) == want and _bytes(cfg, count, 255) == want, (count, want)
     # a larger solver_power never takes less
     assert _bytes(_config("smb", 14, 114, 16383), 64, 16) > _bytes(_config("smb", 14, 114, 400), 64, 16)

@@ -220,3 +220,7 @@ def test_workspace_sizes():
         assert sizes[0] >= int(_lib.load().pcgrl_get_stats_bytes(C.byref(sok), count))
         last = sizes[0]
     assert _bytes(_config("sokoban", 14, 14), 10, 10) >= 256         # 16 x 16 = 256 bordered cells: the last size with the form
+    # the exact values, recorded from the library as it was before solve() and playthrough() came to share one plan
+    for cfg in (sok, _config("sokoban", 14, 14)):
+        for count, want in zip((1, 63, 64, 65, 129, 4096, 65536), (801024, 802816, 802816, 1603584, 2406144, 51364096, 207225088)):
+            assert _bytes(cfg, count, 1) == want and _bytes(cfg, count, 255) == want, (count, want)
