@@ -106,6 +106,47 @@ def solve_levels(prob, maps, device=None, max_len=None, **params):
     return _on_levels("solve_levels", prob, maps, device, params, lambda env: env.solve(maps, max_len=max_len))
 
 
+def path_levels(prob, maps, device=None, max_len=None, **params):
+    """The paths behind binary's path-length and zelda's path-length / nearest-enemy of a stack of levels in one call, next to
+    solve_levels(): `maps` array-like uint8 [M, H, W], `params` as for adjust_param.  Returns BatchedPcgrlEnv.paths()'s Paths (cells,
+    length, rows, stats)."""
+    return _on_levels("path_levels", prob, maps, device, params, lambda env: env.paths(maps, max_len=max_len))
+
+
+class PathCheck:
+    """What check_path() returns: `legal` bool [T] per cell (in range, on a passable tile, 4-adjacent to the cell before it, not seen
+    before) and `ok`: every cell is legal."""
+    __slots__ = ("legal", "ok")
+
+    def __init__(self, legal, ok):
+        self.legal, self.ok = legal, ok
+
+
+def check_path(level, cells, passable_tiles):
+    """Is `cells` (y * W + x each; a negative entry ends the list, like the -1 padding of Paths.cells) a walk on `level` [H, W] of tile
+    ids: every cell in range, on one of `passable_tiles`, 4-adjacent to the one before it, and none repeated?  Host side, numpy: for a
+    drawing loop, and a check of paths() that owes nothing to a recorded result.  Returns a PathCheck (legal per cell, ok)."""
+    import numpy as np
+    lv = np.asarray(level)
+    if lv.ndim != 2:
+        raise ValueError("check_path(): level must be [H, W], got shape %s" % (lv.shape,))
+    H, W = lv.shape
+    ok_tiles = set(int(t) for t in np.asarray(passable_tiles).reshape(-1).tolist())
+    legal, seen, prev = [], set(), None
+    for c in np.asarray(cells).reshape(-1).tolist():
+        if c < 0:
+            break
+        c = int(c)
+        good = c < H * W and int(lv[c // W, c % W]) in ok_tiles and c not in seen
+        if good and prev is not None:
+            good = prev < H * W and abs(c // W - prev // W) + abs(c % W - prev % W) == 1
+        legal.append(bool(good))
+        seen.add(c)
+        prev = c
+    legal = np.array(legal, bool)
+    return PathCheck(legal, bool(legal.all()))
+
+
 class SokobanReplay:
     """What replay_sokoban() returns: `player` int [T+1, 2] and `crates` int [T+1, K, 2] -- (row, column) per frame, frame 0 the level
     as given, frame t after move t; the crates keep their row-major order of frame 0 -- `targets` int [K', 2], `legal` (every move

@@ -59,6 +59,7 @@
 #include "lanegroup_dev.h"
 #include "mt19937.h"
 #include "pcgrl_algos.h"
+#include "path_trace.h"
 #include "sokoban_solver.h"
 #include "sokoban_fast.h"
 #include "mdungeon_solver.h"
@@ -84,6 +85,7 @@
 #include "kernels_step_solver.h"
 #include "kernels_search_async.h"
 #include "kernels_evaluate.h"
+#include "kernels_paths.h"
 #include "kernels_moves.h"
 #include "kernels_smb_play.h"     // (after kernels_moves.h: SolOut)
 #include "search_big.h"
@@ -630,6 +632,7 @@ PCGRL_LOCAL int launch_smb(pcgrl_env* h, int32_t* sync, int list_a, int mode_a, 
 PCGRL_LOCAL int launch_step_solver(pcgrl_env* h, const int32_t* actions, hipStream_t st, const RolloutArgs& R, int epb);
 PCGRL_LOCAL int launch_get_stats(pcgrl_env* h, const uint8_t* maps, int count, int32_t* rows_out, int32_t* head, int32_t* jobs, hipStream_t st);
 PCGRL_LOCAL int launch_get_stats_search(pcgrl_env* h, const uint8_t* maps, int32_t* rows_out, int32_t* head, const int32_t* jobs, SokNode* pools, int blocks, hipStream_t st);
+PCGRL_LOCAL int launch_get_paths(pcgrl_env* h, const uint8_t* maps, int count, int max_len, int16_t* cells_out, int32_t* length_out, int32_t* rows_out, hipStream_t st);
 PCGRL_LOCAL int launch_get_moves(pcgrl_env* h, const uint8_t* maps, int32_t* rows_out, const SolOut& out, int32_t* head, const int32_t* jobs, SokNode* pools, uint32_t* traces, int blocks, hipStream_t st);
 PCGRL_LOCAL int launch_smb_play(pcgrl_env* h, const uint8_t* maps, int count, int32_t* rows_out, const SolOut& out, int32_t* ticket, uint8_t* arenas, int slots, hipStream_t st);
 PCGRL_LOCAL int launch_search_async(pcgrl_env* h, int32_t* tickets, int list_a, int mode_a, int list_b, int mode_b, int parity, int rst_list, int clr, int budget, int resume, int small, hipStream_t st);
@@ -780,6 +783,20 @@ PCGRL_LOCAL int launch_get_stats(pcgrl_env* h, const uint8_t* maps, int count, i
         constexpr int PROB = prob();
         return with_lanes(P.group, P.mask_bytes, [&](auto g, auto m) {
             return launch<k_get_stats<PROB, g(), type_of<decltype(m)>>>(h, grid, PCGRL_BLOCK, lds, st, P, maps, count, rows_out, h->B.status, head, jobs);
+        });
+    });
+}
+// pcgrl_get_paths (kernels_paths.h): launch_get_stats' grid and stage, binary and zelda only
+PCGRL_LOCAL int launch_get_paths(pcgrl_env* h, const uint8_t* maps, int count, int max_len, int16_t* cells_out, int32_t* length_out, int32_t* rows_out, hipStream_t st) {
+    const PcgrlParams& P = h->P;
+    const int per_block = (PCGRL_BLOCK / 64) * (64 / P.group);            // maps a block takes per round
+    const long long blocks = ((long long)count + per_block - 1) / per_block;
+    const int grid = (int)(blocks < 8192 ? blocks : 8192);
+    const size_t lds = (size_t)per_block * reset_tile_bytes(P.width * P.height);
+    return with_prob<PCGRL_PROB_BINARY, PCGRL_PROB_ZELDA>(P.prob, [&](auto prob) {
+        constexpr int PROB = prob();
+        return with_lanes(P.group, P.mask_bytes, [&](auto g, auto m) {
+            return launch<k_get_paths<PROB, g(), type_of<decltype(m)>>>(h, grid, PCGRL_BLOCK, lds, st, P, maps, count, max_len, cells_out, length_out, rows_out, h->B.status);
         });
     });
 }
@@ -1812,6 +1829,34 @@ int pcgrl_get_smb_play(pcgrl_env* h, const uint8_t* maps, int32_t count, int32_t
                       [&](const SmbPlayPlan& S, uint8_t* w, int32_t* head, int32_t* rows, const SolOut& out, hipStream_t st) -> int {
         return launch_smb_play(h, maps, count, rows, out, head, at<uint8_t>(w, S.arenas), S.slots, st);
     });
+}
+
+// ---- pcgrl_get_paths (kernels_paths.h, path_trace.h): the cells behind binary's path-length and zelda's path-length / nearest-enemy --
+// The workspace, cut from one plan like pcgrl_get_stats': the kernel keeps a sweep's distance classes in registers and needs nothing
+// per map, so the plan is the head every such call has (the size the caller is told stays a whole 256-byte region).
+struct PathsPlan { Region head; size_t total; };
+static PathsPlan paths_plan(const pcgrl_config*, int) {
+    PathsPlan S = {};
+    Bump b = {0};
+    S.head = b.take(256);
+    S.total = b.off;
+    return S;
+}
+int32_t pcgrl_get_paths_legs(const pcgrl_config* c) { return c ? paths_legs(c->prob) : 0; }
+size_t pcgrl_get_paths_bytes(const pcgrl_config* c, int32_t count, int32_t max_len) {
+    if (!c || paths_legs(c->prob) == 0 || max_len < 1 || pcgrl_get_stats_bytes(c, count) == 0) return 0;
+    pcgrl_config one = *c;
+    one.num_envs = 1;
+    return paths_plan(&one, count).total;
+}
+int pcgrl_get_paths(pcgrl_env* h, const uint8_t* maps, int32_t count, int32_t max_len, int16_t* cells_out, int32_t* length_out, int32_t* rows_out,
+                    void* work, size_t work_bytes, void* stream) {
+    if (!h || !h->bound) return PCGRL_ESTATE;
+    if (!maps || !cells_out || !length_out || !work || count < 1 || max_len < 1 || ((uintptr_t)work & 255) != 0) return PCGRL_EINVAL;
+    const size_t need = pcgrl_get_paths_bytes(&h->cfg, count, max_len);
+    if (need == 0 || work_bytes < need) return PCGRL_EINVAL;
+    DeviceGuard guard(h->device);
+    return launch_get_paths(h, maps, count, max_len, cells_out, length_out, rows_out, (hipStream_t)stream);
 }
 
 }  // extern "C"

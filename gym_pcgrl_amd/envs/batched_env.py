@@ -94,6 +94,32 @@ class Playthroughs(_PlannerMoves):
         return self.agent >= 0
 
 
+class Paths:
+    """What BatchedPcgrlEnv.paths() returns: `cells` int16 [M, legs, max_len] (cell i of each leg as y * W + x, start -> target; -1 beyond
+    the leg), `length` int32 [M, legs] (the full length in steps, also beyond max_len; -1: the leg does not exist), `rows` / `stats` as in
+    an Evaluation; `legs`: the legs' names -- ("longest",) for binary, ("key", "door", "enemy") for zelda; `exists` bool [M, legs];
+    `truncated` bool [M, legs]: the row holds only a prefix; xy(): the cells as (x, y)."""
+    __slots__ = ("cells", "length", "rows", "stats", "legs", "width")
+
+    def __init__(self, cells, length, rows, stats, legs, width):
+        self.cells, self.length, self.rows, self.stats, self.legs, self.width = cells, length, rows, stats, legs, width
+
+    @property
+    def exists(self):
+        return self.length >= 0
+
+    @property
+    def truncated(self):
+        return self.length + 1 > self.cells.shape[2]
+
+    def xy(self):
+        """(x, y): two int16 tensors shaped like `cells`, -1 where the cell is -1."""
+        c = self.cells
+        none = c < 0
+        x, y = c % self.width, c // self.width
+        return x.masked_fill(none, -1), y.masked_fill(none, -1)
+
+
 class BatchedPcgrlEnv:
     metadata = {"render.modes": []}
 
@@ -734,7 +760,7 @@ class BatchedPcgrlEnv:
             over = over.view(torch.bool)
         return Evaluation(rows, self._prob.decode_rows(rows), reward, over)
 
-    # ---- what evaluate(), solve(), playthrough() and playthrough_smb() share
+    # ---- what evaluate(), solve(), playthrough(), playthrough_smb() and paths() share
     def _scoring_handle(self):
         """A handle that can take the parameters in force: a new one where there is none yet, or one that was only ever bound for
         scoring and cannot take them (bound, not reset: step() and set_maps() still ask for reset())."""
@@ -842,6 +868,56 @@ class BatchedPcgrlEnv:
                                          " (playthrough() returns its play)" if self._prob.name in ("mdungeon", "ddave") else ""))
         return self._planner_moves("playthrough_smb", "pcgrl_get_smb_play", "pcgrl_get_smb_play_bytes", Playthroughs, lambda w, h, power: (
             "playthrough_smb(): the library does not take this configuration (width %d, height %d, solver_power %d)" % (w, h, power)), maps, max_len)
+
+    # ---- the paths behind path-length / nearest-enemy, binary and zelda (pcgrl_get_paths)
+    PATH_LEGS = {"binary": ("longest",), "zelda": ("key", "door", "enemy")}
+
+    def paths(self, maps=None, max_len=None):
+        """The cells of the paths that the statistics measure, for `maps` -- array-like uint8 [M, H, W] as for evaluate(); None: this
+        environment's current levels (after a reset(); the handle's own map buffer is read in place) -- with the parameters in force.
+        binary: one leg, "longest" -- the longest shortest path `path-length` is the length of (helper.py:250-264).  zelda: three --
+        "key" (player -> key) and "door" (key -> door), whose lengths add up to `path-length`, and "enemy" (player -> the nearest
+        enemy, `nearest-enemy` long), zelda_prob.py:91-110.  The rule that makes each leg unique is in include/pcgrl_hip.h
+        (pcgrl_get_paths).  `max_len`: columns of a leg's row, by default H * W, which holds every leg; a smaller one saves memory at
+        large M (M * legs * max_len * 2 bytes) and leaves prefixes (`truncated`).  Returns Paths (cells, length, rows, stats), all on
+        the device.  A pure function like evaluate(): episodes, random streams and pending asynchronous searches are not touched, a
+        tile id >= get_num_tiles() is clamped on the way and reported by check_status(), nothing is waited for; the workspace is
+        evaluate()'s (the same one-stream rule).  NotImplementedError for the other problems (their routes are plays: solve(),
+        playthrough(), playthrough_smb()) and where the library has no one-call form (maps beyond 64 x 64): there is no
+        scratch-environment route for the cells."""
+        name = self._prob.name
+        if name not in self.PATH_LEGS:
+            raise NotImplementedError("paths(): the paths of binary and zelda only, not problem %r (%s)" % (name, {
+                "sokoban": "solve() returns sokoban's solution", "smb": "playthrough_smb() returns smb's play"}.get(name, "playthrough() returns its play")))
+        torch = self._torch
+        if maps is None:
+            if self._handle is None or not self._was_reset or self._needs_reset:
+                raise RuntimeError("paths() without maps reads the environment's current levels: call reset() first")
+        self._scoring_handle()
+        if self._realloc:
+            raise NotImplementedError("paths(): an adjust_param() that this handle could not take in place waits for the next reset(); "
+                                      "the handle still scores with the old parameters")
+        w, h = self._alloc_dims
+        m = self._bufs["map"] if maps is None else self._as_maps("paths", maps)
+        M = int(m.shape[0])
+        max_len = h * w if max_len is None else int(max_len)
+        if max_len < 1:
+            raise ValueError("paths(): max_len must be at least 1, got %d" % max_len)
+        cfg = self._config(self._alloc_dims)
+        need = int(self._lib.pcgrl_get_paths_bytes(C.byref(cfg), M, max_len))
+        if not need:
+            raise NotImplementedError("paths(): no one-call form for this configuration (maps of %d rows x %d columns): "
+                                      "the row-bitboard kernels take maps up to 64 x 64" % (h, w))
+        legs = self.PATH_LEGS[name]
+        cells = torch.empty((M, len(legs), max_len), dtype=torch.int16, device=self.device)
+        length = torch.empty((M, len(legs)), dtype=torch.int32, device=self.device)
+        rows = torch.empty((M, 8), dtype=torch.int32, device=self.device)
+        if self._eval_work is None or self._eval_work.numel() < need:
+            self._eval_work = torch.empty((need,), dtype=torch.uint8, device=self.device)
+        _lib.check(self._lib.pcgrl_get_paths(self._handle, C.c_void_p(m.data_ptr()), M, max_len, C.c_void_p(cells.data_ptr()),
+                                             C.c_void_p(length.data_ptr()), C.c_void_p(rows.data_ptr()),
+                                             C.c_void_p(self._eval_work.data_ptr()), self._eval_work.numel(), self._stream()), "pcgrl_get_paths")
+        return Paths(cells, length, rows, self._prob.decode_rows(rows), legs, w)
 
     def _evaluate_by_set_maps(self, m, rows, chunk):
         """evaluate() where pcgrl_get_stats_bytes is 0: a scratch environment of this problem (wide representation, the same

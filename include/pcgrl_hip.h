@@ -20,6 +20,8 @@
  *   pcgrl_get_solution               SokobanProblem.get_stats(map)["solution"] sokoban_prob.py:133-145: the planner's moves
  *   pcgrl_get_playthrough            the moves of the play _run_game scores, mdungeon_prob.py:100-138 / ddave_prob.py:92-127
  *   pcgrl_get_smb_play               the same for smb's two agents, smb_prob.py:90-124
+ *   pcgrl_get_paths                  the cells of the paths that binary's path-length (helper.py:250-264) and zelda's path-length /
+ *                                    nearest-enemy (zelda_prob.py:91-110) measure, from the run_dikjstra maps (helper.py:222-237)
  *
  * Conventions: plain pointers and sizes only; every function returns 0 on success or a negative
  * PCGRL_E* code (no exceptions cross the ABI); all device buffers are OWNED BY THE CALLER (hipMalloc,
@@ -51,7 +53,9 @@ extern "C" {
  *     Still 15: + pcgrl_get_solution_bytes / pcgrl_get_solution -- additive in the same way; detected by the symbol pcgrl_get_solution.
  *     Still 15: + pcgrl_get_playthrough_bytes / pcgrl_get_playthrough -- additive in the same way; detected by the symbol
  *     pcgrl_get_playthrough.
- *     Still 15: + pcgrl_get_smb_play_bytes / pcgrl_get_smb_play -- additive in the same way; detected by the symbol pcgrl_get_smb_play. */
+ *     Still 15: + pcgrl_get_smb_play_bytes / pcgrl_get_smb_play -- additive in the same way; detected by the symbol pcgrl_get_smb_play.
+ *     Still 15: + pcgrl_get_paths_legs / pcgrl_get_paths_bytes / pcgrl_get_paths -- additive in the same way; detected by the symbol
+ *     pcgrl_get_paths. */
 #define PCGRL_ABI_VERSION 15
 #define PCGRL_OK 0
 #define PCGRL_EINVAL (-1)   /* bad argument / unsupported configuration */
@@ -344,7 +348,8 @@ int    pcgrl_get_reward(pcgrl_env* env, const int32_t* rows, const int32_t* ref_
  *   PCGRL_EINVAL: a NULL maps / moves_out / length_out / work, count < 1, max_len < 1, work not 256-byte aligned or too small, or a
  *   configuration for which pcgrl_get_solution_bytes is 0.
  * pcgrl_get_solution_bytes: from the configuration alone.  0 wherever pcgrl_get_stats_bytes is 0, for every problem but sokoban (the
- *   other planners' get_stats keep only the length; binary, zelda and smb have no move list) and for max_len < 1; else >= 256. */
+ *   other planners' get_stats keep only the length; binary, zelda and smb have no move list -- binary and zelda have paths:
+ *   pcgrl_get_paths) and for max_len < 1; else >= 256. */
 size_t pcgrl_get_solution_bytes(const pcgrl_config* cfg, int32_t count, int32_t max_len);
 int    pcgrl_get_solution(pcgrl_env* env, const uint8_t* maps, int32_t count, int32_t max_len,
                           int8_t* moves_out, int32_t* length_out, int8_t* agent_out, int32_t* rows_out,
@@ -396,6 +401,45 @@ size_t pcgrl_get_smb_play_bytes(const pcgrl_config* cfg, int32_t count, int32_t 
 int    pcgrl_get_smb_play(pcgrl_env* env, const uint8_t* maps, int32_t count, int32_t max_len,
                           int8_t* moves_out, int32_t* length_out, int8_t* agent_out, int32_t* rows_out,
                           void* work, size_t work_bytes, void* stream);
+/* The paths behind binary's `path-length` and zelda's `path-length` / `nearest-enemy`.  The reference computes the distance maps these
+ * routes follow -- run_dikjstra (helper.py:222-237) inside calc_longest_path (helper.py:250-264) and ZeldaProblem.get_stats
+ * (zelda_prob.py:91-110) -- keeps one number of each and throws the maps away.  This entry returns the cells.  A cell is y * W + x.
+ *   Walk-back: with D = run_dikjstra(sx, sy, map, passable) and a cell t with D[t] >= 0, the leg from (sx, sy) to t is built backwards
+ *   from t: the predecessor of a cell c with D[c] > 0 is the first neighbour n of c in run_dikjstra's order -- (dx, dy) = (-1,0), (1,0),
+ *   (0,-1), (0,1): left, right, up, down -- with D[n] == D[c] - 1.  The leg is reported start -> target: length = D[t] steps,
+ *   length + 1 cells; D[t] == -1: length -1, no cells.  "First" among cells is row-major (np.argmax, get_tile_locations).
+ *   binary, one leg ("longest"): the regions in the order of their first cell; for each, calc_longest_path's first map from that cell,
+ *   (mx, my) = its first arg-max, the second map D2 from (mx, my).  The region is the first whose D2.max() equals the returned
+ *   path-length (the reference updates on `>` only); the leg is the walk-back over D2 from (mx, my) to the first arg-max of D2.  A
+ *   path-length of 0 with an empty tile: that region's single start cell (length 0, one cell).  No empty tile: length -1.  Whenever
+ *   length >= 0, length == path-length.
+ *   zelda, three legs ("key", "door", "enemy"), conditions and passable sets of zelda_prob.py:91-110.  Legs 0 and 1 exist when player == 1
+ *   and regions == 1 and key == 1 and door == 1: leg 0 over run_dikjstra(player; empty, key, player, enemies) to the key, leg 1 over
+ *   run_dikjstra(key; the same + door) to the door, length -1 when the door is walled off; length[0] + length[1] == path-length (the
+ *   reference adds the -1 too).  Leg 2 exists when player == 1 and regions == 1 and enemies > 0 and some enemy has D > 0 in
+ *   run_dikjstra(player; empty, player, enemies) -- the key is not passable there: its target is the first enemy cell with
+ *   D == nearest-enemy, its length is nearest-enemy.  A leg whose condition does not hold has length -1.
+ * Same contract as pcgrl_get_solution: a bound handle, no reset needed, no episode state read or written, of the handle only the sticky
+ * status word written (bit 2: a tile id beyond the last is clamped in the LDS copy, the caller's map stays), asynchronous on the stream.
+ *   maps        DEVICE u8 [count,H,W], read only.
+ *   max_len     columns of a leg's row of cells_out, >= 1 (H * W holds every leg).
+ *   cells_out   DEVICE i16 [count,legs,max_len], legs = pcgrl_get_paths_legs(cfg): cell i of the leg for i < min(length + 1, max_len);
+ *               -1 from there to the end of the row.
+ *   length_out  DEVICE i32 [count,legs]: the full length in steps, also when length + 1 > max_len (the row then holds the first max_len
+ *               cells); -1: the leg does not exist.
+ *   rows_out    DEVICE i32 [count,8] or NULL: exactly what pcgrl_get_stats writes for these maps.
+ *   work        DEVICE, 256-byte aligned, at least pcgrl_get_paths_bytes(cfg, count, max_len) bytes; the call's own.
+ *   PCGRL_EINVAL: a NULL maps / cells_out / length_out / work, count < 1, max_len < 1, work not 256-byte aligned or too small, or a
+ *   configuration for which pcgrl_get_paths_bytes is 0.  PCGRL_ESTATE before pcgrl_bind.
+ * pcgrl_get_paths_legs: 1 for binary, 3 for zelda, 0 for the other problems (their routes are plays: pcgrl_get_solution,
+ *   pcgrl_get_playthrough, pcgrl_get_smb_play) and for a NULL cfg.
+ * pcgrl_get_paths_bytes: from the configuration alone.  Non-zero (then >= 256) exactly for binary and zelda where pcgrl_get_stats_bytes is
+ *   non-zero (maps up to 64 x 64), with count >= 1 and max_len >= 1. */
+int32_t pcgrl_get_paths_legs(const pcgrl_config* cfg);
+size_t pcgrl_get_paths_bytes(const pcgrl_config* cfg, int32_t count, int32_t max_len);
+int    pcgrl_get_paths(pcgrl_env* env, const uint8_t* maps, int32_t count, int32_t max_len,
+                       int16_t* cells_out, int32_t* length_out, int32_t* rows_out,
+                       void* work, size_t work_bytes, void* stream);
 /* ActionMap.step for the wide representation (wrappers.py:139-154): flat DEVICE i32 [N] index into
  * (H, W, tiles) -> xyv DEVICE i32 [N,3] = (x, y, tile), the action pcgrl_step takes. */
 int pcgrl_action_map(pcgrl_env* env, const int32_t* flat, int32_t* xyv, void* stream);
