@@ -183,12 +183,14 @@ def oracle_tape(prob, rep, calls, E, T, seed0, rs, sample=None):
 
 
 def run_config(prob, rep, calls, E, T, seed0, rs, use_rollout, mixed=False, steps_scale=1.0, auto_reset=True, map_every=MAP_EVERY,
-               tuning=None, sample=None, tape=None):
+               tuning=None, sample=None, tape=None, setup=None):
     """One configuration on the GPU against the oracle.  `mixed`: the first part of the tape as one rollout of ODD length,
     the rest as single steps on the same handle (switching between the fused and the work-list pipelines).  auto_reset=False:
     the environments step on past done, the oracle without reset().  tuning: the library's developer switches for this handle.
     sample: indices of the environments compared with the oracle (default: all).  tape: (acts, exp) of oracle_tape -- the actions
-    and the oracle's side made beforehand (`rs` is then not drawn from).  Returns None or a string describing the first mismatch."""
+    and the oracle's side made beforehand (`rs` is then not drawn from).  setup: called with the batch after `calls`, before reset() -- for what
+    adjust_param does not take (smb's solver_power); the tape's oracle side has to be made the same way.  Returns None or a string describing
+    the first mismatch."""
     import torch
     from gym_pcgrl_amd.envs import BatchedPcgrlEnv
     T = max(4, int(T * steps_scale))
@@ -196,6 +198,9 @@ def run_config(prob, rep, calls, E, T, seed0, rs, use_rollout, mixed=False, step
     try:
         for kw in calls:
             env.adjust_param(**kw)
+        if setup is not None:
+            assert tape is not None, "setup= needs the oracle's side made the same way: pass tape="
+            setup(env)
         env.reset()
         sp = env.single_action_space
         dims = [sp.n] if hasattr(sp, "n") else [int(k) for k in sp.nvec]

@@ -2,7 +2,8 @@
 small copies (kernel_rows=False) on a twin batch -- same seeds, a policy that is a pure function of the observation, two consecutive
 rollouts -- bit for bit: every tensor of the buffer, the Monitor columns (float columns as int64: NaN patterns count) and the
 environments' own state afterwards.  One case per pipeline that writes rows: the fused k_step (its row-writing instantiations, all
-block sizes, the flat-index path), k_update + k_stats, k_stats_wide, k_big, the lockstep searches, k_smb, and the asynchronous ticks."""
+block sizes, the flat-index path), k_update + k_stats, k_stats_wide, k_big, the lockstep searches, k_smb, k_update_block (action widths 2
+and 9), and the asynchronous ticks behind k_update and behind k_update_block."""
 import ctypes as C
 
 import numpy as np
@@ -24,7 +25,20 @@ def _policy_for(torch, space):
     return policy
 
 
-def _collect_twins(env_id, rep, N, T, monitor, pop_budget=None, nslots=None, kw=None):
+def _policy_by_digits(torch, space):
+    """For the (type, value) action spaces: _policy_for's multipliers 3 and 5 leave a type below 3 or 6 at 0 (or 3) and a value below 5
+    at 0 -- no block is ever written.  Here every column is its own digit of the hash, so every type and value occurs."""
+    nvec = torch.as_tensor(np.asarray(space.nvec), dtype=torch.int64, device="cuda:0")
+    div = torch.as_tensor([7 ** i for i in range(nvec.numel())], dtype=torch.int64, device="cuda:0")
+
+    def policy(obs):
+        flat = obs.reshape(obs.shape[0], -1).to(torch.int64)
+        w = torch.arange(1, flat.shape[1] + 1, device=obs.device, dtype=torch.int64) % 97 + 1
+        return ((flat * w).sum(1)[:, None] // div[None, :]) % nvec[None, :]
+    return policy
+
+
+def _collect_twins(env_id, rep, N, T, monitor, pop_budget=None, nslots=None, kw=None, policy_for=None):
     """-> per kernel_rows in (True, False): the snapshots of two consecutive rollouts and of the environments' state afterwards."""
     import torch
     from gym_pcgrl_amd.rollout import RolloutCollector
@@ -37,7 +51,7 @@ def _collect_twins(env_id, rep, N, T, monitor, pop_budget=None, nslots=None, kw=
             assert e.enable_async(nslots)
         col = RolloutCollector(venv, T, kernel_rows=rows)
         assert col.kernel_rows is rows
-        policy = _policy_for(torch, venv.action_space)
+        policy = (policy_for or _policy_for)(torch, venv.action_space)
         snap = {"direct": col.direct}
         for r in range(2):
             b = col.collect(policy, pop_budget=pop_budget)
@@ -100,8 +114,12 @@ def test_row_kernel_behind_the_other_pipelines(monkeypatch, env_id, rep, N, T, k
     from gym_pcgrl_amd import _lib
     for k, v in tune.items():
         monkeypatch.setitem(_lib.TUNING_OVERRIDES, k, v)
-    rows, copies = _collect_twins(env_id, rep, N, T, True, kw=kw)
+    # (type, value) actions: every type and value, so that blocks are written (_policy_by_digits)
+    rows, copies = _collect_twins(env_id, rep, N, T, True, kw=kw, policy_for=_policy_by_digits if rep == "narrowcast" else None)
     _assert_same(rows, copies)
+    if rep == "narrowcast":
+        a = rows["0/actions"].reshape(-1, 2).cpu().numpy()
+        assert set(a[:, 0].tolist()) == {0, 1, 2} and set(a[:, 1].tolist()) == {0, 1}
 
 
 # ---- asynchronous ticks: took / fresh, zeroed rewards, carried episode starts
@@ -124,6 +142,19 @@ def test_asynchronous_ticks_write_the_row(env_id, kw, budget, nslots):
     rows, copies = _collect_twins(env_id, "narrow", N, T, True, pop_budget=budget, nslots=nslots, kw=kw)
     _assert_same(rows, copies)
     _async_masks(rows)
+
+
+@pytest.mark.parametrize("env_id,rep,kw", [("sokoban-narrowmulti-v0", "narrowmulti", dict(change_percentage=0.6)), ("sokoban-turtlecast-v0", "turtlecast", dict(change_percentage=0.6))])
+def test_asynchronous_ticks_write_the_row_block_representations(env_id, rep, kw):
+    """The same for the representations of k_update_block (its own copy of the tick's preamble writes `took`): int64 actions of
+    width 9 and 2 under ticks.  Slots for every environment, so that no search overflows (see above)."""
+    N, T = 384, 40
+    rows, copies = _collect_twins(env_id, rep, N, T, True, pop_budget=4, nslots=1024, kw=kw, policy_for=_policy_by_digits if rep == "turtlecast" else None)
+    _assert_same(rows, copies)
+    _async_masks(rows)
+    if rep == "turtlecast":         # the policy really moves and writes: all six types, every tile
+        a = rows["0/actions"].reshape(-1, 2).cpu().numpy()
+        assert set(a[:, 0].tolist()) == set(range(6)) and set(a[:, 1].tolist()) == set(range(5))
 
 
 @pytest.mark.parametrize("budget", [4, 40])
