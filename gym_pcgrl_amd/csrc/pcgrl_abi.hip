@@ -772,31 +772,32 @@ PCGRL_LOCAL int launch_update(pcgrl_env* h, const int32_t* actions, int parity, 
         });
     });
 }
-// pcgrl_get_stats, first launch (kernels_evaluate.h): a lane group per map, grid-stride over `count`
-PCGRL_LOCAL int launch_get_stats(pcgrl_env* h, const uint8_t* maps, int count, int32_t* rows_out, int32_t* head, int32_t* jobs, hipStream_t st) {
-    const PcgrlParams& P = h->P;
+// A lane group per caller-supplied map, grid-stride over `count`: the blocks, and the LDS where a block stages its maps' tiles
+struct MapGrid { int grid; size_t lds; };
+static MapGrid map_grid(const PcgrlParams& P, int count) {
     const int per_block = (PCGRL_BLOCK / 64) * (64 / P.group);            // maps a block takes per round
     const long long blocks = ((long long)count + per_block - 1) / per_block;
-    const int grid = (int)(blocks < 8192 ? blocks : 8192);
-    const size_t lds = (size_t)per_block * reset_tile_bytes(P.width * P.height);
+    return {(int)(blocks < 8192 ? blocks : 8192), (size_t)per_block * reset_tile_bytes(P.width * P.height)};
+}
+// pcgrl_get_stats, first launch (kernels_evaluate.h)
+PCGRL_LOCAL int launch_get_stats(pcgrl_env* h, const uint8_t* maps, int count, int32_t* rows_out, int32_t* head, int32_t* jobs, hipStream_t st) {
+    const PcgrlParams& P = h->P;
+    const MapGrid G = map_grid(P, count);
     return with_prob<PCGRL_PROB_BINARY, PCGRL_PROB_ZELDA, PCGRL_PROB_MDUNGEON, PCGRL_PROB_DDAVE, PCGRL_PROB_SOKOBAN>(P.prob, [&](auto prob) {
         constexpr int PROB = prob();
         return with_lanes(P.group, P.mask_bytes, [&](auto g, auto m) {
-            return launch<k_get_stats<PROB, g(), type_of<decltype(m)>>>(h, grid, PCGRL_BLOCK, lds, st, P, maps, count, rows_out, h->B.status, head, jobs);
+            return launch<k_get_stats<PROB, g(), type_of<decltype(m)>>>(h, G.grid, PCGRL_BLOCK, G.lds, st, P, maps, count, rows_out, h->B.status, head, jobs);
         });
     });
 }
 // pcgrl_get_paths (kernels_paths.h): launch_get_stats' grid and stage, binary and zelda only
 PCGRL_LOCAL int launch_get_paths(pcgrl_env* h, const uint8_t* maps, int count, int max_len, int16_t* cells_out, int32_t* length_out, int32_t* rows_out, hipStream_t st) {
     const PcgrlParams& P = h->P;
-    const int per_block = (PCGRL_BLOCK / 64) * (64 / P.group);            // maps a block takes per round
-    const long long blocks = ((long long)count + per_block - 1) / per_block;
-    const int grid = (int)(blocks < 8192 ? blocks : 8192);
-    const size_t lds = (size_t)per_block * reset_tile_bytes(P.width * P.height);
+    const MapGrid G = map_grid(P, count);
     return with_prob<PCGRL_PROB_BINARY, PCGRL_PROB_ZELDA>(P.prob, [&](auto prob) {
         constexpr int PROB = prob();
         return with_lanes(P.group, P.mask_bytes, [&](auto g, auto m) {
-            return launch<k_get_paths<PROB, g(), type_of<decltype(m)>>>(h, grid, PCGRL_BLOCK, lds, st, P, maps, count, max_len, cells_out, length_out, rows_out, h->B.status);
+            return launch<k_get_paths<PROB, g(), type_of<decltype(m)>>>(h, G.grid, PCGRL_BLOCK, G.lds, st, P, maps, count, max_len, cells_out, length_out, rows_out, h->B.status);
         });
     });
 }
@@ -883,36 +884,37 @@ PCGRL_LOCAL int smb_device_setup(pcgrl_env*) {
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_smb_play<0>), hipFuncAttributeMaxDynamicSharedMemorySize, SMB_LDS_BUDGET));
     return PCGRL_OK;
 }
-PCGRL_LOCAL int launch_smb(pcgrl_env* h, int32_t* sync, int list_a, int mode_a, int list_b, int mode_b, int parity, int rst_list, int clr, hipStream_t st, int inline_reset) {
-    // per wavefront: the heap (smb_search: its first levels; a deeper heap continues in the arena) + the visited bitmap;
-    // as many wavefronts per block (one block per compute unit) as the LDS budget holds, SMB_MAX_WAVES at most
-    int heap_n = 4 * h->P.solver_power + 4 < h->smb_heap ? ((4 * h->P.solver_power + 4 + 3) & ~3) : h->smb_heap;
-    const int reset_words = reset_stage_bytes(h->P.width * h->P.height) / 4;       // the in-kernel reset stages its ring and tiles there
-    if (heap_n < reset_words) heap_n = (reset_words + 3) & ~3;
+// The LDS budget of a k_smb / k_smb_play block, split: per wavefront the heap (smb_search: its first levels; a deeper heap continues
+// in the arena; `floor_words` at least) + the visited bitmap; as many wavefronts per block (one block per compute unit) as the budget
+// holds, SMB_MAX_WAVES at most.  false: one search does not fit a compute unit's LDS.
+struct SmbSplit { int heap_n, nw; size_t per_wave; };
+static bool smb_lds_split(const pcgrl_env* h, int floor_words, SmbSplit* S) {
+    S->heap_n = 4 * h->P.solver_power + 4 < h->smb_heap ? ((4 * h->P.solver_power + 4 + 3) & ~3) : h->smb_heap;
+    if (S->heap_n < floor_words) S->heap_n = (floor_words + 3) & ~3;
     const size_t vis_words = ((size_t)((h->P.width + 6) * (h->P.height + SMB_YOFF + 1) * 5 + 31) / 32 + 3) & ~(size_t)3;
-    const size_t per_wave = ((size_t)heap_n + vis_words) * 4;
-    int nw = (int)(SMB_LDS_BUDGET / per_wave);
-    nw = nw > SMB_MAX_WAVES ? SMB_MAX_WAVES : (nw < 1 ? 1 : nw);
-    if ((size_t)nw * per_wave > SMB_LDS_BUDGET) return PCGRL_EINVAL;      // one search does not fit a compute unit's LDS
+    S->per_wave = ((size_t)S->heap_n + vis_words) * 4;
+    const int nw = (int)(SMB_LDS_BUDGET / S->per_wave);
+    S->nw = nw > SMB_MAX_WAVES ? SMB_MAX_WAVES : (nw < 1 ? 1 : nw);
+    return (size_t)S->nw * S->per_wave <= SMB_LDS_BUDGET;
+}
+PCGRL_LOCAL int launch_smb(pcgrl_env* h, int32_t* sync, int list_a, int mode_a, int list_b, int mode_b, int parity, int rst_list, int clr, hipStream_t st, int inline_reset) {
+    SmbSplit S;
+    if (!smb_lds_split(h, reset_stage_bytes(h->P.width * h->P.height) / 4, &S)) return PCGRL_EINVAL;   // (the in-kernel reset stages its ring and tiles in the heap)
     // (a step's changed levels come on two lists: WL_INC = the ones expected to take long, first; see k_update)
-    return launch_fn(k_smb<0>, SOK_BLOCKS, nw * 64, nw * per_wave, st, h->P, h->B, (list_a == WL_CHG && mode_a == MODE_STEP) ? (int)WL_INC : -1,
-                     list_a, mode_a, list_b, mode_b, parity, rst_list, sync, clr, heap_n, inline_reset, gen_flag(h));
+    return launch_fn(k_smb<0>, SOK_BLOCKS, S.nw * 64, S.nw * S.per_wave, st, h->P, h->B, (list_a == WL_CHG && mode_a == MODE_STEP) ? (int)WL_INC : -1,
+                     list_a, mode_a, list_b, mode_b, parity, rst_list, sync, clr, S.heap_n, inline_reset, gen_flag(h));
 }
 // pcgrl_get_smb_play (kernels_smb_play.h): k_smb's blocks -- the same split of the LDS budget, without the in-kernel reset's staging
 // area -- on `count` levels; `slots` wavefront arenas of smb_play_wave_bytes each are the caller's (SmbPlayPlan)
 PCGRL_LOCAL int launch_smb_play(pcgrl_env* h, const uint8_t* maps, int count, int32_t* rows_out, const SolOut& out, int32_t* ticket, uint8_t* arenas, int slots, hipStream_t st) {
-    const int heap_n = 4 * h->P.solver_power + 4 < h->smb_heap ? ((4 * h->P.solver_power + 4 + 3) & ~3) : h->smb_heap;
-    const size_t vis_words = ((size_t)((h->P.width + 6) * (h->P.height + SMB_YOFF + 1) * 5 + 31) / 32 + 3) & ~(size_t)3;
-    const size_t per_wave = ((size_t)heap_n + vis_words) * 4;
-    int nw = (int)(SMB_LDS_BUDGET / per_wave);
-    nw = nw > SMB_MAX_WAVES ? SMB_MAX_WAVES : (nw < 1 ? 1 : nw);
-    if ((size_t)nw * per_wave > SMB_LDS_BUDGET) return PCGRL_EINVAL;      // one search does not fit a compute unit's LDS
-    if (nw > count) nw = count;
+    SmbSplit S;
+    if (!smb_lds_split(h, 0, &S)) return PCGRL_EINVAL;
+    const int nw = S.nw > count ? count : S.nw;
     int blocks = (count + nw - 1) / nw;
     blocks = blocks > SOK_BLOCKS ? SOK_BLOCKS : blocks;
     if ((long long)blocks * nw > slots) return PCGRL_EINVAL;              // (the plan holds count + SMB_MAX_WAVES - 1 arenas, or all of them)
-    return launch_fn(k_smb_play<0>, blocks, nw * 64, nw * per_wave, st, h->P, maps, count, rows_out, out, h->B.status, ticket, arenas,
-                     smb_play_wave_bytes(h->P.solver_power), nw, heap_n);
+    return launch_fn(k_smb_play<0>, blocks, nw * 64, nw * S.per_wave, st, h->P, maps, count, rows_out, out, h->B.status, ticket, arenas,
+                     smb_play_wave_bytes(h->P.solver_power), nw, S.heap_n);
 }
 #endif  // PART_SMB
 #if PCGRL_IN_PART(PART_SEARCH)
@@ -1697,18 +1699,25 @@ static EvalPlan eval_plan(const pcgrl_config* c, int count) {
     E.total = b.off;
     return E;
 }
+// `c` for one environment -- no workspace depends on the handle's batch -- and whether that is a configuration the library takes
+static bool one_env(const pcgrl_config* c, pcgrl_config* one) {
+    (*one = *c).num_envs = 1;
+    return validate_config(one) == PCGRL_OK;
+}
+// What pcgrl_get_stats, moves_call and pcgrl_get_paths verify before they do anything: a bound handle, the pointers the call cannot
+// do without (`ptrs`), at least one level and one column, a 256-byte aligned workspace of the call's own `need` bytes (0: no form)
+static int readout_check(const pcgrl_env* h, bool ptrs, int32_t count, int32_t max_len, const void* work, size_t work_bytes, size_t need) {
+    if (!h || !h->bound) return PCGRL_ESTATE;
+    const bool args_ok = ptrs && work && count >= 1 && max_len >= 1 && ((uintptr_t)work & 255) == 0;
+    return args_ok && need != 0 && work_bytes >= need ? PCGRL_OK : PCGRL_EINVAL;
+}
 size_t pcgrl_get_stats_bytes(const pcgrl_config* c, int32_t count) {
-    if (!c || count < 1) return 0;
-    pcgrl_config one = *c;
-    one.num_envs = 1;                    // (the workspace does not depend on the handle's batch)
-    if (validate_config(&one) != PCGRL_OK || !eval_applies(&one)) return 0;
+    pcgrl_config one;
+    if (!c || count < 1 || !one_env(c, &one) || !eval_applies(&one)) return 0;
     return eval_plan(&one, count).total;
 }
 int pcgrl_get_stats(pcgrl_env* h, const uint8_t* maps, int32_t count, int32_t* rows_out, void* work, size_t work_bytes, void* stream) {
-    if (!h || !h->bound) return PCGRL_ESTATE;
-    if (!maps || !rows_out || !work || count < 1 || ((uintptr_t)work & 255) != 0) return PCGRL_EINVAL;
-    const size_t need = pcgrl_get_stats_bytes(&h->cfg, count);
-    if (need == 0 || work_bytes < need) return PCGRL_EINVAL;
+    if (int rc = readout_check(h, maps && rows_out, count, 1, work, work_bytes, h ? pcgrl_get_stats_bytes(&h->cfg, count) : 0)) return rc;
     DeviceGuard guard(h->device);
     hipStream_t st = (hipStream_t)stream;
     const EvalPlan E = eval_plan(&h->cfg, count);
@@ -1761,9 +1770,8 @@ static SmbPlayPlan smb_play_plan(const pcgrl_config* c, int count) {
 }
 static Region plan_head(const SmbPlayPlan& S) { return S.head; }
 static size_t moves_bytes(const pcgrl_config* c, int32_t count, int32_t max_len, bool right_problem) {
-    if (!c || !right_problem || max_len < 1 || pcgrl_get_stats_bytes(c, count) == 0) return 0;
-    pcgrl_config one = *c;
-    one.num_envs = 1;
+    pcgrl_config one;
+    if (!c || !right_problem || max_len < 1 || pcgrl_get_stats_bytes(c, count) == 0 || !one_env(c, &one)) return 0;
     return moves_plan(&one, count).total;
 }
 size_t pcgrl_get_solution_bytes(const pcgrl_config* c, int32_t count, int32_t max_len) {
@@ -1773,10 +1781,8 @@ size_t pcgrl_get_playthrough_bytes(const pcgrl_config* c, int32_t count, int32_t
     return moves_bytes(c, count, max_len, c && (c->prob == PCGRL_MDUNGEON || c->prob == PCGRL_DDAVE));
 }
 size_t pcgrl_get_smb_play_bytes(const pcgrl_config* c, int32_t count, int32_t max_len) {
-    if (!c || c->prob != PCGRL_SMB || count < 1 || max_len < 1) return 0;
-    pcgrl_config one = *c;
-    one.num_envs = 1;                    // (the workspace does not depend on the handle's batch)
-    if (validate_config(&one) != PCGRL_OK) return 0;
+    pcgrl_config one;
+    if (!c || c->prob != PCGRL_SMB || count < 1 || max_len < 1 || !one_env(c, &one)) return 0;
     return smb_play_plan(&one, count).total;
 }
 // What the three calls do before their launches: the checks (`bytes`: the call's own *_bytes, 0 for another problem), the workspace
@@ -1786,10 +1792,7 @@ template <class Plan, class Launch>
 static int moves_call(pcgrl_env* h, const uint8_t* maps, int32_t count, int32_t max_len, int8_t* moves_out, int32_t* length_out, int8_t* agent_out,
                       int32_t* rows_out, void* work, size_t work_bytes, void* stream, size_t (*bytes)(const pcgrl_config*, int32_t, int32_t),
                       Plan (*plan)(const pcgrl_config*, int), Launch launch) {
-    if (!h || !h->bound) return PCGRL_ESTATE;
-    if (!maps || !moves_out || !length_out || !work || count < 1 || max_len < 1 || ((uintptr_t)work & 255) != 0) return PCGRL_EINVAL;
-    const size_t need = bytes(&h->cfg, count, max_len);
-    if (need == 0 || work_bytes < need) return PCGRL_EINVAL;
+    if (int rc = readout_check(h, maps && moves_out && length_out, count, max_len, work, work_bytes, h ? bytes(&h->cfg, count, max_len) : 0)) return rc;
     DeviceGuard guard(h->device);
     hipStream_t st = (hipStream_t)stream;
     const Plan S = plan(&h->cfg, count);
@@ -1844,17 +1847,13 @@ static PathsPlan paths_plan(const pcgrl_config*, int) {
 }
 int32_t pcgrl_get_paths_legs(const pcgrl_config* c) { return c ? paths_legs(c->prob) : 0; }
 size_t pcgrl_get_paths_bytes(const pcgrl_config* c, int32_t count, int32_t max_len) {
-    if (!c || paths_legs(c->prob) == 0 || max_len < 1 || pcgrl_get_stats_bytes(c, count) == 0) return 0;
-    pcgrl_config one = *c;
-    one.num_envs = 1;
+    pcgrl_config one;
+    if (!c || paths_legs(c->prob) == 0 || max_len < 1 || pcgrl_get_stats_bytes(c, count) == 0 || !one_env(c, &one)) return 0;
     return paths_plan(&one, count).total;
 }
 int pcgrl_get_paths(pcgrl_env* h, const uint8_t* maps, int32_t count, int32_t max_len, int16_t* cells_out, int32_t* length_out, int32_t* rows_out,
                     void* work, size_t work_bytes, void* stream) {
-    if (!h || !h->bound) return PCGRL_ESTATE;
-    if (!maps || !cells_out || !length_out || !work || count < 1 || max_len < 1 || ((uintptr_t)work & 255) != 0) return PCGRL_EINVAL;
-    const size_t need = pcgrl_get_paths_bytes(&h->cfg, count, max_len);
-    if (need == 0 || work_bytes < need) return PCGRL_EINVAL;
+    if (int rc = readout_check(h, maps && cells_out && length_out, count, max_len, work, work_bytes, h ? pcgrl_get_paths_bytes(&h->cfg, count, max_len) : 0)) return rc;
     DeviceGuard guard(h->device);
     return launch_get_paths(h, maps, count, max_len, cells_out, length_out, rows_out, (hipStream_t)stream);
 }

@@ -466,6 +466,15 @@ class BatchedPcgrlEnv:
             _lib.check(self._lib.pcgrl_bind_row(self._handle, C.byref(r)), "pcgrl_bind_row")
         self._row_applied = key
 
+    def _step_result(self):
+        """Behind the library call of step(), step_flat() and tick(): the strict status check, then the live views they return."""
+        if self.strict_actions:
+            self.check_status()
+        b = self._bufs
+        decode = self._prob.decode_rows if self._prob.packed_rows else None
+        info = InfoBatch(self._prob.info_keys, b["info"], self._max_iterations, self._max_changes, decode)
+        return self._obs(), b["reward"], b["done"].view(self._torch.bool), info
+
     def step(self, actions):
         """pcgrl_env.py:129-150 for every environment.  actions: int [N] (narrow/turtle) or [N,3]
         (wide: x, y, tile).  Returns (obs, reward f64[N], done bool[N], InfoBatch); tensors are views
@@ -476,12 +485,7 @@ class BatchedPcgrlEnv:
         self._last_actions = a   # keep the buffer alive until the launches are done
         _lib.check(self._lib.pcgrl_step(self._handle, C.c_void_p(a.data_ptr()), self._stream()), "pcgrl_step")
         self._row_rest()
-        if self.strict_actions:
-            self.check_status()
-        b = self._bufs
-        decode = self._prob.decode_rows if self._prob.packed_rows else None
-        info = InfoBatch(self._prob.info_keys, b["info"], self._max_iterations, self._max_changes, decode)
-        return self._obs(), b["reward"], b["done"].view(self._torch.bool), info
+        return self._step_result()
 
     def step_flat(self, flat, xyv):
         """ActionMap.step + step() for the wide representation in one call of the library (pcgrl_step_flat): `flat` int32 or int64 [N] device
@@ -492,12 +496,7 @@ class BatchedPcgrlEnv:
         self._last_actions = (flat, xyv)
         _lib.check(self._lib.pcgrl_step_flat(self._handle, C.c_void_p(flat.data_ptr()), C.c_void_p(xyv.data_ptr()), self._stream()), "pcgrl_step_flat")
         self._row_rest()
-        if self.strict_actions:
-            self.check_status()
-        b = self._bufs
-        decode = self._prob.decode_rows if self._prob.packed_rows else None
-        info = InfoBatch(self._prob.info_keys, b["info"], self._max_iterations, self._max_changes, decode)
-        return self._obs(), b["reward"], b["done"].view(self._torch.bool), info
+        return self._step_result()
 
     def rollout(self, actions, want_info=True, out=None):
         """`T` consecutive steps on a tape of actions: int tensor [T, N] (narrow, turtle), [T, N, 3] (wide), [T, N, 2] /
@@ -643,12 +642,7 @@ class BatchedPcgrlEnv:
         self._last_actions = a
         _lib.check(self._lib.pcgrl_step_async(self._handle, C.c_void_p(a.data_ptr()), int(pop_budget), self._stream()), "pcgrl_step_async")
         self._row_rest()
-        if self.strict_actions:
-            self.check_status()
-        b = self._bufs
-        decode = self._prob.decode_rows if self._prob.packed_rows else None
-        info = InfoBatch(self._prob.info_keys, b["info"], self._max_iterations, self._max_changes, decode)
-        return self._obs(), b["reward"], b["done"].view(self._torch.bool), info, self._async["pending"]
+        return self._step_result() + (self._async["pending"],)
 
     def async_idle(self):
         """bool [N] device tensor (a new one, not a view): the environments that take their action at the next tick -- those with no
@@ -739,10 +733,8 @@ class BatchedPcgrlEnv:
         cfg = self._config(self._alloc_dims)
         need = 0 if stale else int(self._lib.pcgrl_get_stats_bytes(C.byref(cfg), M))
         if need:
-            if self._eval_work is None or self._eval_work.numel() < need:
-                self._eval_work = torch.empty((need,), dtype=torch.uint8, device=self.device)
             _lib.check(self._lib.pcgrl_get_stats(self._handle, C.c_void_p(m.data_ptr()), M, C.c_void_p(rows.data_ptr()),
-                                                 C.c_void_p(self._eval_work.data_ptr()), self._eval_work.numel(), self._stream()), "pcgrl_get_stats")
+                                                 *self._workspace(need), self._stream()), "pcgrl_get_stats")
         else:
             self._evaluate_by_set_maps(m, rows, int(chunk))
         reward = over = None
@@ -780,37 +772,48 @@ class BatchedPcgrlEnv:
             raise ValueError("%s(): maps of shape %s for an environment of %d rows x %d columns (at least one map)" % (who, tuple(m.shape), h, w))
         return m.to(device=self.device, dtype=torch.uint8).contiguous()
 
-    def _planner_moves(self, who, fn, bytes_fn, result_cls, no_form_message, maps, max_len):
-        """solve(), playthrough() and playthrough_smb() behind their problem checks: library call `fn` with the workspace `bytes_fn`
-        asks for, on `maps` or (None) the handle's own map buffer.  `no_form_message(w, h, power)`: the text where `bytes_fn` gives 0."""
-        torch = self._torch
+    def _workspace(self, need):
+        """The cached workspace, grown to `need` bytes: the (pointer, size) pair a library call takes."""
+        if self._eval_work is None or self._eval_work.numel() < need:
+            self._eval_work = self._torch.empty((need,), dtype=self._torch.uint8, device=self.device)
+        return C.c_void_p(self._eval_work.data_ptr()), self._eval_work.numel()
+
+    def _readout(self, who, verb, bytes_fn, no_form_message, maps, max_len, default_len):
+        """solve(), playthrough(), playthrough_smb() and paths() behind their problem checks, up to their outputs: the levels `m` ([M,
+        H, W]: `maps`, or (None) the handle's own map buffer), `max_len` (None: `default_len(w, h)`) and the workspace
+        `bytes_fn` asks for, as (m, M, max_len, work).  `no_form_message(w, h)`: the text where `bytes_fn` gives 0."""
         if maps is None:
             if self._handle is None or not self._was_reset or self._needs_reset:
                 raise RuntimeError("%s() without maps reads the environment's current levels: call reset() first" % who)
         self._scoring_handle()
         if self._realloc:
             raise NotImplementedError("%s(): an adjust_param() that this handle could not take in place waits for the next reset(); "
-                                      "the handle still plans with the old parameters" % who)
+                                      "the handle still %s with the old parameters" % (who, verb))
         w, h = self._alloc_dims
         m = self._bufs["map"] if maps is None else self._as_maps(who, maps)
         M = int(m.shape[0])
-        power = int(self._prob._solver_power)
-        max_len = min(power, 255) if max_len is None else int(max_len)
+        max_len = default_len(w, h) if max_len is None else int(max_len)
         if max_len < 1:
             raise ValueError("%s(): max_len must be at least 1, got %d" % (who, max_len))
         cfg = self._config(self._alloc_dims)
         need = int(getattr(self._lib, bytes_fn)(C.byref(cfg), M, max_len))
         if not need:
-            raise NotImplementedError(no_form_message(w, h, power))
+            raise NotImplementedError(no_form_message(w, h))
+        return m, M, max_len, self._workspace(need)
+
+    def _planner_moves(self, who, fn, bytes_fn, result_cls, no_form_message, maps, max_len):
+        """solve(), playthrough() and playthrough_smb() behind their problem checks: library call `fn` with the workspace `bytes_fn`
+        asks for, on `maps` or (None) the handle's own map buffer.  `no_form_message(w, h, power)`: the text where `bytes_fn` gives 0."""
+        torch = self._torch
+        power = int(self._prob._solver_power)
+        m, M, max_len, work = self._readout(who, "plans", bytes_fn, lambda w, h: no_form_message(w, h, power), maps, max_len, lambda w, h: min(power, 255))
         moves = torch.empty((M, max_len), dtype=torch.int8, device=self.device)
         length = torch.empty((M,), dtype=torch.int32, device=self.device)
         agent = torch.empty((M,), dtype=torch.int8, device=self.device)
         rows = torch.empty((M, 8), dtype=torch.int32, device=self.device)
-        if self._eval_work is None or self._eval_work.numel() < need:
-            self._eval_work = torch.empty((need,), dtype=torch.uint8, device=self.device)
         _lib.check(getattr(self._lib, fn)(self._handle, C.c_void_p(m.data_ptr()), M, max_len, C.c_void_p(moves.data_ptr()),
                                           C.c_void_p(length.data_ptr()), C.c_void_p(agent.data_ptr()), C.c_void_p(rows.data_ptr()),
-                                          C.c_void_p(self._eval_work.data_ptr()), self._eval_work.numel(), self._stream()), fn)
+                                          *work, self._stream()), fn)
         return result_cls(moves, length, agent, rows, self._prob.decode_rows(rows))
 
     # ---- SokobanProblem.get_stats(map)["solution"] on any level (pcgrl_get_solution)
@@ -890,34 +893,17 @@ class BatchedPcgrlEnv:
             raise NotImplementedError("paths(): the paths of binary and zelda only, not problem %r (%s)" % (name, {
                 "sokoban": "solve() returns sokoban's solution", "smb": "playthrough_smb() returns smb's play"}.get(name, "playthrough() returns its play")))
         torch = self._torch
-        if maps is None:
-            if self._handle is None or not self._was_reset or self._needs_reset:
-                raise RuntimeError("paths() without maps reads the environment's current levels: call reset() first")
-        self._scoring_handle()
-        if self._realloc:
-            raise NotImplementedError("paths(): an adjust_param() that this handle could not take in place waits for the next reset(); "
-                                      "the handle still scores with the old parameters")
-        w, h = self._alloc_dims
-        m = self._bufs["map"] if maps is None else self._as_maps("paths", maps)
-        M = int(m.shape[0])
-        max_len = h * w if max_len is None else int(max_len)
-        if max_len < 1:
-            raise ValueError("paths(): max_len must be at least 1, got %d" % max_len)
-        cfg = self._config(self._alloc_dims)
-        need = int(self._lib.pcgrl_get_paths_bytes(C.byref(cfg), M, max_len))
-        if not need:
-            raise NotImplementedError("paths(): no one-call form for this configuration (maps of %d rows x %d columns): "
-                                      "the row-bitboard kernels take maps up to 64 x 64" % (h, w))
+        m, M, max_len, work = self._readout("paths", "scores", "pcgrl_get_paths_bytes", lambda w, h: (
+            "paths(): no one-call form for this configuration (maps of %d rows x %d columns): "
+            "the row-bitboard kernels take maps up to 64 x 64" % (h, w)), maps, max_len, lambda w, h: h * w)
         legs = self.PATH_LEGS[name]
         cells = torch.empty((M, len(legs), max_len), dtype=torch.int16, device=self.device)
         length = torch.empty((M, len(legs)), dtype=torch.int32, device=self.device)
         rows = torch.empty((M, 8), dtype=torch.int32, device=self.device)
-        if self._eval_work is None or self._eval_work.numel() < need:
-            self._eval_work = torch.empty((need,), dtype=torch.uint8, device=self.device)
         _lib.check(self._lib.pcgrl_get_paths(self._handle, C.c_void_p(m.data_ptr()), M, max_len, C.c_void_p(cells.data_ptr()),
                                              C.c_void_p(length.data_ptr()), C.c_void_p(rows.data_ptr()),
-                                             C.c_void_p(self._eval_work.data_ptr()), self._eval_work.numel(), self._stream()), "pcgrl_get_paths")
-        return Paths(cells, length, rows, self._prob.decode_rows(rows), legs, w)
+                                             *work, self._stream()), "pcgrl_get_paths")
+        return Paths(cells, length, rows, self._prob.decode_rows(rows), legs, self._alloc_dims[0])
 
     def _evaluate_by_set_maps(self, m, rows, chunk):
         """evaluate() where pcgrl_get_stats_bytes is 0: a scratch environment of this problem (wide representation, the same

@@ -7,29 +7,11 @@ import numpy as np
 import pytest
 
 import oracle_lib as ol
+import readout_harness as rh
+from readout_harness import N_ENVS, make_env as _make, torch as _torch
 
 pytestmark = pytest.mark.gpu
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-N_ENVS = 3
-
-
-def _torch():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return torch
-
-
-def _make(prob, h, w, power=None, rep="wide", tuning=None, seed=1000, auto_reset=True):
-    from gym_pcgrl_amd.envs import BatchedPcgrlEnv
-    env = BatchedPcgrlEnv(prob=prob, rep=rep, num_envs=N_ENVS, seed=seed, auto_reset=auto_reset, tuning=tuning)
-    kw = dict(width=w, height=h)
-    if power is not None and prob != "smb":
-        kw["solver_power"] = int(power)
-    env.adjust_param(**kw)
-    if power is not None and prob == "smb":      # smb_prob.py:40-53: solver_power is an attribute there, not an adjust_param key
-        env._prob._solver_power = int(power)
-        env.adjust_param()
-    return env
 
 
 def _fixture(name):
@@ -237,22 +219,10 @@ def test_evaluate_levels_convenience():
 # ------------------------------------------------------------------ a tile id beyond the last
 @pytest.mark.parametrize("name", ["binary_14x14", "mdungeon_5x5_p5000", "sokoban_5x5"])
 def test_bad_tile_is_clamped_and_reported(name):
-    torch = _torch()
     prob, maps, _, power = _fixture(name)
-    env = _make(prob, maps.shape[1], maps.shape[2], power)
-    nt = env.get_num_tiles()
-    bad, clamped = maps[:5].copy(), maps[:5].copy()
-    for i in range(5):
-        bad[i, i % maps.shape[1], (2 * i) % maps.shape[2]] = 200
-        clamped[i, i % maps.shape[1], (2 * i) % maps.shape[2]] = nt - 1
-    want = env.evaluate(clamped).rows.clone()
-    assert env.check_status() == 0
-    given = torch.as_tensor(bad).to(env.device)
-    got = env.evaluate(given).rows.clone()
-    assert torch.equal(got, want)
-    with pytest.raises(ValueError):
-        env.check_status()
-    assert np.array_equal(given.cpu().numpy(), bad) and (given == 200).sum().item() == 5     # the caller's tensor still holds 200
+    h, w = maps.shape[1:]
+    env = _make(prob, h, w, power)
+    rh.check_bad_tile(env, env.evaluate, ("rows",), maps[:5], [(i, i % h, (2 * i) % w) for i in range(5)])
     env.close()
 
 

@@ -7,29 +7,18 @@ import os
 import numpy as np
 import pytest
 
+import readout_harness as rh
+from readout_harness import N_ENVS, make_env as _make, torch as _torch
+
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 G = os.path.join(HERE, "golden")
-N_ENVS = 3
 PASSABLE = {"binary": [[0]], "zelda": [[0, 2, 3, 5, 6, 7], [0, 2, 3, 4, 5, 6, 7], [0, 2, 5, 6, 7]]}
 LEGS = {"binary": ("longest",), "zelda": ("key", "door", "enemy")}
 GROUPS = ["stats_binary_%s" % s for s in ("1x1", "1x9", "8x1", "3x7", "5x5", "14x14", "16x11", "9x32", "64x64")] + \
          ["stats_zelda_%s" % s for s in ("5x5", "7x11", "11x16", "16x11")] + \
          ["rand_binary_%s" % s for s in ("5x40", "16x33", "16x32", "17x9", "17x33")] + ["rand_zelda_%s" % s for s in ("5x40", "16x33", "17x9")] + \
          ["hand_binary_64x64", "hand_binary_3x7", "hand_zelda_7x11"]
-
-
-def _torch():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return torch
-
-
-def _make(prob, h, w, rep="wide", seed=1000, n=N_ENVS):
-    from gym_pcgrl_amd.envs import BatchedPcgrlEnv
-    env = BatchedPcgrlEnv(prob=prob, rep=rep, num_envs=n, seed=seed)
-    env.adjust_param(width=w, height=h)
-    return env
 
 
 _CACHE = {}
@@ -51,11 +40,7 @@ def _group(name):
 
 
 def _padded(want, max_len):
-    """The fixture's rows cut or -1 padded to max_len columns."""
-    out = np.full(want.shape[:2] + (max_len,), -1, np.int16)
-    k = min(max_len, want.shape[2])
-    out[:, :, :k] = want[:, :, :k]
-    return out
+    return rh.padded(want, max_len, np.int16)
 
 
 def _same(a, b):
@@ -142,25 +127,17 @@ def test_max_len_and_row_bounds(name):
         p = env.paths(m, max_len=max_len)
         assert np.array_equal(p.length.cpu().numpy(), wlen) and np.array_equal(p.cells.cpu().numpy(), _padded(want, max_len)), max_len
         assert np.array_equal(p.truncated.cpu().numpy(), wlen + 1 > max_len) and p.truncated.any().item() == (max_len < full + 1)
-        guard = 64
-        cl = torch.full((guard + M * legs * max_len + guard,), 0x5A5A, dtype=torch.int16, device=dev)
-        ln = torch.full((guard + M * legs + guard,), 0x5A5A5A5A, dtype=torch.int32, device=dev)
-        rw = torch.full((guard + M * 8 + guard,), 0x5A5A5A5A, dtype=torch.int32, device=dev)
+        cl, ln, rw = rh.Guarded(torch.int16, M * legs * max_len, dev), rh.Guarded(torch.int32, M * legs, dev), rh.Guarded(torch.int32, M * 8, dev)
         need = int(env._lib.pcgrl_get_paths_bytes(C.byref(cfg), M, max_len))
         assert need >= 256
         work = torch.empty((need,), dtype=torch.uint8, device=dev)
-        for rows_ptr in (C.c_void_p(rw.data_ptr() + 4 * guard), None):                  # (the second time no rows wanted)
-            rc = env._lib.pcgrl_get_paths(env._handle, C.c_void_p(m.data_ptr()), M, max_len, C.c_void_p(cl.data_ptr() + 2 * guard),
-                                          C.c_void_p(ln.data_ptr() + 4 * guard), rows_ptr, C.c_void_p(work.data_ptr()), need, env._stream())
-            assert rc == 0
-            torch.cuda.synchronize()
-            for t, fill in ((cl, 0x5A5A), (ln, 0x5A5A5A5A), (rw, 0x5A5A5A5A)):
-                assert (t[:guard] == fill).all().item() and (t[-guard:] == fill).all().item()
-            assert torch.equal(cl[guard:-guard].view(M, legs, max_len), p.cells) and torch.equal(ln[guard:-guard].view(M, legs), p.length)
-            assert torch.equal(rw[guard:-guard].view(M, 8), p.rows)
+        for rows_ptr in (rw.ptr, None):                  # (the second time no rows wanted)
+            rh.guarded_call((cl, ln, rw), lambda a, b, _: env._lib.pcgrl_get_paths(env._handle, rh.ptr(m), M, max_len, a, b, rows_ptr, rh.ptr(work), need, env._stream()))
+            assert torch.equal(cl.inner.view(M, legs, max_len), p.cells) and torch.equal(ln.inner.view(M, legs), p.length)
+            assert torch.equal(rw.inner.view(M, 8), p.rows)
         # refusals: a workspace one byte short, max_len 0, count 0, no cells
-        args = lambda **kw: (env._handle, C.c_void_p(m.data_ptr()), kw.get("count", M), kw.get("max_len", max_len), kw.get("cells", C.c_void_p(cl.data_ptr() + 2 * guard)),
-                             C.c_void_p(ln.data_ptr() + 4 * guard), None, C.c_void_p(work.data_ptr()), kw.get("need", need), env._stream())
+        args = lambda **kw: (env._handle, rh.ptr(m), kw.get("count", M), kw.get("max_len", max_len), kw.get("cells", cl.ptr),
+                             ln.ptr, None, rh.ptr(work), kw.get("need", need), env._stream())
         for kw in (dict(need=need - 1), dict(max_len=0), dict(count=0), dict(cells=None)):
             assert env._lib.pcgrl_get_paths(*args(**kw)) == -1, kw
     assert env.check_status() == 0
@@ -173,65 +150,31 @@ def test_handle_in_the_middle_of_its_episodes(prob, rep):
     torch = _torch()
     from gym_pcgrl_amd.envs import BatchedPcgrlEnv
     n = 24
-    env, twin = (BatchedPcgrlEnv(prob=prob, rep=rep, num_envs=n, seed=77) for _ in range(2))
-    with pytest.raises(RuntimeError):
-        env.paths()                                               # its own levels: only after a reset()
-    W, H, nt = env._prob._width, env._prob._height, env.get_num_tiles()
-    rs = np.random.RandomState(3)
-    if rep == "narrow":
-        acts = rs.randint(0, nt + 1, size=(40, n)).astype(np.int32)
-    else:
-        acts = np.stack([rs.randint(0, W, size=(40, n)), rs.randint(0, H, size=(40, n)), rs.randint(0, nt, size=(40, n))], -1).astype(np.int32)
-    for e in (env, twin):
-        e.reset()
-        for t in range(20):
-            e.step(acts[t])
-    before = env.state_dict()
-    names = [k for k in ("map", "old_map", "planes", "stats", "start_stats", "counters", "heatmap", "pos", "reward", "done", "rng_cursor", "rng_rep", "rng_prob", "info") if env._bufs.get(k) is not None]
-    bufs = {k: env._bufs[k].clone() for k in names}
-    own = env.paths()                                             # the handle's own map buffer, read in place
-    again = env.paths(env._bufs["map"].clone())
-    assert _same(own, again) and tuple(own.cells.shape) == (n, len(LEGS[prob]), H * W)
-    ns = 2 if prob == "binary" else 7
-    assert torch.equal(own.rows[:, :ns], env._bufs["stats"][:, :ns])
-    assert (own.length >= 0).any().item()
-    after = env.state_dict()
-    assert before.keys() == after.keys()
-    for k in before:
-        assert (before[k] is None and after[k] is None) or torch.equal(before[k], after[k]), k
-    for k, v in bufs.items():
-        assert torch.equal(env._bufs[k], v), k
-    for t in range(20, 40):                                       # the episodes go on as if nothing had happened
-        x, y = env.step(acts[t]), twin.step(acts[t])
-        if t % 5 == 0:
-            env.paths()
-        assert torch.equal(x[0]["map"], y[0]["map"]) and torch.equal(x[1], y[1]) and torch.equal(x[2], y[2]), t
-    for k in names:
-        assert torch.equal(env._bufs[k], twin._bufs[k]), k
-    assert env.check_status() == 0
-    for e in (env, twin):
-        e.close()
+
+    def sample(env):
+        W, H, nt = env._prob._width, env._prob._height, env.get_num_tiles()
+        rs = np.random.RandomState(3)
+        if rep == "narrow":
+            return rs.randint(0, nt + 1, size=(40, n)).astype(np.int32)
+        return np.stack([rs.randint(0, W, size=(40, n)), rs.randint(0, H, size=(40, n)), rs.randint(0, nt, size=(40, n))], -1).astype(np.int32)
+
+    def after_own(env, own):
+        assert tuple(own.cells.shape) == (n, len(LEGS[prob]), env._prob._height * env._prob._width)
+        ns = 2 if prob == "binary" else 7
+        assert torch.equal(own.rows[:, :ns], env._bufs["stats"][:, :ns])
+        assert (own.length >= 0).any().item()
+
+    names = ("map", "old_map", "planes", "stats", "start_stats", "counters", "heatmap", "pos", "reward", "done", "rng_cursor", "rng_rep", "rng_prob", "info")
+    rh.check_handle_left_alone(lambda: BatchedPcgrlEnv(prob=prob, rep=rep, num_envs=n, seed=77), sample, lambda env, *m: env.paths(*m), ("cells", "length", "rows"),
+                               lambda env: [k for k in names if env._bufs.get(k) is not None], after_own, twin_too=True)
 
 
 @pytest.mark.parametrize("name", ["stats_binary_5x5", "stats_zelda_7x11"])
 def test_bad_tile_is_clamped_and_reported(name):
-    torch = _torch()
     prob, maps, stats, want, wlen = _group(name)
     h, w = maps.shape[1:]
     env = _make(prob, h, w)
-    nt = env.get_num_tiles()
-    bad, clamped = maps[:40].copy(), maps[:40].copy()
-    for i in range(5):
-        bad[i, i % h, (2 * i) % w] = 200
-        clamped[i, i % h, (2 * i) % w] = nt - 1
-    ref = env.paths(clamped)
-    assert env.check_status() == 0
-    given = torch.as_tensor(bad).to(env.device)
-    got = env.paths(given)
-    assert _same(got, ref)
-    with pytest.raises(ValueError):
-        env.check_status()
-    assert np.array_equal(given.cpu().numpy(), bad) and (given == 200).sum().item() == 5     # the caller's tensor still holds 200
+    rh.check_bad_tile(env, env.paths, ("cells", "length", "rows"), maps[:40], [(i, i % h, (2 * i) % w) for i in range(5)])
     env.close()
 
 

@@ -8,6 +8,9 @@ import re
 import numpy as np
 import pytest
 
+import readout_harness as rh
+from readout_harness import N_ENVS, make_env as _make, padded as _padded, torch as _torch
+
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 G = os.path.join(HERE, "golden")
@@ -16,28 +19,11 @@ FILES = {
     "ddave": ["1x5_p5000", "2x6_p5000", "5x5_p5000", "6x9_p150", "7x11_p600", "7x11_p5000", "11x7_p5000", "14x14_p5000"],
 }
 CASES = [(p, f) for p in ("mdungeon", "ddave") for f in FILES[p]]
-N_ENVS = 3
 NHAND = 3
 CSRC = os.path.join(os.path.dirname(HERE), "gym_pcgrl_amd", "csrc")
 SMALL_POPS = int(re.search(r"#define SS_SMALL_POPS (\d+)", open(os.path.join(CSRC, "kernels_step_solver.h")).read()).group(1))
 # columns of a decoded statistics row (the stats fixtures' keys): dist-win, sol-length, and what the replays count
 DIST, SOLLEN = 9, 10
-
-
-def _torch():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return torch
-
-
-def _make(prob, h, w, power=None, tuning=None, rep="wide", seed=1000, num_envs=N_ENVS):
-    from gym_pcgrl_amd.envs import BatchedPcgrlEnv
-    env = BatchedPcgrlEnv(prob=prob, rep=rep, num_envs=num_envs, seed=seed, tuning=tuning)
-    kw = dict(width=w, height=h)
-    if power is not None:
-        kw["solver_power"] = int(power)
-    env.adjust_param(**kw)
-    return env
 
 
 _CACHE = {}
@@ -50,13 +36,6 @@ def _fixture(prob, name):
         s = np.load(os.path.join(G, "playthroughs.npz"))
         _CACHE[prob, name] = (d["maps"], d["stats"], d["agents"], int(d["solver_power"]), s["moves_%s_%s" % (prob, name)], s["length_%s_%s" % (prob, name)])
     return _CACHE[prob, name]
-
-
-def _padded(want, max_len):
-    out = np.full((want.shape[0], max_len), -1, np.int8)
-    k = min(max_len, want.shape[1])
-    out[:, :k] = want[:, :k]
-    return out
 
 
 def _check(env, maps, stats, agents, want, wlen, max_len=None):
@@ -221,42 +200,21 @@ def test_replayed_without_a_fixture(prob):
 # ------------------------------------------------------------------ the handle is left alone
 @pytest.mark.parametrize("prob", ["mdungeon", "ddave"])
 def test_handle_in_the_middle_of_its_episodes(prob):
-    torch = _torch()
     from gym_pcgrl_amd.envs import BatchedPcgrlEnv
     maps, stats, agents, power, want, wlen = _fixture(prob, "7x11_p5000")
-    env, twin = (BatchedPcgrlEnv(prob=prob, rep="narrow", num_envs=N_ENVS, seed=77) for _ in range(2))
-    nt = env.get_num_tiles()
-    acts = np.random.RandomState(3).randint(0, nt + 1, size=(40, N_ENVS)).astype(np.int32)
-    with pytest.raises(RuntimeError):
-        env.playthrough()                                         # its own levels: only after a reset()
-    for e in (env, twin):
-        e.adjust_param(width=11, height=7)
-        e.reset()
-        for t in range(20):
-            e.step(acts[t])
-    before = env.state_dict()
-    bufs = {k: v.clone() for k, v in env._bufs.items() if v is not None}      # every device buffer of the handle, scratch included
-    own = env.playthrough()                                       # the handle's own map buffer, read in place
-    again = env.playthrough(env._bufs["map"].clone())
-    for a, b in ((own.moves, again.moves), (own.length, again.length), (own.agent, again.agent), (own.rows, again.rows)):
-        assert torch.equal(a, b)
-    assert own.moves.shape == (N_ENVS, 255)
-    _check(env, maps[:40], stats[:40], agents[:40], want[:40], wlen[:40])       # ... and other levels in between
-    torch.cuda.synchronize()
-    for k, v in bufs.items():
-        assert torch.equal(env._bufs[k], v), k
-    after = env.state_dict()
-    assert before.keys() == after.keys()
-    for k in before:
-        assert (before[k] is None and after[k] is None) or torch.equal(before[k], after[k]), k
-    for t in range(20, 40):                                       # the episodes go on as if nothing had happened
-        x, y = env.step(acts[t]), twin.step(acts[t])
-        if t % 5 == 0:
-            env.playthrough()
-        assert torch.equal(x[0]["map"], y[0]["map"]) and torch.equal(x[1], y[1]) and torch.equal(x[2], y[2]), t
-    assert env.check_status() == 0
-    for e in (env, twin):
-        e.close()
+
+    def make():
+        env = BatchedPcgrlEnv(prob=prob, rep="narrow", num_envs=N_ENVS, seed=77)
+        env.adjust_param(width=11, height=7)
+        return env
+
+    def after_own(env, own):
+        assert own.moves.shape == (N_ENVS, 255)
+
+    rh.check_handle_left_alone(make, lambda env: np.random.RandomState(3).randint(0, env.get_num_tiles() + 1, size=(40, N_ENVS)).astype(np.int32),
+                               lambda env, *m: env.playthrough(*m), ("moves", "length", "agent", "rows"),
+                               lambda env: [k for k, v in env._bufs.items() if v is not None],      # every device buffer of the handle, scratch included
+                               after_own, lambda env: _check(env, maps[:40], stats[:40], agents[:40], want[:40], wlen[:40]))
 
 
 @pytest.mark.parametrize("prob", ["mdungeon", "ddave"])
@@ -308,61 +266,39 @@ def test_raw_abi_row_bounds_and_refusals(max_len):
     env = _make("mdungeon", 11, 7, power)
     pt = _check(env, maps, stats, agents, want, wlen, max_len=max_len)
     assert pt.truncated.any().item() == (max_len < 56)
-    M, guard = maps.shape[0], 64
-    dev = env.device
-    mv = torch.full((guard + M * max_len + guard,), 0x5A, dtype=torch.int8, device=dev)
-    ln = torch.full((guard + M + guard,), 0x5A5A5A5A, dtype=torch.int32, device=dev)
-    ag = torch.full((guard + M + guard,), 0x5A, dtype=torch.int8, device=dev)
-    rw = torch.full((guard + M * 8 + guard,), 0x5A5A5A5A, dtype=torch.int32, device=dev)
+    M, dev, lib = maps.shape[0], env.device, env._lib
+    outs = lambda: (rh.Guarded(torch.int8, M * max_len, dev), rh.Guarded(torch.int32, M, dev), rh.Guarded(torch.int8, M, dev), rh.Guarded(torch.int32, M * 8, dev))
+    mv, ln, ag, rw = outs()
     m = torch.as_tensor(np.ascontiguousarray(maps)).to(dev)
     cfg = env._config()
-    lib = env._lib
     need = int(lib.pcgrl_get_playthrough_bytes(C.byref(cfg), M, max_len))
     assert need >= 256
     work = torch.empty((need + 256,), dtype=torch.uint8, device=dev)
     assert work.data_ptr() % 256 == 0
-    p = lambda t, off=0: C.c_void_p(t.data_ptr() + off)
-    assert lib.pcgrl_get_playthrough(env._handle, p(m), M, max_len, p(mv, guard), p(ln, 4 * guard), p(ag, guard), p(rw, 4 * guard), p(work), need, env._stream()) == 0
-    torch.cuda.synchronize()
-    for t, fill in ((mv, 0x5A), (ln, 0x5A5A5A5A), (ag, 0x5A), (rw, 0x5A5A5A5A)):
-        assert (t[:guard] == fill).all().item() and (t[-guard:] == fill).all().item()
-    assert torch.equal(mv[guard:-guard].view(M, max_len), pt.moves) and torch.equal(ln[guard:-guard], pt.length) and torch.equal(ag[guard:-guard], pt.agent)
-    assert torch.equal(rw[guard:-guard].view(M, 8), pt.rows)
+    p = rh.ptr
+    rh.guarded_call((mv, ln, ag, rw), lambda a, b, c, d: lib.pcgrl_get_playthrough(env._handle, p(m), M, max_len, a, b, c, d, p(work), need, env._stream()))
+    assert torch.equal(mv.inner.view(M, max_len), pt.moves) and torch.equal(ln.inner, pt.length) and torch.equal(ag.inner, pt.agent)
+    assert torch.equal(rw.inner.view(M, 8), pt.rows)
     # the optional outputs NULL: moves and lengths are the same
-    mv2, ln2 = torch.full_like(mv, 0x5A), torch.full_like(ln, 0x5A5A5A5A)
-    assert lib.pcgrl_get_playthrough(env._handle, p(m), M, max_len, p(mv2, guard), p(ln2, 4 * guard), None, None, p(work), need, env._stream()) == 0
-    torch.cuda.synchronize()
-    assert torch.equal(mv2, mv) and torch.equal(ln2, ln)
+    mv2, ln2 = outs()[:2]
+    rh.guarded_call((mv2, ln2), lambda a, b: lib.pcgrl_get_playthrough(env._handle, p(m), M, max_len, a, b, None, None, p(work), need, env._stream()))
+    assert torch.equal(mv2.full, mv.full) and torch.equal(ln2.full, ln.full)
     # refusals: a workspace one byte short, a misaligned one, max_len 0, count 0
-    args = (p(mv2, guard), p(ln2, 4 * guard), None, None)
+    args = (mv2.ptr, ln2.ptr, None, None)
     assert lib.pcgrl_get_playthrough(env._handle, p(m), M, max_len, *args, p(work), need - 1, env._stream()) == -1
     assert lib.pcgrl_get_playthrough(env._handle, p(m), M, max_len, *args, p(work, 128), need, env._stream()) == -1
     assert lib.pcgrl_get_playthrough(env._handle, p(m), M, 0, *args, p(work), need, env._stream()) == -1
     assert lib.pcgrl_get_playthrough(env._handle, p(m), 0, max_len, *args, p(work), need, env._stream()) == -1
     torch.cuda.synchronize()
-    assert torch.equal(mv2, mv) and torch.equal(ln2, ln)               # a refused call writes nothing
+    assert torch.equal(mv2.full, mv.full) and torch.equal(ln2.full, ln.full)               # a refused call writes nothing
     env.close()
 
 
 @pytest.mark.parametrize("prob", ["mdungeon", "ddave"])
 def test_bad_tile_is_clamped_and_reported(prob):
-    torch = _torch()
     maps, stats, agents, power, want, wlen = _fixture(prob, "5x5_p5000")
     env = _make(prob, 5, 5, power)
-    nt = env.get_num_tiles()
-    bad, clamped = maps[:40].copy(), maps[:40].copy()
-    for i in range(5):
-        bad[i, i % 5, (2 * i) % 5] = 200
-        clamped[i, i % 5, (2 * i) % 5] = nt - 1
-    ref = env.playthrough(clamped)
-    assert env.check_status() == 0
-    given = torch.as_tensor(bad).to(env.device)
-    got = env.playthrough(given)
-    for a, b in ((got.moves, ref.moves), (got.length, ref.length), (got.agent, ref.agent), (got.rows, ref.rows)):
-        assert torch.equal(a, b)
-    with pytest.raises(ValueError):
-        env.check_status()
-    assert np.array_equal(given.cpu().numpy(), bad) and (given == 200).sum().item() == 5     # the caller's tensor still holds 200
+    rh.check_bad_tile(env, env.playthrough, ("moves", "length", "agent", "rows"), maps[:40], [(i, i % 5, (2 * i) % 5) for i in range(5)])
     env.close()
 
 

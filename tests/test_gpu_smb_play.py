@@ -9,27 +9,19 @@ import os
 import numpy as np
 import pytest
 
+import readout_harness as rh
+from readout_harness import N_ENVS, make_env, padded as _padded, torch as _torch
+
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 G = os.path.join(HERE, "golden")
 FILES = ["4x9_p200", "6x12_p10000", "8x24_p400", "10x30_p10000", "14x40_p2500", "14x114_p1500", "14x114_p10000"]
 EDGES = ["edge_w123", "edge_w250", "edge_h3", "edge_p16383", "edge_q4095"]
-N_ENVS = 3
 JUMPS, JDIST, DIST = 5, 6, 7
 
 
-def _torch():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return torch
-
-
-def _make(h, w, power, tuning=None, rep="wide", seed=1000, num_envs=N_ENVS):
-    from gym_pcgrl_amd.envs import BatchedPcgrlEnv
-    env = BatchedPcgrlEnv(prob="smb", rep=rep, num_envs=num_envs, seed=seed, tuning=tuning)
-    env._prob._solver_power = int(power)          # smb_prob.py:40-53: an attribute, not an adjust_param key
-    env.adjust_param(width=w, height=h)
-    return env
+def _make(h, w, power, tuning=None):
+    return make_env("smb", h, w, power, tuning=tuning)
 
 
 _CACHE = {}
@@ -46,13 +38,6 @@ def _fixture(name):
             d = np.load(os.path.join(G, "stats_smb_%s.npz" % name))
             _CACHE[name] = (d["maps"], d["stats"], d["agents"], int(d["solver_power"]), s["moves_" + name], s["length_" + name])
     return _CACHE[name]
-
-
-def _padded(want, max_len):
-    out = np.full((want.shape[0], max_len), -1, np.int8)
-    k = min(max_len, want.shape[1])
-    out[:, :k] = want[:, :k]
-    return out
 
 
 def _check(env, maps, stats, agents, want, wlen, max_len=None):
@@ -138,43 +123,36 @@ def test_short_rows_are_prefixes_and_nothing_is_written_behind_them(name):
     longest = int(wlen.max())
     assert longest == want.shape[1] > 6
     env = _make(maps.shape[1], maps.shape[2], power)
-    M, guard = maps.shape[0], 64
-    dev = env.device
+    M, dev = maps.shape[0], env.device
     m = torch.as_tensor(np.ascontiguousarray(maps)).to(dev)
     cfg, lib = env._config(), env._lib
-    p = lambda t, off=0: C.c_void_p(t.data_ptr() + off)
+    p = rh.ptr
     for max_len in (1, 5, longest - 1):
         pt = _check(env, maps, stats, agents, want, wlen, max_len=max_len)
         assert pt.truncated.any().item() and np.array_equal(pt.truncated.cpu().numpy(), wlen > max_len)
-        mv = torch.full((guard + M * max_len + guard,), 0x5A, dtype=torch.int8, device=dev)
-        ln = torch.full((guard + M + guard,), 0x5A5A5A5A, dtype=torch.int32, device=dev)
-        ag = torch.full((guard + M + guard,), 0x5A, dtype=torch.int8, device=dev)
-        rw = torch.full((guard + M * 8 + guard,), 0x5A5A5A5A, dtype=torch.int32, device=dev)
+        outs = lambda: (rh.Guarded(torch.int8, M * max_len, dev), rh.Guarded(torch.int32, M, dev), rh.Guarded(torch.int8, M, dev), rh.Guarded(torch.int32, M * 8, dev))
+        mv, ln, ag, rw = outs()
         need = int(lib.pcgrl_get_smb_play_bytes(C.byref(cfg), M, max_len))
         assert need >= 256
         work = torch.empty((need + 256,), dtype=torch.uint8, device=dev)
         assert work.data_ptr() % 256 == 0
-        assert lib.pcgrl_get_smb_play(env._handle, p(m), M, max_len, p(mv, guard), p(ln, 4 * guard), p(ag, guard), p(rw, 4 * guard), p(work), need, env._stream()) == 0
-        torch.cuda.synchronize()
-        for t, fill in ((mv, 0x5A), (ln, 0x5A5A5A5A), (ag, 0x5A), (rw, 0x5A5A5A5A)):
-            assert (t[:guard] == fill).all().item() and (t[-guard:] == fill).all().item()
-        assert torch.equal(mv[guard:-guard].view(M, max_len), pt.moves) and torch.equal(ln[guard:-guard], pt.length) and torch.equal(ag[guard:-guard], pt.agent)
-        assert torch.equal(rw[guard:-guard].view(M, 8), pt.rows)
+        rh.guarded_call((mv, ln, ag, rw), lambda a, b, c, d: lib.pcgrl_get_smb_play(env._handle, p(m), M, max_len, a, b, c, d, p(work), need, env._stream()))
+        assert torch.equal(mv.inner.view(M, max_len), pt.moves) and torch.equal(ln.inner, pt.length) and torch.equal(ag.inner, pt.agent)
+        assert torch.equal(rw.inner.view(M, 8), pt.rows)
         if max_len == 5:
             # the optional outputs NULL: moves and lengths are the same; refusals write nothing
-            mv2, ln2 = torch.full_like(mv, 0x5A), torch.full_like(ln, 0x5A5A5A5A)
-            assert lib.pcgrl_get_smb_play(env._handle, p(m), M, max_len, p(mv2, guard), p(ln2, 4 * guard), None, None, p(work), need, env._stream()) == 0
-            torch.cuda.synchronize()
-            assert torch.equal(mv2, mv) and torch.equal(ln2, ln)
-            args = (p(mv2, guard), p(ln2, 4 * guard), None, None)
+            mv2, ln2 = outs()[:2]
+            rh.guarded_call((mv2, ln2), lambda a, b: lib.pcgrl_get_smb_play(env._handle, p(m), M, max_len, a, b, None, None, p(work), need, env._stream()))
+            assert torch.equal(mv2.full, mv.full) and torch.equal(ln2.full, ln.full)
+            args = (mv2.ptr, ln2.ptr, None, None)
             assert lib.pcgrl_get_smb_play(env._handle, p(m), M, max_len, *args, p(work), need - 1, env._stream()) == -1
             assert lib.pcgrl_get_smb_play(env._handle, p(m), M, max_len, *args, p(work, 128), need, env._stream()) == -1
             assert lib.pcgrl_get_smb_play(env._handle, p(m), M, 0, *args, p(work), need, env._stream()) == -1
             assert lib.pcgrl_get_smb_play(env._handle, p(m), 0, max_len, *args, p(work), need, env._stream()) == -1
             assert lib.pcgrl_get_smb_play(env._handle, None, M, max_len, *args, p(work), need, env._stream()) == -1
-            assert lib.pcgrl_get_smb_play(env._handle, p(m), M, max_len, None, p(ln2, 4 * guard), None, None, p(work), need, env._stream()) == -1
+            assert lib.pcgrl_get_smb_play(env._handle, p(m), M, max_len, None, ln2.ptr, None, None, p(work), need, env._stream()) == -1
             torch.cuda.synchronize()
-            assert torch.equal(mv2, mv) and torch.equal(ln2, ln)
+            assert torch.equal(mv2.full, mv.full) and torch.equal(ln2.full, ln.full)
     env.close()
 
 
@@ -245,23 +223,11 @@ def test_bad_tile_is_clamped_and_reported():
     torch = _torch()
     maps, stats, agents, power, want, wlen = _fixture("8x24_p400")
     env = _make(8, 24, power)
-    nt = env.get_num_tiles()
-    assert nt == 7
-    bad, clamped = maps[:40].copy(), maps[:40].copy()
-    for i in range(6):
-        y, x = (5 + i) % 8, (3 * i + 2) % 24                    # floor and sky cells in the player's way: a tube there changes plays
-        bad[i, y, x] = 7 if i == 0 else 200
-        clamped[i, y, x] = nt - 1
-    ref = env.playthrough_smb(clamped)
-    assert env.check_status() == 0
-    given = torch.as_tensor(bad).to(env.device)
-    got = env.playthrough_smb(given)
-    for a, b in ((got.moves, ref.moves), (got.length, ref.length), (got.agent, ref.agent), (got.rows, ref.rows)):
-        assert torch.equal(a, b)
+    assert env.get_num_tiles() == 7
+    # floor and sky cells in the player's way: a tube there changes plays
+    ref, clamped = rh.check_bad_tile(env, env.playthrough_smb, ("moves", "length", "agent", "rows"), maps[:40],
+                                     [(i, (5 + i) % 8, (3 * i + 2) % 24) for i in range(6)], [7] + [200] * 5)
     assert torch.equal(ref.rows, env.evaluate(clamped).rows)
-    with pytest.raises(ValueError):
-        env.check_status()
-    assert np.array_equal(given.cpu().numpy(), bad) and (given >= 7).sum().item() == 6        # the caller's tensor still holds them
     env.close()
 
 

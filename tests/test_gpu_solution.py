@@ -8,30 +8,16 @@ import re
 import numpy as np
 import pytest
 
+import readout_harness as rh
+from readout_harness import N_ENVS, make_env, padded as _padded, torch as _torch
+
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 G = os.path.join(HERE, "golden")
 SIZES = ["4x6", "5x5", "5x6", "6x6", "7x7", "7x8", "8x8"]
-N_ENVS = 3
 CSRC = os.path.join(os.path.dirname(HERE), "gym_pcgrl_amd", "csrc")
 # what a small-region try may pop per agent
 SMALL_POPS = int(re.search(r"#define SS_SMALL_POPS (\d+)", open(os.path.join(CSRC, "kernels_step_solver.h")).read()).group(1))
-
-
-def _torch():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return torch
-
-
-def _make(h, w, power=None, tuning=None, prob="sokoban", rep="wide", seed=1000):
-    from gym_pcgrl_amd.envs import BatchedPcgrlEnv
-    env = BatchedPcgrlEnv(prob=prob, rep=rep, num_envs=N_ENVS, seed=seed, tuning=tuning)
-    kw = dict(width=w, height=h)
-    if power is not None:
-        kw["solver_power"] = int(power)
-    env.adjust_param(**kw)
-    return env
 
 
 _CACHE = {}
@@ -44,14 +30,6 @@ def _fixture(size):
         s = np.load(os.path.join(G, "solutions_sokoban.npz"))
         _CACHE[size] = (d["maps"], d["stats"], d["agents"], int(d["solver_power"]), s["moves_" + size])
     return _CACHE[size]
-
-
-def _padded(want, max_len):
-    """The fixture's rows cut or -1 padded to max_len columns."""
-    out = np.full((want.shape[0], max_len), -1, np.int8)
-    k = min(max_len, want.shape[1])
-    out[:, :k] = want[:, :k]
-    return out
 
 
 def _check(env, maps, stats, agents, want, max_len=None, sol=None):
@@ -95,7 +73,7 @@ def test_fixture_solutions(size, tuning):
     torch = _torch()
     maps, stats, agents, power, want = _fixture(size)
     assert maps.shape[0] != N_ENVS and maps.shape[0] <= 412
-    env = _make(maps.shape[1], maps.shape[2], power, tuning=tuning)
+    env = make_env("sokoban", maps.shape[1], maps.shape[2], power, tuning=tuning)
     sol = _check(env, maps, stats, agents, want, max_len=want.shape[1])
     assert torch.equal(sol.rows, env.evaluate(maps).rows)
     assert _replay_all(maps, sol.moves.cpu().numpy(), sol.length.cpu().numpy()) == int((stats[:, 5] > 0).sum()) > 0
@@ -112,7 +90,7 @@ def test_hand_made_levels_reach_the_generic_search():
         assert int((m == 3).sum()) > maxc                           # more crates than the compact search takes
         st, ag, want = s["hand_stats"][i:i + 1], s["hand_agents"][i:i + 1], s["hand_moves"][i:i + 1]
         assert st[0, 5] > 0 and ag[0, 4] >= 2                        # solved, by a later agent
-        env = _make(m.shape[0], m.shape[1], power)
+        env = make_env("sokoban", m.shape[0], m.shape[1], power)
         sol = _check(env, m[None], st, ag, want, max_len=want.shape[1])
         assert _replay_all(m[None], sol.moves.cpu().numpy(), sol.length.cpu().numpy()) == 1
         env.close()
@@ -128,7 +106,7 @@ def test_full_region_redo():
         pick = np.nonzero((agents[:, :4].max(1) > SMALL_POPS) & (agents[:, 4] > -2))[0]
         if pick.size == 0:
             continue
-        env = _make(maps.shape[1], maps.shape[2], power)
+        env = make_env("sokoban", maps.shape[1], maps.shape[2], power)
         sol = _check(env, maps[pick], stats[pick], agents[pick], want[pick], max_len=want.shape[1])
         solved += _replay_all(maps[pick], sol.moves.cpu().numpy(), sol.length.cpu().numpy())
         total += pick.size
@@ -147,7 +125,7 @@ def test_chunk_and_ticket_edges(count):
     pick = order[:count]
     if count > 1:
         assert (agents[pick, 4] == -2).any() and (agents[pick, 4] == -1).any() and (agents[pick, 4] >= 0).any()
-    env = _make(5, 5, power)
+    env = make_env("sokoban", 5, 5, power)
     sol = _check(env, maps[pick], stats[pick], agents[pick], want[pick])
     assert sol.moves.shape[1] == 255                                                    # the default: min(solver_power, 255)
     assert (stats[pick, 5] > 0).any()
@@ -161,69 +139,37 @@ def test_max_len_and_row_bounds(max_len):
     torch = _torch()
     maps, stats, agents, power, want = _fixture("7x8")
     assert int(stats[:, 5].max()) == 72
-    env = _make(7, 8, power)
+    env = make_env("sokoban", 7, 8, power)
     sol = _check(env, maps, stats, agents, want, max_len=max_len)
     assert sol.truncated.any().item() == (max_len < 72)
-    M, guard = maps.shape[0], 64
-    dev = env.device
-    mv = torch.full((guard + M * max_len + guard,), 0x5A, dtype=torch.int8, device=dev)
-    ln = torch.full((guard + M + guard,), 0x5A5A5A5A, dtype=torch.int32, device=dev)
-    ag = torch.full((guard + M + guard,), 0x5A, dtype=torch.int8, device=dev)
+    M, dev, lib = maps.shape[0], env.device, env._lib
+    mv, ln, ag = rh.Guarded(torch.int8, M * max_len, dev), rh.Guarded(torch.int32, M, dev), rh.Guarded(torch.int8, M, dev)
     m = torch.as_tensor(np.ascontiguousarray(maps)).to(dev)
     cfg = env._config()
-    need = int(env._lib.pcgrl_get_solution_bytes(C.byref(cfg), M, max_len))
+    need = int(lib.pcgrl_get_solution_bytes(C.byref(cfg), M, max_len))
     assert need >= 256
     work = torch.empty((need,), dtype=torch.uint8, device=dev)
-    rc = env._lib.pcgrl_get_solution(env._handle, C.c_void_p(m.data_ptr()), M, max_len, C.c_void_p(mv.data_ptr() + guard), C.c_void_p(ln.data_ptr() + 4 * guard),
-                                     C.c_void_p(ag.data_ptr() + guard), None, C.c_void_p(work.data_ptr()), need, env._stream())      # (no rows wanted)
-    assert rc == 0
-    torch.cuda.synchronize()
-    for t, fill in ((mv, 0x5A), (ln, 0x5A5A5A5A), (ag, 0x5A)):
-        assert (t[:guard] == fill).all().item() and (t[-guard:] == fill).all().item()
-    assert torch.equal(mv[guard:-guard].view(M, max_len), sol.moves) and torch.equal(ln[guard:-guard], sol.length) and torch.equal(ag[guard:-guard], sol.agent)
+    rh.guarded_call((mv, ln, ag), lambda a, b, c: lib.pcgrl_get_solution(env._handle, rh.ptr(m), M, max_len, a, b, c, None, rh.ptr(work), need, env._stream()))      # (no rows wanted)
+    assert torch.equal(mv.inner.view(M, max_len), sol.moves) and torch.equal(ln.inner, sol.length) and torch.equal(ag.inner, sol.agent)
     # refusals: a workspace one byte short, max_len 0
-    assert env._lib.pcgrl_get_solution(env._handle, C.c_void_p(m.data_ptr()), M, max_len, C.c_void_p(mv.data_ptr() + guard), C.c_void_p(ln.data_ptr() + 4 * guard),
-                                       None, None, C.c_void_p(work.data_ptr()), need - 1, env._stream()) == -1
-    assert env._lib.pcgrl_get_solution(env._handle, C.c_void_p(m.data_ptr()), M, 0, C.c_void_p(mv.data_ptr() + guard), C.c_void_p(ln.data_ptr() + 4 * guard),
-                                       None, None, C.c_void_p(work.data_ptr()), need, env._stream()) == -1
+    assert lib.pcgrl_get_solution(env._handle, rh.ptr(m), M, max_len, mv.ptr, ln.ptr, None, None, rh.ptr(work), need - 1, env._stream()) == -1
+    assert lib.pcgrl_get_solution(env._handle, rh.ptr(m), M, 0, mv.ptr, ln.ptr, None, None, rh.ptr(work), need, env._stream()) == -1
     env.close()
 
 
 # ------------------------------------------------------------------ the handle is left alone
 def test_handle_in_the_middle_of_its_episodes():
-    torch = _torch()
     from gym_pcgrl_amd.envs import BatchedPcgrlEnv
     maps, stats, agents, power, want = _fixture("5x5")
-    acts = np.random.RandomState(3).randint(0, 6, size=(40, N_ENVS)).astype(np.int32)
-    env, twin = (BatchedPcgrlEnv(prob="sokoban", rep="narrow", num_envs=N_ENVS, seed=77) for _ in range(2))
-    with pytest.raises(RuntimeError):
-        env.solve()                                               # its own levels: only after a reset()
-    for e in (env, twin):
-        e.reset()
-        for t in range(20):
-            e.step(acts[t])
-    before = env.state_dict()
-    bufs = {k: env._bufs[k].clone() for k in ("map", "stats", "start_stats", "counters", "heatmap", "pos")}
-    own = env.solve()                                             # the handle's own map buffer, read in place
-    again = env.solve(env._bufs["map"].clone())
-    for a, b in ((own.moves, again.moves), (own.length, again.length), (own.agent, again.agent), (own.rows, again.rows)):
-        assert torch.equal(a, b)
-    assert own.moves.shape == (N_ENVS, 255)
-    _check(env, maps[:9], stats[:9], agents[:9], want[:9])       # ... and other levels in between
-    after = env.state_dict()
-    assert before.keys() == after.keys()
-    for k in before:
-        assert (before[k] is None and after[k] is None) or torch.equal(before[k], after[k]), k
-    for k, v in bufs.items():
-        assert torch.equal(env._bufs[k], v), k
-    for t in range(20, 40):                                       # the episodes go on as if nothing had happened
-        x, y = env.step(acts[t]), twin.step(acts[t])
-        if t % 5 == 0:
-            env.solve()
-        assert torch.equal(x[0]["map"], y[0]["map"]) and torch.equal(x[1], y[1]) and torch.equal(x[2], y[2]), t
-    assert env.check_status() == 0
-    for e in (env, twin):
-        e.close()
+
+    def after_own(env, own):
+        assert own.moves.shape == (N_ENVS, 255)
+
+    rh.check_handle_left_alone(lambda: BatchedPcgrlEnv(prob="sokoban", rep="narrow", num_envs=N_ENVS, seed=77),
+                               lambda env: np.random.RandomState(3).randint(0, 6, size=(40, N_ENVS)).astype(np.int32),
+                               lambda env, *m: env.solve(*m), ("moves", "length", "agent", "rows"),
+                               lambda env: ("map", "stats", "start_stats", "counters", "heatmap", "pos"), after_own,
+                               lambda env: _check(env, maps[:9], stats[:9], agents[:9], want[:9]))
 
 
 def test_solve_leaves_pending_searches_alone():
@@ -263,35 +209,21 @@ def test_solve_leaves_pending_searches_alone():
 
 
 def test_bad_tile_is_clamped_and_reported():
-    torch = _torch()
     maps, stats, agents, power, want = _fixture("5x5")
-    env = _make(5, 5, power)
-    nt = env.get_num_tiles()
-    bad, clamped = maps[:40].copy(), maps[:40].copy()
-    for i in range(5):
-        bad[i, i % 5, (2 * i) % 5] = 200
-        clamped[i, i % 5, (2 * i) % 5] = nt - 1
-    ref = env.solve(clamped)
-    assert env.check_status() == 0
-    given = torch.as_tensor(bad).to(env.device)
-    got = env.solve(given)
-    for a, b in ((got.moves, ref.moves), (got.length, ref.length), (got.agent, ref.agent), (got.rows, ref.rows)):
-        assert torch.equal(a, b)
-    with pytest.raises(ValueError):
-        env.check_status()
-    assert np.array_equal(given.cpu().numpy(), bad) and (given == 200).sum().item() == 5     # the caller's tensor still holds 200
+    env = make_env("sokoban", 5, 5, power)
+    rh.check_bad_tile(env, env.solve, ("moves", "length", "agent", "rows"), maps[:40], [(i, i % 5, (2 * i) % 5) for i in range(5)])
     env.close()
 
 
 def test_configurations_without_the_form():
     _torch()
     import gym_pcgrl_amd
-    for kw in (dict(h=5, w=5, prob="mdungeon"), dict(h=16, w=24, power=2500), dict(h=5, w=5, power=5001)):
-        env = _make(**kw)
+    for kw in (dict(prob="mdungeon", h=5, w=5), dict(prob="sokoban", h=16, w=24, power=2500), dict(prob="sokoban", h=5, w=5, power=5001)):
+        env = make_env(**kw)
         with pytest.raises(NotImplementedError):
             env.solve(np.zeros((2, kw["h"], kw["w"]), np.uint8))
         env.close()
-    env = _make(5, 5)
+    env = make_env("sokoban", 5, 5)
     with pytest.raises(ValueError):
         env.solve(np.zeros((2, 5, 6), np.uint8))
     with pytest.raises(ValueError):

@@ -5,27 +5,21 @@ oracle.  This covers the algorithm logic on CPU; the DPP/ballot backend itself i
 import ctypes as C
 import glob
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import oracle_lib as ol
+from hostsim_build import build_so
 from oracle_lib import _p
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 G = os.path.join(HERE, "golden")
-SRC = os.path.join(HERE, "hostsim", "sim_algos.cpp")
-SO = os.path.join(HERE, "hostsim", "libsim_algos.so")
-CSRC = os.path.join(os.path.dirname(HERE), "gym_pcgrl_amd", "csrc")
 
 
 @pytest.fixture(scope="module")
 def sim():
-    deps = [SRC] + glob.glob(os.path.join(CSRC, "*.h"))
-    if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", SO, SRC])
-    L = C.CDLL(SO)
+    L = build_so("sim_algos.cpp", ["-ffp-contract=off"])
     L.sim_stats.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.sim_range_reward.argtypes = [C.c_double] * 4
     L.sim_range_reward.restype = C.c_double

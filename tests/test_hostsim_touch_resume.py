@@ -4,20 +4,16 @@ them -- incremental, touch, resume on a give-up, the plain computation only for 
 step against the oracle, and the carried state (champion rows, the bound on the other components) checked by brute force inside the
 simulator after every step.  CPU only."""
 import ctypes as C
-import glob
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import oracle_lib as ol
+from hostsim_build import build_so
 from oracle_lib import _p
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "hostsim", "sim_touch_resume.cpp")
-SO = os.path.join(HERE, "hostsim", "libsim_touch_resume.so")
-CSRC = os.path.join(os.path.dirname(HERE), "gym_pcgrl_amd", "csrc")
 INVARIANT = {1: "the champion is not one whole component", 2: "the champion's double sweep is not the path",
              3: "no champion, but the path is not the tiny components'", 4: "ub2 is below another component's double-sweep value",
              5: "ub2 is unknown or above the path", 6: "the parent's route gives other statistics"}
@@ -25,10 +21,7 @@ INVARIANT = {1: "the champion is not one whole component", 2: "the champion's do
 
 @pytest.fixture(scope="module")
 def sim():
-    deps = [SRC, os.path.join(HERE, "hostsim", "sim_algos.cpp")] + glob.glob(os.path.join(CSRC, "*.h"))
-    if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", SO, SRC])
-    L = C.CDLL(SO)
+    L = build_so("sim_touch_resume.cpp", ["-ffp-contract=off"])
     L.sim_touch_resume.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     L.sim_touch_resume.restype = C.c_long
     L.sim_set_spurious.argtypes = [C.c_int]

@@ -3,7 +3,6 @@ gym_pcgrl_amd/csrc/path_trace.h on the CPU lane-group simulator (tests/hostsim/s
 run_dikjstra maps define (tests/golden/paths.npz), the host check check_path(), and the host side of pcgrl_get_paths_legs /
 pcgrl_get_paths_bytes / pcgrl_get_paths."""
 import ctypes as C
-import glob
 import os
 import re
 import subprocess
@@ -11,16 +10,12 @@ import subprocess
 import numpy as np
 import pytest
 
+from hostsim_build import build_sanitized, build_so
 from oracle_lib import _p
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 G = os.path.join(HERE, "golden")
-SRC = os.path.join(HERE, "hostsim", "sim_paths.cpp")
-SO = os.path.join(HERE, "hostsim", "libsim_paths.so")
-EXE = os.path.join(HERE, "hostsim", "sim_paths_san")
-CSRC = os.path.join(ROOT, "gym_pcgrl_amd", "csrc")
-DEPS = [SRC, os.path.join(HERE, "hostsim", "sim_algos.cpp")]
 PROB_ID = {"binary": 0, "zelda": 1}
 # what a leg may walk on (zelda_prob.py:98, :107, :109; binary_prob.py:84): tile ids
 PASSABLE = {"binary": [[0]], "zelda": [[0, 2, 3, 5, 6, 7], [0, 2, 3, 4, 5, 6, 7], [0, 2, 5, 6, 7]]}
@@ -44,10 +39,7 @@ def forms(h, w):
 
 @pytest.fixture(scope="module")
 def sim():
-    deps = DEPS + glob.glob(os.path.join(CSRC, "*.h"))
-    if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", SO, SRC])
-    L = C.CDLL(SO)
+    L = build_so("sim_paths.cpp")
     L.sim_paths.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     return L
 
@@ -151,11 +143,7 @@ def test_fixture_covers_what_the_issue_lists(fix):
 def test_sanitized_stand_alone_program():
     """sim_paths.cpp with its own main(), built with the address and undefined-behaviour sanitizers and run as a program: built-in
     levels through every leg on every (lane group, mask width) form, with guard words behind the rows."""
-    deps = DEPS + glob.glob(os.path.join(CSRC, "*.h"))
-    if not os.path.exists(EXE) or os.path.getmtime(EXE) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-DSIM_PATHS_MAIN",
-                               "-o", EXE, SRC])
-    r = subprocess.run([EXE], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=120)
+    r = subprocess.run([build_sanitized("sim_paths.cpp", "SIM_PATHS_MAIN")], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=120)
     assert r.returncode == 0 and r.stdout.strip().endswith("ok") and "runtime error" not in r.stdout, r.stdout[-2000:]
 
 

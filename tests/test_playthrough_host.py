@@ -2,7 +2,6 @@
 on the CPU (tests/hostsim/sim_playthrough.cpp) against the reference's agents' moves (tests/golden/playthroughs.npz), the host replays
 replay_mdungeon() / replay_ddave(), and the host side of pcgrl_get_playthrough_bytes / pcgrl_get_playthrough."""
 import ctypes as C
-import glob
 import os
 import re
 import subprocess
@@ -10,15 +9,12 @@ import subprocess
 import numpy as np
 import pytest
 
+from hostsim_build import build_sanitized, build_so
 from oracle_lib import _p
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 G = os.path.join(HERE, "golden")
-SRC = os.path.join(HERE, "hostsim", "sim_playthrough.cpp")
-SO = os.path.join(HERE, "hostsim", "libsim_playthrough.so")
-EXE = os.path.join(HERE, "hostsim", "sim_playthrough_san")
-CSRC = os.path.join(ROOT, "gym_pcgrl_amd", "csrc")
 FILES = {
     "mdungeon": ["1x6_p5000", "5x5_p5000", "6x9_p300", "7x11_p5000", "11x7_p1200", "11x7_p5000", "14x14_p5000"],
     "ddave": ["1x5_p5000", "2x6_p5000", "5x5_p5000", "6x9_p150", "7x11_p600", "7x11_p5000", "11x7_p5000", "14x14_p5000"],
@@ -32,10 +28,7 @@ RES_COLS = {"mdungeon": [9, 10, 6, 7, 8], "ddave": [9, 10, 7, 8]}
 
 @pytest.fixture(scope="module")
 def sim():
-    deps = [SRC] + glob.glob(os.path.join(CSRC, "*.h"))
-    if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", SO, SRC])
-    L = C.CDLL(SO)
+    L = build_so("sim_playthrough.cpp")
     L.sim_playthrough.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.sim_play_things.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int]
     return L
@@ -150,11 +143,7 @@ def test_truncated_rows_are_prefixes(sim, play):
 def test_sanitized_stand_alone_program():
     """sim_playthrough.cpp with its own main(), built with the address and undefined-behaviour sanitizers and run as a program: a
     handful of built-in levels through every traced search and walk-back."""
-    deps = [SRC] + glob.glob(os.path.join(CSRC, "*.h"))
-    if not os.path.exists(EXE) or os.path.getmtime(EXE) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-DSIM_PLAYTHROUGH_MAIN",
-                               "-o", EXE, SRC])
-    r = subprocess.run([EXE], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=120)
+    r = subprocess.run([build_sanitized("sim_playthrough.cpp", "SIM_PLAYTHROUGH_MAIN")], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=120)
     assert r.returncode == 0 and r.stdout.strip().endswith("ok") and "runtime error" not in r.stdout, r.stdout[-2000:]
 
 

@@ -2,32 +2,25 @@
 (tests/hostsim/sim_solution.cpp) against the reference's get_stats(map)["solution"] (tests/golden/solutions_sokoban.npz), the host side
 of pcgrl_get_solution_bytes / pcgrl_get_solution, and replay_sokoban()."""
 import ctypes as C
-import glob
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+from hostsim_build import build_so
 from oracle_lib import _p
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 G = os.path.join(HERE, "golden")
-SRC = os.path.join(HERE, "hostsim", "sim_solution.cpp")
-SO = os.path.join(HERE, "hostsim", "libsim_solution.so")
-CSRC = os.path.join(ROOT, "gym_pcgrl_amd", "csrc")
 SIZES = ["4x6", "5x5", "5x6", "6x6", "7x7", "7x8", "8x8"]
 NHAND = 4
 
 
 @pytest.fixture(scope="module")
 def sim():
-    deps = [SRC] + glob.glob(os.path.join(CSRC, "*.h"))
-    if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", SO, SRC])
-    L = C.CDLL(SO)
+    L = build_so("sim_solution.cpp")
     L.sim_sokoban_solution.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     return L
 

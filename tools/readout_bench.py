@@ -1,0 +1,295 @@
+#!/usr/bin/env python3
+"""Levels/s of the level read-outs of BatchedPcgrlEnv -- evaluate() (pcgrl_get_stats), solve() (pcgrl_get_solution), playthrough()
+(pcgrl_get_playthrough), playthrough_smb() (pcgrl_get_smb_play) and paths() (pcgrl_get_paths) -- each next to the route it is compared
+with, on the GPU box.  One method: wall clock around the call with a device synchronisation, after a warm-up of each call (the handle,
+the workspace, the kernels' code objects, the allocator's blocks); a call is a few ms and the box is shared, so the calls of a case run in
+ONE process on one handle, alternating, `rounds` rounds: minimum, median and maximum of each.  Every case runs in a child process of its
+own under a time limit, so that a hang ends there; a child that fails ends the session.  One JSON line at the end.
+
+    python tools/readout_bench.py evaluate [M] [problem ...]         (default: 65536 binary zelda sokoban)
+    python tools/readout_bench.py solve [M]                          (default: 65536)
+    python tools/readout_bench.py playthrough [--prob mdungeon|ddave] [M]   (default: mdungeon, 65536)
+    python tools/readout_bench.py smb_play [M] [max_len]             (default: 4096 maps, max_len 255)
+    python tools/readout_bench.py paths [M14 [M11x16 [M64]]]         (defaults: 65536 65536 4096)
+
+evaluate: evaluate() next to the route there was before it -- a handle of M environments: reset(); set_maps(maps); stats -- three runs
+of each; the handle route is timed with and without building the handle (allocation + seeding + reset), which that route needs once per
+batch size.  solve, playthrough: the call next to evaluate() on the same M seeded random levels (sokoban 5 x 5; mdungeon, ddave 7 x 11),
+and on a handle's own levels (M environments after a reset, the map buffer read in place), 30 rounds.  smb_play: playthrough_smb() next
+to evaluate() (for smb the scratch-environment route: set_maps() of a private environment, that is k_smb) on the 14 x 114 levels of
+tests/golden/stats_smb_14x114_p1500.npz tiled to M maps, 20 rounds.  paths: paths() with the default max_len (H * W: every leg whole) and
+with max_len 64 (the rows a drawing loop of short legs would ask for) next to evaluate(), binary 14 x 14, zelda 11 x 16, binary 64 x 64,
+30 rounds.  The statistics rows of the calls of a case must agree.
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+sys.path.insert(0, ROOT)
+LIMIT_S = 240
+SHAPES = {"binary": (14, 14), "zelda": (11, 16), "sokoban": (5, 5), "mdungeon": (7, 11), "ddave": (7, 11)}      # rows, columns
+EVALUATE_SHAPES = dict(SHAPES, mdungeon=(11, 7))
+SMB_FIXTURE = os.path.join(ROOT, "tests", "golden", "stats_smb_14x114_p1500.npz")
+
+
+# ---- what every child shares
+def levels(prob, m, h, w):
+    """M seeded random levels with the problem's own tile probabilities (what reset() draws)."""
+    import numpy as np
+    from gym_pcgrl_amd.envs.problems import PROBLEMS
+    p = np.array(list(PROBLEMS[prob]()._prob.values()), dtype=np.float64)
+    return np.random.RandomState(7).choice(len(p), size=(m, h, w), p=p / p.sum()).astype(np.uint8)
+
+
+def timed(call, sync):
+    t0 = time.perf_counter()
+    r = call()
+    sync()
+    return time.perf_counter() - t0, r
+
+
+def alternate(calls, rounds):
+    """Warm every call up, then `rounds` rounds of all of them in turn: what the box does meanwhile meets them alike.  -> ({name: [s]}, {name: last result})"""
+    import torch
+    sync = torch.cuda.synchronize
+    last = {k: c() for k, c in calls.items()}
+    sync()
+    t = {k: [] for k in calls}
+    for _ in range(rounds):
+        for k, c in calls.items():
+            dt, last[k] = timed(c, sync)
+            t[k].append(dt)
+    return t, last
+
+
+def make_env(prob, shape=None, num_envs=1, power=None):
+    from gym_pcgrl_amd.envs import BatchedPcgrlEnv
+    env = BatchedPcgrlEnv(prob=prob, rep="wide", num_envs=num_envs, seed=0)
+    if power is not None:
+        env._prob._solver_power = power           # (smb's is an attribute)
+    if shape is not None:
+        env.adjust_param(width=shape[1], height=shape[0])
+    return env
+
+
+def checksum(env, rows):
+    import torch
+    return int(rows[:, :env._layout.nstats].to(torch.int64).sum().item())
+
+
+def device_maps(array):
+    import torch
+    return torch.as_tensor(array).cuda()
+
+
+# ---- the children: one case each, -> the case's result
+def evaluate_child(route, prob, m):
+    import torch
+    shape = EVALUATE_SHAPES[prob]
+    maps = device_maps(levels(prob, m, *shape))
+    out = {"route": route, "prob": prob, "M": m}
+    if route == "evaluate":
+        env = make_env(prob, shape)
+        t, last = alternate({"evaluate": lambda: env.evaluate(maps)}, 3)
+        out["s"] = t["evaluate"]
+        out["checksum"] = checksum(env, last["evaluate"].rows)
+    else:
+        t, tb = [], []
+        for _ in range(3 + 1):                  # (the first pass is the warm-up)
+            t0 = time.perf_counter()
+            env = make_env(prob, shape, num_envs=m)
+            env.reset()
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            dt, _ = timed(lambda: env.set_maps(maps), torch.cuda.synchronize)
+            tb.append(t1 - t0 + dt)
+            t.append(dt)
+            out["checksum"] = checksum(env, env._bufs["stats"])
+            env.close()
+        out["s"] = t[1:]
+        out["s_with_handle"] = tb[1:]
+    return out
+
+
+def moves_child(method, route, prob, m):
+    """solve() / playthrough(): `pair` -- the call and evaluate() on the same maps -- or `own` -- the call on a handle's own levels."""
+    import torch
+    shape = SHAPES[prob]
+    resize = shape if method == "playthrough" else None       # (5 x 5 is sokoban's own size)
+    out = {"route": route, "prob": prob, "M": m} if method == "playthrough" else {"route": route, "M": m}
+    if route == "own":
+        env = make_env(prob, resize, num_envs=m)
+        env.reset()
+        calls = {method + "_own": lambda: getattr(env, method)()}
+    else:
+        maps = device_maps(levels(prob, m, *shape))
+        env = make_env(prob, resize)
+        calls = {"evaluate": lambda: env.evaluate(maps), method: lambda: getattr(env, method)(maps)}
+    out["s"], last = alternate(calls, 30)
+    out["checksum"] = {k: checksum(env, r.rows) for k, r in last.items()}
+    r = last[method + "_own" if route == "own" else method]
+    if method == "solve":
+        out["solved"] = int((r.length > 0).sum().item())
+    else:
+        out["ran"] = int((r.agent > -2).sum().item())
+        out["won"] = int((r.agent >= 0).sum().item())
+    out["moves"] = int(r.length.to(torch.int64).sum().item())
+    out["longest"] = int(r.length.max().item())
+    assert env.check_status() == 0
+    return out
+
+
+def smb_play_child(m, max_len):
+    import numpy as np
+    import torch
+    d = np.load(SMB_FIXTURE)
+    base, power = d["maps"], int(d["solver_power"])
+    pick = np.arange(m) % base.shape[0]
+    maps = device_maps(np.ascontiguousarray(base[pick]))
+    env = make_env("smb", base.shape[1:], power=power)
+    t, last = alternate({"evaluate": lambda: env.evaluate(maps, chunk=m), "playthrough_smb": lambda: env.playthrough_smb(maps, max_len=max_len)}, 20)
+    pt = last["playthrough_smb"]
+    assert torch.equal(pt.rows, last["evaluate"].rows), "playthrough_smb() and evaluate() disagree on the statistics rows"
+    assert env.check_status() == 0
+    return {"M": m, "max_len": max_len, "power": power, "s": t, "won": int((pt.agent >= 0).sum().item()), "second_agent": int((pt.agent != 0).sum().item()),
+            "moves": int(pt.length.to(torch.int64).sum().item()), "longest": int(pt.length.max().item()),
+            "pops": [int(d["agents"][pick, k].sum()) for k in (0, 1)]}
+
+
+def paths_child(prob, h, w, m):
+    import torch
+    out = {"prob": prob, "h": h, "w": w, "M": m}
+    maps = device_maps(levels(prob, m, h, w))
+    env = make_env(prob, (h, w))
+    short = min(64, h * w)
+    out["s"], last = alternate({"evaluate": lambda: env.evaluate(maps), "paths": lambda: env.paths(maps),
+                                "paths_%d" % short: lambda: env.paths(maps, max_len=short)}, 30)
+    out["checksum"] = {k: checksum(env, r.rows) for k, r in last.items()}
+    p, rows = last["paths"], last["paths"].rows
+    ln = p.length.to(torch.int64)
+    if prob == "binary":        # the lengths are the statistics': path-length; key + door = path-length, enemy = nearest-enemy
+        assert torch.equal(ln[ln[:, 0] >= 0, 0], rows[ln[:, 0] >= 0, 1].to(torch.int64))
+    else:
+        both = ln[:, 0] >= 0
+        assert torch.equal(ln[both, 0] + ln[both, 1], rows[both, 6].to(torch.int64)) and torch.equal(ln[ln[:, 2] >= 0, 2], rows[ln[:, 2] >= 0, 5].to(torch.int64))
+    assert torch.equal(p.cells[:, :, :short], last["paths_%d" % short].cells)
+    out["legs"] = [int(v) for v in (ln >= 0).sum(0).tolist()]
+    out["cells"] = int((ln + 1).clamp(min=0).sum().item())
+    out["longest"] = int(ln.max().item())
+    out["bytes_cells"] = {k: int(r.cells.numel() * 2) for k, r in last.items() if k != "evaluate"}
+    assert env.check_status() == 0
+    return out
+
+
+# ---- the subcommands: arguments -> cases (label, child arguments); a note behind a call's report line; the results -> the JSON
+def moves_note(r, k):
+    if k == "evaluate":
+        return ""
+    return ("   solved %d" % r["solved"] if "solved" in r else "   planner ran %d, won %d" % (r["ran"], r["won"])) + ", %d moves, longest %d" % (r["moves"], r["longest"])
+
+
+def moves_final(method):
+    def final(res):
+        res = {r["route"]: r for r in res}
+        assert res["pair"]["checksum"]["evaluate"] == res["pair"]["checksum"][method], "%s() and evaluate() disagree on the statistics rows" % method
+        return res
+    return final
+
+
+def evaluate_final(res):
+    out = {}
+    for r in res:
+        out.setdefault(r["prob"], {})[r["route"]] = r
+    for prob, routes in out.items():
+        assert routes["evaluate"]["checksum"] == routes["handle"]["checksum"], (prob, "the two routes disagree")
+    return out
+
+
+def paths_final(res):
+    for r in res:
+        assert len(set(r["checksum"].values())) == 1, "paths() and evaluate() disagree on the statistics rows"
+    return res
+
+
+def smb_play_final(res):
+    r, = res
+    print("won %d of %d, the second agent played %d, %d moves, longest %d; pops of the two agents %s" % (r["won"], r["M"], r["second_agent"], r["moves"], r["longest"], r["pops"]))
+    return r
+
+
+def arguments(p, sub):
+    if sub == "evaluate":
+        p.add_argument("m", nargs="?", type=int, default=65536, metavar="M")
+        p.add_argument("probs", nargs="*", metavar="problem", help="of %s" % ", ".join(sorted(EVALUATE_SHAPES)))
+    elif sub == "paths":
+        p.add_argument("ms", nargs="*", type=int, default=[], metavar="M", help="levels of binary 14 x 14, zelda 11 x 16, binary 64 x 64 (65536 65536 4096)")
+    else:
+        if sub == "playthrough":
+            p.add_argument("--prob", default="mdungeon", choices=("mdungeon", "ddave"))
+        p.add_argument("m", nargs="?", type=int, default=4096 if sub == "smb_play" else 65536, metavar="M")
+        if sub == "smb_play":
+            p.add_argument("max_len", nargs="?", type=int, default=255)
+
+
+SPECS = {
+    "evaluate": dict(child=evaluate_child, final=evaluate_final, note=lambda r, k: "",
+                     cases=lambda a: [("%s / %s" % (prob, route), (route, prob, a.m)) for prob in a.probs or ["binary", "zelda", "sokoban"] for route in ("evaluate", "handle")]),
+    "solve": dict(child=lambda *c: moves_child("solve", *c), final=moves_final("solve"), note=moves_note,
+                  cases=lambda a: [(route, (route, "sokoban", a.m)) for route in ("pair", "own")]),
+    "playthrough": dict(child=lambda *c: moves_child("playthrough", *c), final=moves_final("playthrough"), note=moves_note,
+                        cases=lambda a: [("%s %s" % (a.prob, route), (route, a.prob, a.m)) for route in ("pair", "own")]),
+    "smb_play": dict(child=smb_play_child, final=smb_play_final, note=lambda r, k: "", cases=lambda a: [("smb", (a.m, a.max_len))]),
+    "paths": dict(child=paths_child, final=paths_final,
+                  note=lambda r, k: "" if k == "evaluate" else "   legs %s, %d cells, longest %d, %.1f MB of rows" % (r["legs"], r["cells"], r["longest"], r["bytes_cells"][k] / 1e6),
+                  cases=lambda a: [("%s %dx%d" % (prob, h, w), (prob, h, w, m))
+                                   for (prob, h, w), m in zip((("binary", 14, 14), ("zelda", 11, 16), ("binary", 64, 64)), a.ms + [65536, 65536, 4096][len(a.ms):])]),
+}
+
+
+def run_child(sub, label, cargs):
+    """The case in a process of its own under the time limit; a fault, an abort or the time limit: nothing more is started on the GPU."""
+    p = subprocess.run(["timeout", "-k", "10", str(LIMIT_S), sys.executable, os.path.abspath(__file__), "--child", sub, json.dumps(cargs)],
+                       capture_output=True, text=True)
+    if p.returncode != 0:
+        sys.stderr.write(p.stdout[-2000:] + p.stderr[-4000:])
+        sys.exit("readout_bench %s: %s ended with status %d" % (sub, label, p.returncode))
+    return json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")][-1][7:])
+
+
+def report(label, k, m, ts, note):
+    ts = sorted(ts)
+    med = ts[len(ts) // 2]
+    print("%-16s %-18s M=%d  %d rounds  ms: min %.3f  median %.3f  max %.3f   M levels/s at the median: %.4f%s" % (
+        label, k, m, len(ts), ts[0] * 1e3, med * 1e3, ts[-1] * 1e3, m / med / 1e6, note), flush=True)
+
+
+def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "--child":
+        import torch
+        if not torch.cuda.is_available():
+            sys.exit("readout_bench: needs the GPU")
+        print("RESULT " + json.dumps(SPECS[sys.argv[2]]["child"](*json.loads(sys.argv[3]))), flush=True)
+        return
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    subs = ap.add_subparsers(dest="sub", required=True)
+    for sub in SPECS:
+        arguments(subs.add_parser(sub), sub)
+    a = ap.parse_args()
+    if [p for p in getattr(a, "probs", []) if p not in EVALUATE_SHAPES]:
+        ap.error("evaluate: problems of %s" % ", ".join(sorted(EVALUATE_SHAPES)))
+    spec = SPECS[a.sub]
+    res = []
+    for label, cargs in spec["cases"](a):
+        r = run_child(a.sub, label, cargs)
+        res.append(r)
+        for k, ts in (r["s"].items() if isinstance(r["s"], dict) else [(key, r[key]) for key in ("s", "s_with_handle") if key in r]):
+            report(label, k, r["M"], ts, spec["note"](r, k))
+    print(json.dumps(spec["final"](res)))
+
+
+if __name__ == "__main__":
+    main()
