@@ -113,6 +113,13 @@ def path_levels(prob, maps, device=None, max_len=None, **params):
     return _on_levels("path_levels", prob, maps, device, params, lambda env: env.paths(maps, max_len=max_len))
 
 
+def change_levels(prob, maps, cells=None, device=None, start=None, rows=True, **params):
+    """Every one-cell change of a stack of levels scored in one call, next to evaluate_levels() and path_levels(): `maps` array-like
+    uint8 [M, H, W], `cells` [M, K] or [K] (y * W + x each; None: every cell), `params` as for adjust_param (smb: solver_power is set
+    as an attribute, like evaluate_levels()).  Returns BatchedPcgrlEnv.changes()'s Changes (rows, reward, over, base_rows, cells, stats)."""
+    return _on_levels("change_levels", prob, maps, device, params, lambda env: env.changes(maps, cells=cells, start=start, rows=rows), smb_power="after")
+
+
 class PathCheck:
     """What check_path() returns: `legal` bool [T] per cell (in range, on a passable tile, 4-adjacent to the cell before it, not seen
     before) and `ok`: every cell is legal."""

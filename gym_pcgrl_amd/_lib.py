@@ -37,7 +37,8 @@ class Layout(C.Structure):
 
 
 TUNING_FIELDS = ("no_fused", "fused_zelda", "step_epb", "no_inc", "inline_reset", "pair_min", "no_wide", "wide_waves", "wide_grid",
-                 "wide_pairs", "wide_few", "sok_generic", "sok_hard_cap", "sok_spawn", "md_only_agent", "smb_lds_heap", "full_per_wave", "inc_per_wave", "wide_spin", "step_prio", "no_touch", "touch_tight", "step_pair", "async_split", "big_team", "obs_at_end", "touch_resume")
+                 "wide_pairs", "wide_few", "sok_generic", "sok_hard_cap", "sok_spawn", "md_only_agent", "smb_lds_heap", "full_per_wave", "inc_per_wave", "wide_spin", "step_prio", "no_touch", "touch_tight", "step_pair", "async_split", "big_team", "obs_at_end", "touch_resume",
+                 "changes_grid", "changes_chunk")
 
 
 class Tuning(C.Structure):
@@ -83,7 +84,7 @@ class RenderDesc(C.Structure):
                 ("grid_rows", C.c_int32), ("grid_cols", C.c_int32), ("out", C.c_void_p)]
 
 
-ABI_VERSION = 15         # include/pcgrl_hip.h PCGRL_ABI_VERSION (pcgrl_bind_row, pcgrl_render, pcgrl_get_stats, pcgrl_get_solution, pcgrl_get_playthrough, pcgrl_get_smb_play, pcgrl_get_paths are additions within 15: found by their symbols)
+ABI_VERSION = 15         # include/pcgrl_hip.h PCGRL_ABI_VERSION (pcgrl_bind_row, pcgrl_render, pcgrl_get_stats, pcgrl_get_solution, pcgrl_get_playthrough, pcgrl_get_smb_play, pcgrl_get_paths, pcgrl_get_changes are additions within 15: found by their symbols)
 EXPORTS = ("pcgrl_abi_version", "pcgrl_error_string", "pcgrl_last_hip_error", "pcgrl_query_layout", "pcgrl_create",
            "pcgrl_destroy", "pcgrl_bind", "pcgrl_configure", "pcgrl_seed", "pcgrl_set_tile_probs", "pcgrl_reset",
            "pcgrl_step", "pcgrl_set_maps", "pcgrl_observe", "pcgrl_action_map", "pcgrl_status", "pcgrl_profile",
@@ -92,7 +93,8 @@ EXPORTS = ("pcgrl_abi_version", "pcgrl_error_string", "pcgrl_last_hip_error", "p
            "pcgrl_async_bytes", "pcgrl_bind_async", "pcgrl_step_async", "pcgrl_async_flush", "pcgrl_step_multi", "pcgrl_selftest_step_pool", "pcgrl_step_threads", "pcgrl_selftest_range_reward",
            "pcgrl_bind_row", "pcgrl_render", "pcgrl_get_stats_bytes", "pcgrl_get_stats", "pcgrl_get_reward",
            "pcgrl_get_solution_bytes", "pcgrl_get_solution", "pcgrl_get_playthrough_bytes", "pcgrl_get_playthrough",
-           "pcgrl_get_smb_play_bytes", "pcgrl_get_smb_play", "pcgrl_get_paths_legs", "pcgrl_get_paths_bytes", "pcgrl_get_paths")
+           "pcgrl_get_smb_play_bytes", "pcgrl_get_smb_play", "pcgrl_get_paths_legs", "pcgrl_get_paths_bytes", "pcgrl_get_paths",
+           "pcgrl_get_changes_bytes", "pcgrl_get_changes")
 NPHASE = 6
 # the six intervals between the seven event marks of a step; sokoban: update, stats, reset, solver, reset2, solver2;
 # other problems: update, stats(+resets), -, reset (only with PCGRL_INLINE_RESET=0), -, -
@@ -219,6 +221,11 @@ def load():
     L.pcgrl_get_paths_bytes.restype = C.c_size_t
     # handle, maps, count, max_len, cells, length, rows, work, work_bytes, stream
     L.pcgrl_get_paths.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.pcgrl_get_changes_bytes.argtypes = [C.POINTER(Config), C.c_int32, C.c_int32]
+    L.pcgrl_get_changes_bytes.restype = C.c_size_t
+    # handle, maps, count, cells, ncells, start_rows, base_rows, rows, reward, over, work, work_bytes, stream
+    L.pcgrl_get_changes.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_size_t, C.c_void_p]
     L.pcgrl_action_map.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pcgrl_step_flat.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pcgrl_selftest_heap.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

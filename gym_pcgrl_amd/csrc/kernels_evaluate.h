@@ -5,7 +5,8 @@
 //                        A map that needs the planner gets its partial row and a place on the job list (counter + indices in `work`).
 //   k_get_stats_search   sokoban / mdungeon / ddave: persistent blocks shaped like the search phase of k_step_solver -- eight
 //                        wavefronts try a chunk of jobs in small private regions, wavefront 0 redoes what was stopped by the small
-//                        limit in the full region with the full solver_power.  The job count is read from device memory.
+//                        limit in the full region with the full solver_power.  The job count is read from device memory.  What a job
+//                        is comes from a source: EvalMaps here, ChangeJobs for pcgrl_get_changes (kernels_changes.h).
 //   k_get_reward         a thread per row: compute_reward + episode_over (pcgrl_algos.h).
 #pragma once
 
@@ -15,15 +16,17 @@ enum { EVAL_HEAD_NJOBS = 0, EVAL_HEAD_TICKET = 1 };
 #define EVAL_CHUNK (SS_SEARCH_WAVES * EVAL_JOBS_PER_WAVE)          /* jobs a block takes per ticket */
 #define EVAL_STAGE_BYTES 256                                       /* a compact search level has at most 256 bordered cells */
 
+// a tile id beyond the last counts as the last one: the one rule of every pass that reads the caller's bytes (eval_stage_map, k_changes_finish)
+__device__ __forceinline__ uint8_t eval_tile_clamped(uint8_t t, int ntiles) { return t >= ntiles ? (uint8_t)(ntiles - 1) : t; }
 // the caller's tile bytes of map m into the group's LDS stage: a tile id beyond the last is clamped here (the caller's map stays as
 // it is) and reported in the status word
 __device__ __forceinline__ void eval_stage_map(const uint8_t* __restrict__ maps, long long m, int cells, int ntiles, uint8_t* stage, int lane, int nlanes,
                                                int32_t* status) {
     const uint8_t* src = maps + (size_t)m * cells;
     for (int c = lane; c < cells; c += nlanes) {
-        uint8_t t = src[c];
-        if (t >= ntiles) { atomicOr(status, PCGRL_STATUS_BAD_TILE); t = (uint8_t)(ntiles - 1); }
-        stage[c] = t;
+        const uint8_t t = src[c];
+        if (t >= ntiles) atomicOr(status, PCGRL_STATUS_BAD_TILE);
+        stage[c] = eval_tile_clamped(t, ntiles);
     }
 }
 
@@ -62,8 +65,19 @@ __global__ __launch_bounds__(PCGRL_BLOCK) void k_get_stats(PcgrlParams P, const 
 // `Bs`: what search_game_run reads of a DevBufs -- status, sok_use_lds, sok_fast_maxc (SearchGame<PROB>::build) and `map`, which every
 // wavefront points at its own clamped LDS copy of the job's map (environment 0 of a one-map batch): the agents work on the level
 // that build() left in LDS and on the regions and pools they are handed, nothing else of the struct is dereferenced.
-template <int PROB>
-__global__ __launch_bounds__(SS_THREADS) void k_get_stats_search(PcgrlParams P, DevBufs Bs, const uint8_t* __restrict__ maps, int32_t* __restrict__ rows_out,
+// `Src`: what a job is -- stage(j, P, cells, stage, lane, status) fills a wavefront's stage with job j's level (the wave barrier follows
+// here), row(j) is where its row goes.  EvalMaps: job j is map j of the caller's (pcgrl_get_stats); ChangeJobs (kernels_changes.h): a
+// level with one cell set to a tile.
+struct EvalMaps {
+    const uint8_t* __restrict__ maps;
+    int32_t* __restrict__ rows_out;
+    __device__ __forceinline__ void stage(int m, const PcgrlParams& P, int cells, uint8_t* stage, int lane, int32_t* status) const {
+        eval_stage_map(maps, m, cells, P.ntiles, stage, lane, 64, status);
+    }
+    __device__ __forceinline__ int32_t* row(int m) const { return rows_out + (size_t)m * 8; }
+};
+template <int PROB, class Src>
+__global__ __launch_bounds__(SS_THREADS) void k_get_stats_search(PcgrlParams P, DevBufs Bs, Src src,
                                                                   int32_t* head, const int32_t* __restrict__ jobs, SokNode* pools, int pool_stride) {
     extern __shared__ __attribute__((aligned(16))) uint32_t ss_lds[];     // the full search region; the small ones are carved out of it
     typedef SearchGame<PROB> Game;
@@ -89,14 +103,14 @@ __global__ __launch_bounds__(SS_THREADS) void k_get_stats_search(PcgrlParams P, 
         if (wv < SS_SEARCH_WAVES) {
             for (int j = wv; j < n; j += SS_SEARCH_WAVES) {
                 const int m = jobs[base + j];
-                eval_stage_map(maps, m, cells, P.ntiles, s_stage[wv], lane64, 64, B.status);
+                src.stage(m, P, cells, s_stage[wv], lane64, B.status);
                 __builtin_amdgcn_wave_barrier();
                 __threadfence_block();
                 int res[Game::NRES] = {};
                 const bool final = search_game_run<PROB>(P, B, 0, small_games[wv], ss_lds + wv * SS_SMALL_WORDS, SS_SMALL_HEAP, SS_SMALL_TABLE, small_power,
                                                          pool + (size_t)wv * SS_SMALL_NODES, lane64, res);
                 if (lane64 == 0) {
-                    if (final) Game::pack(rows_out + (size_t)m * 8, res);
+                    if (final) Game::pack(src.row(m), res);
                     else s_big[atomicAdd(&s_nbig, 1)] = m;
                 }
                 __builtin_amdgcn_wave_barrier();
@@ -107,12 +121,12 @@ __global__ __launch_bounds__(SS_THREADS) void k_get_stats_search(PcgrlParams P, 
             const int nbig = s_nbig;
             for (int q = 0; q < nbig; q++) {
                 const int m = s_big[q];
-                eval_stage_map(maps, m, cells, P.ntiles, s_stage[0], lane64, 64, B.status);
+                src.stage(m, P, cells, s_stage[0], lane64, B.status);
                 __builtin_amdgcn_wave_barrier();
                 __threadfence_block();
                 int res[Game::NRES] = {};
                 search_game_run<PROB>(P, B, 0, s_game0, ss_lds, SOK_LDS_HEAP, SOK_LDS_TABLE, P.solver_power, pool, lane64, res);
-                if (lane64 == 0) Game::pack(rows_out + (size_t)m * 8, res);
+                if (lane64 == 0) Game::pack(src.row(m), res);
                 __builtin_amdgcn_wave_barrier();
             }
         }

@@ -85,6 +85,7 @@
 #include "kernels_step_solver.h"
 #include "kernels_search_async.h"
 #include "kernels_evaluate.h"
+#include "kernels_changes.h"      // (after kernels_evaluate.h: eval_stage_map, the job source of k_get_stats_search)
 #include "kernels_paths.h"
 #include "kernels_moves.h"
 #include "kernels_smb_play.h"     // (after kernels_moves.h: SolOut)
@@ -633,6 +634,17 @@ PCGRL_LOCAL int launch_step_solver(pcgrl_env* h, const int32_t* actions, hipStre
 PCGRL_LOCAL int launch_get_stats(pcgrl_env* h, const uint8_t* maps, int count, int32_t* rows_out, int32_t* head, int32_t* jobs, hipStream_t st);
 PCGRL_LOCAL int launch_get_stats_search(pcgrl_env* h, const uint8_t* maps, int32_t* rows_out, int32_t* head, const int32_t* jobs, SokNode* pools, int blocks, hipStream_t st);
 PCGRL_LOCAL int launch_get_paths(pcgrl_env* h, const uint8_t* maps, int count, int max_len, int16_t* cells_out, int32_t* length_out, int32_t* rows_out, hipStream_t st);
+struct ChangesArgs {      // pcgrl_get_changes' arguments as its launches take them; chunk / nchunks / grid_cap: the host's cut into work items
+    const uint8_t* maps; int count; const int32_t* cells; int ncells; const int32_t* start_rows;
+    int32_t* base_rows; int32_t* rows; double* reward; uint8_t* over;
+    int chunk, nchunks, grid_cap;
+};
+PCGRL_LOCAL int launch_get_changes(pcgrl_env* h, const ChangesArgs& A, int32_t* head, int32_t* jobs, hipStream_t st);
+// The lanes a level of k_get_changes takes: the handle's lane group, but a wavefront where a map of at most 16 rows has 64-bit row masks
+// (33 to 64 columns) -- with sixteen lanes that form keeps 4 to 9 dwords a lane in scratch at the 64 registers the kernel is held to,
+// with 64 it keeps none (the rows beyond 16 are empty: planes_from_tiles gives them no bits, row_valid no cells)
+static int changes_group(const PcgrlParams& P) { return (P.group == 16 && P.mask_bytes == 8) ? 64 : P.group; }
+PCGRL_LOCAL int launch_get_changes_search(pcgrl_env* h, const ChangeJobs& src, int32_t* head, const int32_t* jobs, SokNode* pools, int blocks, hipStream_t st);
 PCGRL_LOCAL int launch_get_moves(pcgrl_env* h, const uint8_t* maps, int32_t* rows_out, const SolOut& out, int32_t* head, const int32_t* jobs, SokNode* pools, uint32_t* traces, int blocks, hipStream_t st);
 PCGRL_LOCAL int launch_smb_play(pcgrl_env* h, const uint8_t* maps, int count, int32_t* rows_out, const SolOut& out, int32_t* ticket, uint8_t* arenas, int slots, hipStream_t st);
 PCGRL_LOCAL int launch_search_async(pcgrl_env* h, int32_t* tickets, int list_a, int mode_a, int list_b, int mode_b, int parity, int rst_list, int clr, int budget, int resume, int small, hipStream_t st);
@@ -798,6 +810,22 @@ PCGRL_LOCAL int launch_get_paths(pcgrl_env* h, const uint8_t* maps, int count, i
         constexpr int PROB = prob();
         return with_lanes(P.group, P.mask_bytes, [&](auto g, auto m) {
             return launch<k_get_paths<PROB, g(), type_of<decltype(m)>>>(h, G.grid, PCGRL_BLOCK, G.lds, st, P, maps, count, max_len, cells_out, length_out, rows_out, h->B.status);
+        });
+    });
+}
+// pcgrl_get_changes, first launch (kernels_changes.h): launch_get_stats' stage and grid over the (level, chunk of cells) items
+PCGRL_LOCAL int launch_get_changes(pcgrl_env* h, const ChangesArgs& A, int32_t* head, int32_t* jobs, hipStream_t st) {
+    const PcgrlParams& P = h->P;
+    const int group = changes_group(P), per_block = (PCGRL_BLOCK / 64) * (64 / group);       // (map_grid's shape for that lane group)
+    const long long blocks = ((long long)A.count * A.nchunks + per_block - 1) / per_block;
+    const int grid = (int)(blocks < A.grid_cap ? blocks : A.grid_cap);
+    const size_t lds = (size_t)per_block * changes_group_bytes(P.width * P.height, group, P.mask_bytes);
+    return with_prob<PCGRL_PROB_BINARY, PCGRL_PROB_ZELDA, PCGRL_PROB_MDUNGEON, PCGRL_PROB_DDAVE, PCGRL_PROB_SOKOBAN>(P.prob, [&](auto prob) {
+        constexpr int PROB = prob();
+        return with_lanes(group, P.mask_bytes, [&](auto g, auto m) {
+            if constexpr (g() == 16 && sizeof(type_of<decltype(m)>) == 8) return PCGRL_EINVAL;      // (changes_group)
+            else return launch<k_get_changes<PROB, g(), type_of<decltype(m)>>>(h, grid, PCGRL_BLOCK, lds, st, P, A.maps, A.count, A.cells, A.ncells, A.chunk, A.nchunks,
+                                                                          A.start_rows, A.base_rows, A.rows, A.reward, A.over, h->B.status, head, jobs);
         });
     });
 }
@@ -1045,7 +1073,14 @@ static int search_pool_stride(const pcgrl_env* h) { return (int)(sok_pool_bytes(
 // (kernels_evaluate.h)
 PCGRL_LOCAL int launch_get_stats_search(pcgrl_env* h, const uint8_t* maps, int32_t* rows_out, int32_t* head, const int32_t* jobs, SokNode* pools, int blocks, hipStream_t st) {
     return with_prob<PCGRL_PROB_SOKOBAN, PCGRL_PROB_MDUNGEON, PCGRL_PROB_DDAVE>(h->P.prob, [&](auto prob) {
-        return launch<k_get_stats_search<prob()>>(h, blocks, SS_THREADS, sok_lds_bytes(), st, h->P, search_devbufs(h), maps, rows_out, head, jobs, pools, search_pool_stride(h));
+        return launch<k_get_stats_search<prob(), EvalMaps>>(h, blocks, SS_THREADS, sok_lds_bytes(), st, h->P, search_devbufs(h), EvalMaps{maps, rows_out}, head, jobs, pools,
+                                                            search_pool_stride(h));
+    });
+}
+// (kernels_changes.h: the same searches, a job being a level with one cell set to a tile)
+PCGRL_LOCAL int launch_get_changes_search(pcgrl_env* h, const ChangeJobs& src, int32_t* head, const int32_t* jobs, SokNode* pools, int blocks, hipStream_t st) {
+    return with_prob<PCGRL_PROB_SOKOBAN, PCGRL_PROB_MDUNGEON, PCGRL_PROB_DDAVE>(h->P.prob, [&](auto prob) {
+        return launch<k_get_stats_search<prob(), ChangeJobs>>(h, blocks, SS_THREADS, sok_lds_bytes(), st, h->P, search_devbufs(h), src, head, jobs, pools, search_pool_stride(h));
     });
 }
 // (kernels_moves.h: k_get_stats_search's shape with the traced searches; `traces`: as many words per block as its pool has nodes --
@@ -1736,6 +1771,71 @@ int pcgrl_get_reward(pcgrl_env* h, const int32_t* rows, const int32_t* ref_rows,
     DeviceGuard guard(h->device);
     const int grid = (int)(((long long)count + 255) / 256 < 4096 ? ((long long)count + 255) / 256 : 4096);
     hipLaunchKernelGGL(k_get_reward<0>, dim3(grid), dim3(256), 0, (hipStream_t)stream, h->P, rows, ref_rows, count, reward_out, over_out);
+    HIPCHK(hipGetLastError());
+    return PCGRL_OK;
+}
+
+// ---- pcgrl_get_changes (kernels_changes.h): every listed cell of every level set to every tile -------------------------------------
+// The workspace, cut from one plan like pcgrl_get_stats'.  binary, zelda: the head every such call has -- the one launch keeps the
+// level's row in registers.  The search problems: pcgrl_get_stats' three regions for entries + count jobs (every entry and every
+// level's own row may need the planner), and rows for a caller that wants none: the entries' and the levels'.
+struct ChangesPlan { EvalPlan E; Region rows, base; long long entries; size_t total; };
+static ChangesPlan changes_plan(const pcgrl_config* c, int count, int ncells) {
+    ChangesPlan S = {};
+    S.entries = (long long)count * ncells * ntiles_of(c->prob);
+    if (!solver_prob(c->prob)) { Bump b = {0}; S.E.head = b.take(256); S.total = b.off; return S; }
+    S.E = eval_plan(c, (int)(S.entries + count));
+    Bump b = {S.E.total};
+    S.rows = b.take(align_up((size_t)S.entries * 8 * 4, 256));
+    S.base = b.take(align_up((size_t)count * 8 * 4, 256));
+    S.total = b.off;
+    return S;
+}
+// Cells of a level per work item.  A level is staged, and its planes and own row are made, once per item: as few items a level as
+// still fill the device -- CHANGES_FILL_BLOCKS blocks of map_grid's lane groups, eight blocks on each of 256 compute units --, so a
+// large `count` takes every level whole and a single level is cut down to one cell an item.  (pcgrl_tuning changes_chunk overrides.)
+#define CHANGES_FILL_BLOCKS 2048
+static int changes_chunk(const pcgrl_env* h, int count, int ncells) {
+    if (h->tun.changes_chunk > 0) return h->tun.changes_chunk < ncells ? h->tun.changes_chunk : ncells;
+    const long long want = (long long)CHANGES_FILL_BLOCKS * (PCGRL_BLOCK / 64) * (64 / changes_group(h->P));
+    long long per_level = (want + count - 1) / count;
+    per_level = per_level < 1 ? 1 : (per_level > ncells ? ncells : per_level);
+    return (int)((ncells + per_level - 1) / per_level);
+}
+size_t pcgrl_get_changes_bytes(const pcgrl_config* c, int32_t count, int32_t ncells) {
+    pcgrl_config one;
+    if (!c || count < 1 || ncells < 1 || pcgrl_get_stats_bytes(c, count) == 0 || !one_env(c, &one)) return 0;
+    if ((long long)count * ncells * ntiles_of(one.prob) + count > 0x7FFFFFFFLL) return 0;      // entry indices and the job list are 32-bit
+    return changes_plan(&one, count, ncells).total;
+}
+int pcgrl_get_changes(pcgrl_env* h, const uint8_t* maps, int32_t count, const int32_t* cells, int32_t ncells, const int32_t* start_rows,
+                      int32_t* base_rows_out, int32_t* rows_out, double* reward_out, uint8_t* over_out, void* work, size_t work_bytes, void* stream) {
+    const bool ptrs = h && maps && (rows_out || reward_out || over_out) && (cells || ncells == h->cfg.width * h->cfg.height);
+    if (int rc = readout_check(h, ptrs, count, ncells, work, work_bytes, h ? pcgrl_get_changes_bytes(&h->cfg, count, ncells) : 0)) return rc;
+    DeviceGuard guard(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    const ChangesPlan S = changes_plan(&h->cfg, count, ncells);
+    uint8_t* w = (uint8_t*)work;
+    ChangesArgs A = {maps, count, cells, ncells, start_rows, base_rows_out, rows_out, reward_out, over_out, 0, 0, 0};
+    A.chunk = changes_chunk(h, count, ncells);
+    A.nchunks = (ncells + A.chunk - 1) / A.chunk;
+    A.grid_cap = h->tun.changes_grid > 0 ? h->tun.changes_grid : 8192;
+    if (!S.E.pools.bytes) return launch_get_changes(h, A, nullptr, nullptr, st);
+    // the search problems: the partial rows and the job list, the searches, then the no-op entries, rewards and ends over the finished rows
+    int32_t* head = at<int32_t>(w, S.E.head);
+    int32_t* jobs = at<int32_t>(w, S.E.jobs);
+    if (!A.rows) A.rows = at<int32_t>(w, S.rows);
+    if (!A.base_rows) A.base_rows = at<int32_t>(w, S.base);
+    hipLaunchKernelGGL(k_changes_clear<0>, dim3(1), dim3(64), 0, st, head);
+    HIPCHK(hipGetLastError());
+    int rc = launch_get_changes(h, A, head, jobs, st);
+    if (rc) return rc;
+    const ChangeJobs src = {maps, cells, A.rows, A.base_rows, ncells, (int)S.entries};
+    rc = launch_get_changes_search(h, src, head, jobs, at<SokNode>(w, S.E.pools), S.E.blocks, st);
+    if (rc) return rc;
+    const int grid = (int)((S.entries + 255) / 256 < 4096 ? (S.entries + 255) / 256 : 4096);
+    hipLaunchKernelGGL(k_changes_finish<0>, dim3(grid), dim3(256), 0, st, h->P, maps, cells, ncells, (int)S.entries, start_rows,
+                       (const int32_t*)A.base_rows, A.rows, reward_out, over_out);
     HIPCHK(hipGetLastError());
     return PCGRL_OK;
 }

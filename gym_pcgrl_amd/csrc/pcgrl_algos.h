@@ -201,6 +201,17 @@ PCGRL_HD bool episode_over(const PcgrlParams& P, const int32_t* n, const int32_t
 PCGRL_HD bool episode_over(const PcgrlParams& P, const int32_t* n, const int32_t* start) { return episode_over(P, n, start, P.prob); }
 PCGRL_HD int num_stats(int prob) { return prob == PCGRL_PROB_BINARY ? 2 : (prob == PCGRL_PROB_ZELDA ? 7 : (prob == PCGRL_PROB_SOKOBAN ? 6 : 8)); }   // mdungeon, ddave: packed rows
 
+// One cell of a map set to tile `t` in its row's words of the three bit planes (m0..m2 = bits 0..2 of the tile id, bit x = column x):
+// what the lane that owns the cell's row does to its registers -- k_get_changes (kernels_changes.h); the other rows stay as they are.
+// A problem with one plane (binary: tiles 0 and 1) leaves m1 and m2 zero.
+template <class WordT>
+PCGRL_HD void planes_set_cell(WordT& m0, WordT& m1, WordT& m2, int x, int t) {
+    const WordT keep = ~((WordT)1 << x);
+    m0 = (m0 & keep) | ((WordT)(t & 1) << x);
+    m1 = (m1 & keep) | ((WordT)((t >> 1) & 1) << x);
+    m2 = (m2 & keep) | ((WordT)((t >> 2) & 1) << x);
+}
+
 // ---------------------------------------------------------------- bitboard programs
 //
 // Work-saving structure (results are order-independent, so none of this changes an answer):

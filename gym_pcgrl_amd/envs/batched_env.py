@@ -120,6 +120,33 @@ class Paths:
         return x.masked_fill(none, -1), y.masked_fill(none, -1)
 
 
+class Changes:
+    """What BatchedPcgrlEnv.changes() returns, entry [m, k, t] being level m with cell cells[m, k] set to tile t: `rows` int32 [M, K, T, 8]
+    (None with rows=False), `reward` float64 [M, K, T] (new = the entry's row, old = the level's own), `over` bool [M, K, T],
+    `base_rows` int32 [M, 8] (the levels' own rows: evaluate()'s), `cells` int32 [M, K] (y * W + x), `stats`: base_rows decoded."""
+    __slots__ = ("rows", "reward", "over", "base_rows", "cells", "stats")
+
+    def __init__(self, rows, reward, over, base_rows, cells, stats):
+        self.rows, self.reward, self.over, self.base_rows, self.cells, self.stats = rows, reward, over, base_rows, cells, stats
+
+
+def expand_changes(flat, cells, first, n, ntiles):
+    """The expansion rule of changes(): entries `first` .. `first + n - 1` in the order (m, k, t) -- entry (m * K + k) * T + t is level m
+    with cell cells[m, k] set to tile t -- of `flat` uint8 [M, H * W] and `cells` int64 [M, K] (torch tensors on one device, the CPU
+    included).  Returns (levels uint8 [n, H * W], the level m of each entry, noop bool [n]: the cell already holds the tile -- a tile
+    id beyond the last counts as the last one, what the scoring clamps it to)."""
+    import torch
+    e = torch.arange(first, first + n, dtype=torch.int64, device=flat.device)
+    t, col = e % ntiles, e // ntiles
+    k, lv = col % cells.shape[1], col // cells.shape[1]
+    cell = cells[lv, k]
+    levels = flat[lv]                                              # (a copy: advanced indexing)
+    row = torch.arange(n, device=flat.device)
+    noop = levels[row, cell].clamp(max=ntiles - 1) == t
+    levels[row, cell] = t.to(torch.uint8)
+    return levels, lv, noop
+
+
 class BatchedPcgrlEnv:
     metadata = {"render.modes": []}
 
@@ -904,6 +931,121 @@ class BatchedPcgrlEnv:
                                              C.c_void_p(length.data_ptr()), C.c_void_p(rows.data_ptr()),
                                              *work, self._stream()), "pcgrl_get_paths")
         return Paths(cells, length, rows, self._prob.decode_rows(rows), legs, self._alloc_dims[0])
+
+    # ---- every one-cell change of a level: rows, reward and episode end (pcgrl_get_changes)
+    def changes(self, maps=None, cells=None, start=None, rows=True, chunk=65536):
+        """What would changing one cell do?  For `maps` -- array-like uint8 [M, H, W] as for evaluate(); None: this environment's current
+        levels (after a reset(); the handle's own map buffer is read in place) -- and per level K cells, entry [m, k, t] is level m with
+        cell k set to tile t, for each of the problem's T tiles, scored with the parameters in force:
+        `rows` int32 [M, K, T, 8] (rows=False: None, and nothing that large is allocated) the statistics row of that level, `reward`
+        float64 [M, K, T] Problem.get_reward(new=that row, old=the level's own row) -- what the step that makes the change would pay --
+        and `over` bool [M, K, T] Problem.get_episode_over(new=that row, start).  The entry of the tile a cell already holds is the
+        level's own row with reward 0.  Returns Changes (rows, reward, over, base_rows [M, 8], cells int32 [M, K], stats = base_rows
+        decoded), all on the device; nothing is waited for.
+        `cells`: [M, K] or [K] (the same for every level), a cell being y * W + x, repeats allowed; None: every cell in row-major
+        order.  A host array is range-checked (ValueError); a device tensor is not: a cell outside the map is clamped into it and
+        reported by check_status() like an action outside the action space.  "cursor" (maps=None; not the wide representation,
+        which has none): K = 1, the cell under each environment's cursor, read from the `pos` buffer on the device -- reward[i, 0, a - 1]
+        is what action a > 0 of a narrow environment would be paid next.
+        `start`: int32 [M, 8] or [8] rows that `over` is judged against; None: the level's own row, and with maps=None the handle's
+        start statistics, so that `over` is what the episode would report (max_changes / max_iterations aside).
+        A pure function like evaluate(): episodes, random streams and pending asynchronous searches are not touched, a tile id >=
+        get_num_tiles() is clamped on the way and reported by check_status(); the workspace is evaluate()'s (the same one-stream rule).
+        Which form runs where: the library's one call (pcgrl_get_changes: every level staged once, no-op entries not computed) wherever
+        evaluate() has its fast form -- binary, zelda, and the compact searches of sokoban, mdungeon and ddave, maps up to 64 x 64 --
+        and M * K * T + M below 2^31.  Elsewhere (smb, larger maps, the general searches, more entries, and a handle that waits for a
+        reset() after an adjust_param() it could not take in place) the changed levels are built `chunk` entries at a time with
+        torch indexing on the device and scored through evaluate(..., ref=...): the same result wherever evaluate() works; a device
+        cell outside the map is clamped there too but not reported."""
+        torch = self._torch
+        own = maps is None
+        if own and (self._handle is None or not self._was_reset or self._needs_reset):
+            raise RuntimeError("changes() without maps reads the environment's current levels: call reset() first")
+        self._scoring_handle()
+        stale = self._realloc
+        w, h = self._alloc_dims
+        m = self._bufs["map"] if own else self._as_maps("changes", maps)
+        M, T, ncell = int(m.shape[0]), self.get_num_tiles(), h * w
+        if isinstance(cells, str):
+            if cells != "cursor":
+                raise ValueError("changes(): cells must be an array, None or \"cursor\", got %r" % (cells,))
+            if self._rep.name == "wide":
+                raise ValueError("changes(cells=\"cursor\"): the wide representation has no cursor")
+            if not own:
+                raise ValueError("changes(cells=\"cursor\") reads the environment's own cursors: leave maps=None")
+            pos = self._bufs["pos"]
+            c = (pos[:, 1].to(torch.int32) * w + pos[:, 0].to(torch.int32)).view(M, 1).contiguous()
+        elif cells is None:
+            c = None
+        else:
+            on_device = torch.is_tensor(cells) and cells.is_cuda
+            c = cells if torch.is_tensor(cells) else torch.as_tensor(np.asarray(cells))
+            if c.dtype not in (torch.int32, torch.int64, torch.int16, torch.int8, torch.uint8) or c.dim() not in (1, 2) or c.numel() < 1 or \
+                    (c.dim() == 2 and c.shape[0] != M):
+                raise ValueError("changes(): cells must be integers of shape [%d, K] or [K] with K >= 1, got %s %s" % (M, c.dtype, tuple(c.shape)))
+            if not on_device and (int(c.min()) < 0 or int(c.max()) >= ncell):
+                raise ValueError("changes(): a cell outside [0, %d) for maps of %d rows x %d columns" % (ncell, h, w))
+            c = c.to(device=self.device, dtype=torch.int32)
+            c = (c.expand(M, c.shape[0]) if c.dim() == 1 else c).contiguous()
+        K = ncell if c is None else int(c.shape[1])
+        if start is None:
+            s = self._bufs["start_stats"] if own else None
+        else:
+            s = start if torch.is_tensor(start) else torch.as_tensor(np.asarray(start))
+            if s.dtype not in (torch.int32, torch.int64) or tuple(s.shape) not in ((8,), (M, 8)):
+                raise ValueError("changes(): start must be int32 rows of shape [%d, 8] or [8], got %s %s" % (M, s.dtype, tuple(s.shape)))
+            s = s.to(device=self.device, dtype=torch.int32)
+            s = (s.expand(M, 8) if s.dim() == 1 else s).contiguous()
+        cfg = self._config(self._alloc_dims)
+        need = 0 if stale else int(self._lib.pcgrl_get_changes_bytes(C.byref(cfg), M, K))
+        if not need:
+            return self._changes_by_evaluate(m, c, s, bool(rows), max(1, int(chunk)))
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        out_rows = torch.empty((M, K, T, 8), dtype=torch.int32, device=self.device) if rows else None
+        reward = torch.empty((M, K, T), dtype=torch.float64, device=self.device)
+        over = torch.empty((M, K, T), dtype=torch.uint8, device=self.device)
+        base = torch.empty((M, 8), dtype=torch.int32, device=self.device)
+        _lib.check(self._lib.pcgrl_get_changes(self._handle, ptr(m), M, ptr(c), K, ptr(s), ptr(base), ptr(out_rows), ptr(reward), ptr(over),
+                                               *self._workspace(need), self._stream()), "pcgrl_get_changes")
+        if c is None:
+            c = torch.arange(ncell, dtype=torch.int32, device=self.device).expand(M, ncell)
+        return Changes(out_rows, reward, over.view(torch.bool), base, c, self._prob.decode_rows(base))
+
+    def _changes_by_evaluate(self, m, c, s, want_rows, chunk):
+        """changes() where pcgrl_get_changes_bytes is 0: the entries in their order (m, k, t), `chunk` at a time -- each chunk's levels
+        are copies of their level with the one byte written by torch indexing -- through evaluate(levels, ref=the level's own row);
+        the no-op entries come out as the level's own row, their reward is set to 0; `over` against other start rows: pcgrl_get_reward
+        on the chunk's rows."""
+        torch = self._torch
+        M, T = int(m.shape[0]), self.get_num_tiles()
+        w, h = self._alloc_dims
+        ncell = h * w
+        base = self.evaluate(m, chunk=chunk).rows
+        if c is None:
+            c = torch.arange(ncell, dtype=torch.int32, device=self.device).expand(M, ncell)
+        K = int(c.shape[1])
+        cc = c.clamp(0, ncell - 1).to(torch.int64)
+        flat = m.reshape(M, ncell)
+        E = M * K * T
+        rows = torch.empty((E, 8), dtype=torch.int32, device=self.device) if want_rows else None
+        reward = torch.empty((E,), dtype=torch.float64, device=self.device)
+        over = torch.empty((E,), dtype=torch.uint8, device=self.device)
+        for i in range(0, E, chunk):
+            n = min(chunk, E - i)
+            levels, lv, noop = expand_changes(flat, cc, i, n, T)
+            ev = self.evaluate(levels.view(n, h, w), ref=base[lv], chunk=chunk)
+            if want_rows:
+                rows[i:i + n] = ev.rows
+            reward[i:i + n] = ev.reward.masked_fill(noop, 0.0)
+            if s is None:
+                over[i:i + n] = ev.over
+            else:
+                scorer = self._eval_scratch._handle if self._realloc else self._handle
+                ref = s[lv].contiguous()
+                _lib.check(self._lib.pcgrl_get_reward(scorer, C.c_void_p(ev.rows.data_ptr()), C.c_void_p(ref.data_ptr()), n, None,
+                                                      C.c_void_p(over[i:i + n].data_ptr()), self._stream()), "pcgrl_get_reward")
+        return Changes(rows.view(M, K, T, 8) if want_rows else None, reward.view(M, K, T), over.view(torch.bool).view(M, K, T), base, c,
+                       self._prob.decode_rows(base))
 
     def _evaluate_by_set_maps(self, m, rows, chunk):
         """evaluate() where pcgrl_get_stats_bytes is 0: a scratch environment of this problem (wide representation, the same

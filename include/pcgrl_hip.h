@@ -55,7 +55,9 @@ extern "C" {
  *     pcgrl_get_playthrough.
  *     Still 15: + pcgrl_get_smb_play_bytes / pcgrl_get_smb_play -- additive in the same way; detected by the symbol pcgrl_get_smb_play.
  *     Still 15: + pcgrl_get_paths_legs / pcgrl_get_paths_bytes / pcgrl_get_paths -- additive in the same way; detected by the symbol
- *     pcgrl_get_paths. */
+ *     pcgrl_get_paths.
+ *     Still 15: + pcgrl_get_changes_bytes / pcgrl_get_changes -- additive in the same way; detected by the symbol pcgrl_get_changes.
+ *     The developer switches pcgrl_tuning grew at their end (changes_grid, changes_chunk): fill them with pcgrl_tuning_defaults. */
 #define PCGRL_ABI_VERSION 15
 #define PCGRL_OK 0
 #define PCGRL_EINVAL (-1)   /* bad argument / unsupported configuration */
@@ -170,6 +172,9 @@ typedef struct pcgrl_tuning {
     int32_t touch_resume;    /* k_step, binary, maps of at most 16 x 32: 0 = a change to the champion that binary_touch gives up on is computed
                                 from scratch; default 1 = the computation resumes from what the touch found (csrc/pcgrl_algos.h rlp_resume).
                                 Wider maps (64-bit row masks) and the two-launch pipeline, which has no touch, always compute from scratch */
+    int32_t changes_grid;    /* pcgrl_get_changes: blocks of k_get_changes at most (default 8192; tests: 1 = one block walks every item) */
+    int32_t changes_chunk;   /* pcgrl_get_changes: cells of a level per work item (default: chosen from count and ncells, csrc/pcgrl_abi.hip
+                                changes_chunk) */
 } pcgrl_tuning;
 
 int pcgrl_abi_version(void);
@@ -440,6 +445,36 @@ size_t pcgrl_get_paths_bytes(const pcgrl_config* cfg, int32_t count, int32_t max
 int    pcgrl_get_paths(pcgrl_env* env, const uint8_t* maps, int32_t count, int32_t max_len,
                        int16_t* cells_out, int32_t* length_out, int32_t* rows_out,
                        void* work, size_t work_bytes, void* stream);
+/* ---- Every one-cell change of a level: what a representation's action (narrow_rep.py:99-114, wide_rep.py:67-70, turtle_rep.py:101-129)
+ * or a mutation would do to the statistics, and what the step that makes it would pay.  For each of `count` levels and each of its
+ * `ncells` listed cells, entry (m, k, t) is the level m with cell k set to tile t, for every tile t of the problem (T of them):
+ *   rows     Problem.get_stats of that level;
+ *   reward   Problem.get_reward(new = that row, old = the level's own row);
+ *   over     Problem.get_episode_over(new = that row, start), `start` being start_rows[m] or, without, the level's own row.
+ * The entry of the tile the cell already holds changes nothing: it is the level's own row with reward 0 and is not computed again.
+ *   maps           DEVICE u8 [count,H,W], read only.  A tile id >= T is clamped in the staged copy and reported (status bit 2), as in
+ *                  pcgrl_get_stats; the no-op entry of such a cell is the one of tile T - 1.
+ *   cells          DEVICE i32 [count,ncells], a cell being y * W + x, or NULL = every cell in row-major order (ncells must then be H * W).
+ *                  Cells may repeat.  A cell outside [0, H*W) is clamped into the range and reported like an action outside the action
+ *                  space (status bit 1).
+ *   start_rows     DEVICE i32 [count,8] or NULL: the start statistics `over` is judged against (NULL: the level's own row).
+ *   base_rows_out  DEVICE i32 [count,8] or NULL: exactly what pcgrl_get_stats writes for these maps.
+ *   rows_out       DEVICE i32 [count,ncells,T,8] or NULL, each row packed like pcgrl_get_stats' rows.
+ *   reward_out     DEVICE f64 [count,ncells,T] or NULL;  over_out  DEVICE u8 [count,ncells,T] or NULL.  At least one of rows_out, reward_out
+ *                  and over_out is needed.
+ *   work           DEVICE, 256-byte aligned, at least pcgrl_get_changes_bytes(cfg, count, ncells) bytes; the call's own.
+ * Same contract as pcgrl_get_stats: a bound handle, no reset needed, no episode state read or written, of the handle only the sticky
+ * status word written; asynchronous on the stream, nothing is cleared with a memset and nothing waited for.
+ *   PCGRL_EINVAL: a NULL maps or work, no output, count < 1, ncells < 1, NULL cells with ncells != H * W, work not 256-byte aligned or too
+ *   small, or a configuration for which pcgrl_get_changes_bytes is 0.  PCGRL_ESTATE before pcgrl_bind.
+ * pcgrl_get_changes_bytes: from the configuration alone.  Non-zero (then >= 256) exactly where pcgrl_get_stats_bytes(cfg, count) is, with
+ *   count >= 1, ncells >= 1 and count * ncells * T + count <= 2^31 - 1: an entry's index, and the search problems' job list -- the entries,
+ *   then the levels -- are 32-bit.  Beyond that bound it is 0: split the call. */
+size_t pcgrl_get_changes_bytes(const pcgrl_config* cfg, int32_t count, int32_t ncells);
+int    pcgrl_get_changes(pcgrl_env* env, const uint8_t* maps, int32_t count,
+                         const int32_t* cells, int32_t ncells, const int32_t* start_rows,
+                         int32_t* base_rows_out, int32_t* rows_out, double* reward_out, uint8_t* over_out,
+                         void* work, size_t work_bytes, void* stream);
 /* ActionMap.step for the wide representation (wrappers.py:139-154): flat DEVICE i32 [N] index into
  * (H, W, tiles) -> xyv DEVICE i32 [N,3] = (x, y, tile), the action pcgrl_step takes. */
 int pcgrl_action_map(pcgrl_env* env, const int32_t* flat, int32_t* xyv, void* stream);

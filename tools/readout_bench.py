@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Levels/s of the level read-outs of BatchedPcgrlEnv -- evaluate() (pcgrl_get_stats), solve() (pcgrl_get_solution), playthrough()
-(pcgrl_get_playthrough), playthrough_smb() (pcgrl_get_smb_play) and paths() (pcgrl_get_paths) -- each next to the route it is compared
-with, on the GPU box.  One method: wall clock around the call with a device synchronisation, after a warm-up of each call (the handle,
+(pcgrl_get_playthrough), playthrough_smb() (pcgrl_get_smb_play), paths() (pcgrl_get_paths) and changes() (pcgrl_get_changes) -- each next
+to the route it is compared with, on the GPU box.  One method: wall clock around the call with a device synchronisation, after a warm-up of each call (the handle,
 the workspace, the kernels' code objects, the allocator's blocks); a call is a few ms and the box is shared, so the calls of a case run in
 ONE process on one handle, alternating, `rounds` rounds: minimum, median and maximum of each.  Every case runs in a child process of its
 own under a time limit, so that a hang ends there; a child that fails ends the session.  One JSON line at the end.
@@ -11,6 +11,7 @@ own under a time limit, so that a hang ends there; a child that fails ends the s
     python tools/readout_bench.py playthrough [--prob mdungeon|ddave] [M]   (default: mdungeon, 65536)
     python tools/readout_bench.py smb_play [M] [max_len]             (default: 4096 maps, max_len 255)
     python tools/readout_bench.py paths [M14 [M11x16 [M64]]]         (defaults: 65536 65536 4096)
+    python tools/readout_bench.py changes [Mbinary [Mzelda [Msokoban [M16x40]]]]   (defaults: 1024 each)
 
 evaluate: evaluate() next to the route there was before it -- a handle of M environments: reset(); set_maps(maps); stats -- three runs
 of each; the handle route is timed with and without building the handle (allocation + seeding + reset), which that route needs once per
@@ -19,7 +20,10 @@ and on a handle's own levels (M environments after a reset, the map buffer read 
 to evaluate() (for smb the scratch-environment route: set_maps() of a private environment, that is k_smb) on the 14 x 114 levels of
 tests/golden/stats_smb_14x114_p1500.npz tiled to M maps, 20 rounds.  paths: paths() with the default max_len (H * W: every leg whole) and
 with max_len 64 (the rows a drawing loop of short legs would ask for) next to evaluate(), binary 14 x 14, zelda 11 x 16, binary 64 x 64,
-30 rounds.  The statistics rows of the calls of a case must agree.
+30 rounds.  changes: changes() on M levels with all cells next to evaluate(stack, ref=...) on the materialised M * H * W * T stack of the
+same entries (built once, outside the clock: the yardstick gets its input for nothing), binary 14 x 14, zelda 7 x 11, sokoban 5 x 5 and
+binary 16 x 40 (64-bit row masks on sixteen rows: the shape at which changes() takes a wavefront a level where evaluate() takes four), 30
+rounds; the reported "levels" are entries.  The statistics rows of the calls of a case must agree.
 """
 import argparse
 import json
@@ -185,6 +189,27 @@ def paths_child(prob, h, w, m):
     return out
 
 
+def changes_child(prob, h, w, m):
+    import torch
+    from gym_pcgrl_amd.envs.batched_env import expand_changes
+    maps = device_maps(levels(prob, m, h, w))
+    env = make_env(prob, (h, w))
+    T = env.get_num_tiles()
+    entries = m * h * w * T
+    cells = torch.arange(h * w, device=maps.device).expand(m, h * w)
+    stack, lv, noop = expand_changes(maps.view(m, h * w), cells, 0, entries, T)
+    stack = stack.view(entries, h, w)
+    ref = env.evaluate(maps).rows[lv].contiguous()
+    out = {"prob": prob, "h": h, "w": w, "levels": m, "M": entries, "noop": int(noop.sum().item())}
+    out["s"], last = alternate({"evaluate": lambda: env.evaluate(stack, ref=ref), "changes": lambda: env.changes(maps)}, 30)
+    ev, ch = last["evaluate"], last["changes"]
+    assert torch.equal(ch.rows.view(-1, 8), ev.rows) and torch.equal(ch.reward.view(-1), ev.reward.masked_fill(noop, 0.0)) and torch.equal(ch.over.view(-1), ev.over), \
+        "changes() and evaluate() of the materialised stack disagree"
+    out["checksum"] = {"evaluate": checksum(env, ev.rows), "changes": checksum(env, ch.rows.view(-1, 8))}
+    assert env.check_status() == 0
+    return out
+
+
 # ---- the subcommands: arguments -> cases (label, child arguments); a note behind a call's report line; the results -> the JSON
 def moves_note(r, k):
     if k == "evaluate":
@@ -211,7 +236,7 @@ def evaluate_final(res):
 
 def paths_final(res):
     for r in res:
-        assert len(set(r["checksum"].values())) == 1, "paths() and evaluate() disagree on the statistics rows"
+        assert len(set(r["checksum"].values())) == 1, "the calls of the case disagree on the statistics rows"
     return res
 
 
@@ -225,6 +250,8 @@ def arguments(p, sub):
     if sub == "evaluate":
         p.add_argument("m", nargs="?", type=int, default=65536, metavar="M")
         p.add_argument("probs", nargs="*", metavar="problem", help="of %s" % ", ".join(sorted(EVALUATE_SHAPES)))
+    elif sub == "changes":
+        p.add_argument("ms", nargs="*", type=int, default=[], metavar="M", help="levels of binary 14 x 14, zelda 7 x 11, sokoban 5 x 5, binary 16 x 40 (1024 each)")
     elif sub == "paths":
         p.add_argument("ms", nargs="*", type=int, default=[], metavar="M", help="levels of binary 14 x 14, zelda 11 x 16, binary 64 x 64 (65536 65536 4096)")
     else:
@@ -247,6 +274,9 @@ SPECS = {
                   note=lambda r, k: "" if k == "evaluate" else "   legs %s, %d cells, longest %d, %.1f MB of rows" % (r["legs"], r["cells"], r["longest"], r["bytes_cells"][k] / 1e6),
                   cases=lambda a: [("%s %dx%d" % (prob, h, w), (prob, h, w, m))
                                    for (prob, h, w), m in zip((("binary", 14, 14), ("zelda", 11, 16), ("binary", 64, 64)), a.ms + [65536, 65536, 4096][len(a.ms):])]),
+    "changes": dict(child=changes_child, final=paths_final, note=lambda r, k: "   %d levels, %d no-op entries" % (r["levels"], r["noop"]),
+                    cases=lambda a: [("%s %dx%d" % (prob, h, w), (prob, h, w, m))
+                                     for (prob, h, w), m in zip((("binary", 14, 14), ("zelda", 7, 11), ("sokoban", 5, 5), ("binary", 16, 40)), a.ms + [1024, 1024, 1024, 1024][len(a.ms):])]),
 }
 
 
