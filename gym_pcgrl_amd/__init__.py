@@ -435,5 +435,7 @@ def replay_smb(level, moves):
                      bool(x >= exit_x), bool(y >= H), int(exit_x - x))
 
 
+from . import helper  # noqa: E402,F401  (gym_pcgrl/envs/helper.py on the device for any tile set: gym_pcgrl_amd.helper.calc_num_regions(maps, tiles), ...)
+
 register_with_gym()      # no-op without a gym of the reference's era (none is on the MI355X image)
 register_with_gymnasium()   # likewise for gymnasium / gym >= 0.26 (five-tuple adapter)

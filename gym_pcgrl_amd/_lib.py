@@ -84,7 +84,14 @@ class RenderDesc(C.Structure):
                 ("grid_rows", C.c_int32), ("grid_cols", C.c_int32), ("out", C.c_void_p)]
 
 
-ABI_VERSION = 15         # include/pcgrl_hip.h PCGRL_ABI_VERSION (pcgrl_bind_row, pcgrl_render, pcgrl_get_stats, pcgrl_get_solution, pcgrl_get_playthrough, pcgrl_get_smb_play, pcgrl_get_paths, pcgrl_get_changes are additions within 15: found by their symbols)
+# include/pcgrl_hip.h pcgrl_tile_graph_desc: what pcgrl_tile_graph reads and writes (device pointers; an output None = not wanted)
+class TileGraphDesc(C.Structure):
+    _fields_ = [("maps", C.c_void_p), ("count", C.c_int32), ("passable", C.c_uint32), ("source_tiles", C.c_uint32), ("reach_tiles", C.c_uint32),
+                ("sources", C.c_void_p), ("regions_out", C.c_void_p), ("longest_out", C.c_void_p), ("labels_out", C.c_void_p),
+                ("dist_out", C.c_void_p), ("reach_out", C.c_void_p), ("source_out", C.c_void_p)]
+
+
+ABI_VERSION = 15         # include/pcgrl_hip.h PCGRL_ABI_VERSION (pcgrl_bind_row, pcgrl_render, pcgrl_get_stats, pcgrl_get_solution, pcgrl_get_playthrough, pcgrl_get_smb_play, pcgrl_get_paths, pcgrl_get_changes, pcgrl_tile_graph are additions within 15: found by their symbols)
 EXPORTS = ("pcgrl_abi_version", "pcgrl_error_string", "pcgrl_last_hip_error", "pcgrl_query_layout", "pcgrl_create",
            "pcgrl_destroy", "pcgrl_bind", "pcgrl_configure", "pcgrl_seed", "pcgrl_set_tile_probs", "pcgrl_reset",
            "pcgrl_step", "pcgrl_set_maps", "pcgrl_observe", "pcgrl_action_map", "pcgrl_status", "pcgrl_profile",
@@ -94,7 +101,7 @@ EXPORTS = ("pcgrl_abi_version", "pcgrl_error_string", "pcgrl_last_hip_error", "p
            "pcgrl_bind_row", "pcgrl_render", "pcgrl_get_stats_bytes", "pcgrl_get_stats", "pcgrl_get_reward",
            "pcgrl_get_solution_bytes", "pcgrl_get_solution", "pcgrl_get_playthrough_bytes", "pcgrl_get_playthrough",
            "pcgrl_get_smb_play_bytes", "pcgrl_get_smb_play", "pcgrl_get_paths_legs", "pcgrl_get_paths_bytes", "pcgrl_get_paths",
-           "pcgrl_get_changes_bytes", "pcgrl_get_changes")
+           "pcgrl_get_changes_bytes", "pcgrl_get_changes", "pcgrl_tile_graph_bytes", "pcgrl_tile_graph")
 NPHASE = 6
 # the six intervals between the seven event marks of a step; sokoban: update, stats, reset, solver, reset2, solver2;
 # other problems: update, stats(+resets), -, reset (only with PCGRL_INLINE_RESET=0), -, -
@@ -226,6 +233,10 @@ def load():
     # handle, maps, count, cells, ncells, start_rows, base_rows, rows, reward, over, work, work_bytes, stream
     L.pcgrl_get_changes.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_size_t, C.c_void_p]
+    L.pcgrl_tile_graph_bytes.argtypes = [C.POINTER(Config), C.c_int32]
+    L.pcgrl_tile_graph_bytes.restype = C.c_size_t
+    # handle, desc, work, work_bytes, stream
+    L.pcgrl_tile_graph.argtypes = [C.c_void_p, C.POINTER(TileGraphDesc), C.c_void_p, C.c_size_t, C.c_void_p]
     L.pcgrl_action_map.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pcgrl_step_flat.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pcgrl_selftest_heap.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

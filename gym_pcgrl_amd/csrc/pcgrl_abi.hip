@@ -87,6 +87,7 @@
 #include "kernels_evaluate.h"
 #include "kernels_changes.h"      // (after kernels_evaluate.h: eval_stage_map, the job source of k_get_stats_search)
 #include "kernels_paths.h"
+#include "kernels_tile_graph.h"
 #include "kernels_moves.h"
 #include "kernels_smb_play.h"     // (after kernels_moves.h: SolOut)
 #include "search_big.h"
@@ -634,6 +635,7 @@ PCGRL_LOCAL int launch_step_solver(pcgrl_env* h, const int32_t* actions, hipStre
 PCGRL_LOCAL int launch_get_stats(pcgrl_env* h, const uint8_t* maps, int count, int32_t* rows_out, int32_t* head, int32_t* jobs, hipStream_t st);
 PCGRL_LOCAL int launch_get_stats_search(pcgrl_env* h, const uint8_t* maps, int32_t* rows_out, int32_t* head, const int32_t* jobs, SokNode* pools, int blocks, hipStream_t st);
 PCGRL_LOCAL int launch_get_paths(pcgrl_env* h, const uint8_t* maps, int count, int max_len, int16_t* cells_out, int32_t* length_out, int32_t* rows_out, hipStream_t st);
+PCGRL_LOCAL int launch_tile_graph(pcgrl_env* h, const pcgrl_tile_graph_desc& D, hipStream_t st);
 struct ChangesArgs {      // pcgrl_get_changes' arguments as its launches take them; chunk / nchunks / grid_cap: the host's cut into work items
     const uint8_t* maps; int count; const int32_t* cells; int ncells; const int32_t* start_rows;
     int32_t* base_rows; int32_t* rows; double* reward; uint8_t* over;
@@ -811,6 +813,14 @@ PCGRL_LOCAL int launch_get_paths(pcgrl_env* h, const uint8_t* maps, int count, i
         return with_lanes(P.group, P.mask_bytes, [&](auto g, auto m) {
             return launch<k_get_paths<PROB, g(), type_of<decltype(m)>>>(h, G.grid, PCGRL_BLOCK, G.lds, st, P, maps, count, max_len, cells_out, length_out, rows_out, h->B.status);
         });
+    });
+}
+// pcgrl_tile_graph (kernels_tile_graph.h): launch_get_stats' grid and stage, whatever the problem
+PCGRL_LOCAL int launch_tile_graph(pcgrl_env* h, const pcgrl_tile_graph_desc& D, hipStream_t st) {
+    const PcgrlParams& P = h->P;
+    const MapGrid G = map_grid(P, D.count);
+    return with_lanes(P.group, P.mask_bytes, [&](auto g, auto m) {
+        return launch<k_tile_graph<g(), type_of<decltype(m)>>>(h, G.grid, PCGRL_BLOCK, G.lds, st, P, D, h->B.status);
     });
 }
 // pcgrl_get_changes, first launch (kernels_changes.h): launch_get_stats' stage and grid over the (level, chunk of cells) items
@@ -1956,6 +1966,29 @@ int pcgrl_get_paths(pcgrl_env* h, const uint8_t* maps, int32_t count, int32_t ma
     if (int rc = readout_check(h, maps && cells_out && length_out, count, max_len, work, work_bytes, h ? pcgrl_get_paths_bytes(&h->cfg, count, max_len) : 0)) return rc;
     DeviceGuard guard(h->device);
     return launch_get_paths(h, maps, count, max_len, cells_out, length_out, rows_out, (hipStream_t)stream);
+}
+
+// ---- pcgrl_tile_graph (kernels_tile_graph.h, tile_graph.h): helper.py:170-296 for any tile set ---------------------------------------
+// The workspace, cut from one plan like pcgrl_get_paths': the label and distance planes live in registers, nothing is needed per map,
+// so the plan is the head every such call has.
+struct TileGraphPlan { Region head; size_t total; };
+static TileGraphPlan tile_graph_plan(const pcgrl_config*, int) {
+    TileGraphPlan S = {};
+    Bump b = {0};
+    S.head = b.take(256);
+    S.total = b.off;
+    return S;
+}
+size_t pcgrl_tile_graph_bytes(const pcgrl_config* c, int32_t count) {
+    pcgrl_config one;
+    if (!c || count < 1 || c->prob == PCGRL_SMB || !one_env(c, &one) || big_map(&one)) return 0;
+    return tile_graph_plan(&one, count).total;
+}
+int pcgrl_tile_graph(pcgrl_env* h, const pcgrl_tile_graph_desc* d, void* work, size_t work_bytes, void* stream) {
+    const bool ptrs = d && d->maps && (d->regions_out || d->longest_out || d->labels_out || d->dist_out || d->reach_out || d->source_out);
+    if (int rc = readout_check(h, ptrs, d ? d->count : 0, 1, work, work_bytes, h && d ? pcgrl_tile_graph_bytes(&h->cfg, d->count) : 0)) return rc;
+    DeviceGuard guard(h->device);
+    return launch_tile_graph(h, *d, (hipStream_t)stream);
 }
 
 }  // extern "C"

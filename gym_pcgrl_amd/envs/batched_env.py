@@ -130,6 +130,17 @@ class Changes:
         self.rows, self.reward, self.over, self.base_rows, self.cells, self.stats = rows, reward, over, base_rows, cells, stats
 
 
+class Connectivity:
+    """What BatchedPcgrlEnv.connectivity() returns, all on the device, None where not asked for: `regions` int32 [M] (calc_num_regions),
+    `longest` int32 [M] (calc_longest_path), `labels` int16 [M, H, W] (calc_num_regions' color_map: -1 on impassable cells, else 1 ..
+    regions in the row-major order of the regions' first cells), `dist` int16 [M, H, W] (run_dikjstra's map from the source, -1 where
+    unreached), `reach` int32 [M] (calc_num_reachable_tile), `source` int32 [M] (the source cell that was used, y * W + x, -1: none)."""
+    __slots__ = ("regions", "longest", "labels", "dist", "reach", "source")
+
+    def __init__(self, regions, longest, labels, dist, reach, source):
+        self.regions, self.longest, self.labels, self.dist, self.reach, self.source = regions, longest, labels, dist, reach, source
+
+
 def expand_changes(flat, cells, first, n, ntiles):
     """The expansion rule of changes(): entries `first` .. `first + n - 1` in the order (m, k, t) -- entry (m * K + k) * T + t is level m
     with cell cells[m, k] set to tile t -- of `flat` uint8 [M, H * W] and `cells` int64 [M, K] (torch tensors on one device, the CPU
@@ -806,9 +817,10 @@ class BatchedPcgrlEnv:
         return C.c_void_p(self._eval_work.data_ptr()), self._eval_work.numel()
 
     def _readout(self, who, verb, bytes_fn, no_form_message, maps, max_len, default_len):
-        """solve(), playthrough(), playthrough_smb() and paths() behind their problem checks, up to their outputs: the levels `m` ([M,
-        H, W]: `maps`, or (None) the handle's own map buffer), `max_len` (None: `default_len(w, h)`) and the workspace
-        `bytes_fn` asks for, as (m, M, max_len, work).  `no_form_message(w, h)`: the text where `bytes_fn` gives 0."""
+        """solve(), playthrough(), playthrough_smb(), paths() and connectivity() behind their problem checks, up to their outputs: the
+        levels `m` ([M, H, W]: `maps`, or (None) the handle's own map buffer), `max_len` (None: `default_len(w, h)`) and the workspace
+        `bytes_fn` asks for, as (m, M, max_len, work).  `no_form_message(w, h)`: the text where `bytes_fn` gives 0.  default_len None:
+        the call has no rows of a length -- `bytes_fn` takes the configuration and M, max_len stays None."""
         if maps is None:
             if self._handle is None or not self._was_reset or self._needs_reset:
                 raise RuntimeError("%s() without maps reads the environment's current levels: call reset() first" % who)
@@ -819,11 +831,12 @@ class BatchedPcgrlEnv:
         w, h = self._alloc_dims
         m = self._bufs["map"] if maps is None else self._as_maps(who, maps)
         M = int(m.shape[0])
-        max_len = default_len(w, h) if max_len is None else int(max_len)
-        if max_len < 1:
-            raise ValueError("%s(): max_len must be at least 1, got %d" % (who, max_len))
+        if default_len is not None:
+            max_len = default_len(w, h) if max_len is None else int(max_len)
+            if max_len < 1:
+                raise ValueError("%s(): max_len must be at least 1, got %d" % (who, max_len))
         cfg = self._config(self._alloc_dims)
-        need = int(getattr(self._lib, bytes_fn)(C.byref(cfg), M, max_len))
+        need = int(getattr(self._lib, bytes_fn)(C.byref(cfg), M, *(() if default_len is None else (max_len,))))
         if not need:
             raise NotImplementedError(no_form_message(w, h))
         return m, M, max_len, self._workspace(need)
@@ -931,6 +944,52 @@ class BatchedPcgrlEnv:
                                              C.c_void_p(length.data_ptr()), C.c_void_p(rows.data_ptr()),
                                              *work, self._stream()), "pcgrl_get_paths")
         return Paths(cells, length, rows, self._prob.decode_rows(rows), legs, self._alloc_dims[0])
+
+    # ---- helper.py for any tile set: regions, longest path, labels, distance map, reachable tiles (pcgrl_tile_graph)
+    def connectivity(self, maps=None, passable=(), source=None, reach=None, labels=False, dist=False, scalars=True):
+        """gym_pcgrl/envs/helper.py (helper.py:170-296) on the device for `maps` -- array-like uint8 [M, H, W] as for evaluate(), of any
+        tile values 0..31 whatever this environment's problem; None: this environment's current levels (after a reset(); the handle's
+        own map buffer is read in place).  `passable`: the tiles one can walk on -- ints, or this problem's tile names, one or a list.
+        Returns a Connectivity (regions, longest, labels, dist, reach, source), None where not asked for:
+        `regions` / `longest` (scalars=True) calc_num_regions / calc_longest_path; `labels` (labels=True) calc_num_regions' color_map;
+        `dist` (dist=True) run_dikjstra's map from the source; `reach` (`reach`: tiles like `passable`) calc_num_reachable_tile;
+        `source` (with a `source`) the cell that was used.
+        `source`: None; an int cell y * W + x (-1: none); a tensor / array [M] of cells; a tuple (x, y) of ints or tensors [M]; or a
+        tile name, or a LIST of tiles: the first cell in row-major order that holds one of them.  Host ints are range-checked; a cell
+        of a tensor outside the map counts as none and is reported by check_status() like an action outside the action space.
+        A tile argument is a set, not the reference's list: the rule, and where `longest` and the label numbering deviate from a
+        reference call with several passable values, is in include/pcgrl_hip.h (pcgrl_tile_graph) and gym_pcgrl_amd/helper.py.
+        A pure function like evaluate(): episodes, random streams and pending asynchronous searches are not touched, a byte >= 32 is
+        in no set and reported by check_status(), nothing is waited for; the workspace is evaluate()'s (the same one-stream rule).
+        NotImplementedError where the library has no form: maps beyond 64 x 64, smb."""
+        from ..helper import source_arg, tile_set
+        torch = self._torch
+        names = self._prob.get_tile_types()
+        pass_set = tile_set(passable, names, "passable")
+        reach_set = tile_set(reach, names, "reach")
+        m, M, _, work = self._readout("connectivity", "reads levels", "pcgrl_tile_graph_bytes", lambda w, h: (
+            "connectivity(): no form for this configuration (problem %r, maps of %d rows x %d columns): "
+            "the row-bitboard kernel takes maps up to 64 x 64 and not smb's" % (self._prob.name, h, w)), maps, None, None)
+        w, h = self._alloc_dims
+        kind, src = source_arg(source, w, h, names)
+        if (dist or reach is not None) and kind == "none":
+            raise ValueError("connectivity(): dist and reach are measured from a source: pass source=")
+        if not (scalars or labels or dist or reach is not None or kind != "none"):
+            raise ValueError("connectivity(): nothing was asked for")
+        cells = None
+        if kind == "cells":
+            c = src if torch.is_tensor(src) else torch.as_tensor(np.asarray(src))
+            if c.dtype not in (torch.int32, torch.int64, torch.int16, torch.int8, torch.uint8) or c.dim() > 1 or (c.dim() == 1 and c.shape[0] != M):
+                raise ValueError("connectivity(): source cells must be integers, one or [%d], got %s %s" % (M, c.dtype, tuple(c.shape)))
+            cells = c.to(device=self.device, dtype=torch.int32).expand(M).contiguous()
+        new = lambda want, shape, dtype: torch.empty(shape, dtype=dtype, device=self.device) if want else None
+        out = Connectivity(new(scalars, (M,), torch.int32), new(scalars, (M,), torch.int32), new(labels, (M, h, w), torch.int16),
+                           new(dist, (M, h, w), torch.int16), new(reach is not None, (M,), torch.int32), new(kind != "none", (M,), torch.int32))
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        d = _lib.TileGraphDesc(ptr(m), M, pass_set, src if kind == "tiles" else 0, reach_set, ptr(cells), ptr(out.regions), ptr(out.longest),
+                               ptr(out.labels), ptr(out.dist), ptr(out.reach), ptr(out.source))
+        _lib.check(self._lib.pcgrl_tile_graph(self._handle, C.byref(d), *work, self._stream()), "pcgrl_tile_graph")
+        return out
 
     # ---- every one-cell change of a level: rows, reward and episode end (pcgrl_get_changes)
     def changes(self, maps=None, cells=None, start=None, rows=True, chunk=65536):

@@ -1,0 +1,189 @@
+"""gym_pcgrl/envs/helper.py on the device, for stacks of levels and any tile set: the functions a custom Problem builds its get_stats
+from, under the reference's names, over `maps` uint8 [M, H, W] (tile values 0..31) -- a torch tensor (results: torch tensors on the
+device) or a numpy array (results: numpy arrays).
+
+    from gym_pcgrl_amd import helper
+    regions = helper.calc_num_regions(maps, [0, 2])              # int32 [M]      helper.py:197-207
+    longest = helper.calc_longest_path(maps, [0, 2])             # int32 [M]      helper.py:250-264
+    dist, visited = helper.run_dikjstra(x, y, maps, [0, 2])      # int16 / bool [M, H, W]   helper.py:222-237; x, y ints or [M]
+    n = helper.calc_num_reachable_tile(maps, 2, [0, 2], [3, 4])  # int32 [M]      helper.py:288-296
+    labels = helper.label_regions(maps, [0, 2])                  # int16 [M, H, W]: calc_num_regions' color_map, which it throws away
+    k = helper.calc_certain_tile(maps, [3, 4])                   # int64 [M]      helper.py:272-273 (a torch sum, no kernel)
+    r = helper.get_range_reward(new, old, low, high)             # elementwise    helper.py:366-376
+
+The deviation from the reference: a tile argument is a SET, not a list.  The reference orders cells by the position of their tile
+in the list first and row-major second (_get_certain_tiles), so calc_longest_path starts its double sweep elsewhere in a component,
+and the color_map is numbered differently, for [0, 1] than for [1, 0].  Here every result is the reference's result on the level in
+which every passable tile has been renamed to one single value: a component's first sweep starts at its first cell in row-major
+order, regions are numbered 1, 2, ... by the row-major order of their first cell.  For a single passable value that is the reference
+exactly; for several, calc_num_regions, run_dikjstra and calc_num_reachable_tile are still exactly the reference's, while
+calc_longest_path and the label numbering are the merged-tile ones.  calc_num_reachable_tile takes the first cell of `start_value` in
+row-major order and counts nothing when there is none (the reference raises IndexError).
+
+The device functions are BatchedPcgrlEnv.connectivity() (C ABI: pcgrl_tile_graph) on a private one-environment handle per (device,
+H, W), made once, cached and closed at exit; maps up to 64 x 64.  Nothing is waited for on the torch route.
+"""
+import atexit
+
+import numpy as np
+
+_HANDLES = {}
+
+
+def tile_set(tiles, names=None, what="tiles"):
+    """`tiles` -- an int, a tile name of `names`, or a list / tuple / set of either; None: the empty set -- as a 32-bit set, bit t = tile t."""
+    if tiles is None:
+        return 0
+    if isinstance(tiles, (str, int, np.integer)):
+        tiles = [tiles]
+    if not hasattr(tiles, "__iter__"):
+        raise ValueError("%s: a tile, or a list of tiles, got %r" % (what, tiles))
+    mask = 0
+    for t in tiles:
+        if isinstance(t, str):
+            if names is None or t not in names:
+                raise ValueError("%s: unknown tile name %r (the problem's tiles: %s)" % (what, t, list(names) if names is not None else "none given"))
+            t = list(names).index(t)
+        elif not isinstance(t, (int, np.integer)) or isinstance(t, bool):
+            raise ValueError("%s: a tile is an int or a tile name, got %r" % (what, t))
+        if not 0 <= int(t) < 32:
+            raise ValueError("%s: tile %d outside 0..31" % (what, int(t)))
+        mask |= 1 << int(t)
+    return mask
+
+
+def source_arg(source, width, height, names=None):
+    """BatchedPcgrlEnv.connectivity()'s `source` as ("none", None), ("tiles", 32-bit set) or ("cells", c) with c = y * W + x as an int
+    or an integer array / tensor [M]: None; an int cell; an array / tensor [M] of cells (-1: none); a tuple (x, y) of ints or arrays /
+    tensors; a tile name, or a list of tiles (ints or names): the first cell in row-major order that holds one.  Host ints are
+    range-checked (ValueError); arrays and tensors are not: the device takes a cell outside the map as none and reports it."""
+    if source is None:
+        return "none", None
+    if isinstance(source, str) or isinstance(source, (list, set, frozenset)):
+        return "tiles", tile_set(source, names, "source")
+    if isinstance(source, tuple):
+        if len(source) != 2:
+            raise ValueError("source: a tuple is (x, y), got %d entries (a list names tiles)" % len(source))
+        x, y = source
+        if all(isinstance(v, (int, np.integer)) for v in (x, y)):
+            if not (0 <= int(x) < width and 0 <= int(y) < height):
+                raise ValueError("source: (x, y) = (%d, %d) outside a map of %d rows x %d columns" % (int(x), int(y), height, width))
+            return "cells", int(y) * width + int(x)
+        return "cells", y * width + x
+    if isinstance(source, (int, np.integer)):
+        if not -1 <= int(source) < width * height:
+            raise ValueError("source: cell %d outside [-1, %d)" % (int(source), width * height))
+        return "cells", int(source)
+    if hasattr(source, "shape"):
+        return "cells", source
+    raise ValueError("source: None, a cell, cells [M], (x, y), a tile name or a list of tiles -- got %r" % (source,))
+
+
+def _close_all():
+    for env in _HANDLES.values():
+        env.close()
+    _HANDLES.clear()
+
+
+def _handle(device, height, width):
+    """The private handle for levels of this size on this device: binary, wide, one environment -- only its device, size and lane-group
+    form matter to pcgrl_tile_graph."""
+    import torch
+    from .envs import BatchedPcgrlEnv
+    dev = torch.device("cuda:0" if device is None else device)
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    key = (dev.index, int(height), int(width))
+    env = _HANDLES.get(key)
+    if env is None:
+        if not _HANDLES:
+            atexit.register(_close_all)
+        env = BatchedPcgrlEnv(prob="binary", rep="wide", num_envs=1, device=dev, seed=0, auto_reset=False)
+        env.adjust_param(width=int(width), height=int(height))
+        _HANDLES[key] = env
+    return env
+
+
+def _connectivity(maps, **kw):
+    """connectivity() of the cached handle for `maps`; -> (the Connectivity, the conversion of a result for this kind of input)."""
+    import torch
+    shape = tuple(maps.shape) if hasattr(maps, "shape") else np.asarray(maps).shape
+    if len(shape) != 3:
+        raise ValueError("helper: maps must be [M, H, W], got shape %s" % (shape,))
+    on_host = not torch.is_tensor(maps)
+    device = maps.device if (not on_host and maps.is_cuda) else None
+    out = _handle(device, shape[1], shape[2]).connectivity(maps, **kw)
+    return out, (lambda t: t.cpu().numpy()) if on_host else (lambda t: t)
+
+
+def calc_num_regions(maps, passable_values):
+    """helper.py:197-207 for every level: int32 [M]."""
+    c, conv = _connectivity(maps, passable=passable_values)
+    return conv(c.regions)
+
+
+def calc_longest_path(maps, passable_values):
+    """helper.py:250-264 for every level under the set rule (module docstring): int32 [M]."""
+    c, conv = _connectivity(maps, passable=passable_values)
+    return conv(c.longest)
+
+
+def label_regions(maps, passable_values):
+    """The color_map of calc_num_regions (helper.py:197-207): int16 [M, H, W], -1 on impassable cells, else 1 .. regions in the
+    row-major order of the regions' first cells."""
+    c, conv = _connectivity(maps, passable=passable_values, labels=True, scalars=False)
+    return conv(c.labels)
+
+
+def run_dikjstra(x, y, maps, passable_values):
+    """helper.py:222-237 from (x, y) -- ints, or arrays / tensors [M] -- on every level: (dist int16 [M, H, W], -1 where unreached;
+    visited bool [M, H, W] = dist >= 0)."""
+    c, conv = _connectivity(maps, passable=passable_values, source=(x, y), dist=True, scalars=False)
+    return conv(c.dist), conv(c.dist >= 0)
+
+
+def calc_num_reachable_tile(maps, start_value, passable_values, reachable_values):
+    """helper.py:288-296 for every level: the cells of `reachable_values` that run_dikjstra reaches from the first cell of
+    `start_value` over `passable_values`: int32 [M] (0 without a start cell)."""
+    start = list(start_value) if isinstance(start_value, (list, tuple, set, frozenset)) else [start_value]      # (several values: a set, like the others)
+    c, conv = _connectivity(maps, passable=passable_values, source=start, reach=reachable_values, scalars=False)
+    return conv(c.reach)
+
+
+def calc_certain_tile(maps, tile_values):
+    """helper.py:272-273 for every level: the cells that hold one of `tile_values`, int64 [M].  A torch sum (numpy for a numpy input)."""
+    import torch
+    mask = tile_set(tile_values, None, "tile_values")
+    if not torch.is_tensor(maps):
+        m = np.asarray(maps)
+        return ((((mask >> np.minimum(m, 31).astype(np.int64)) & 1) == 1) & (m < 32)).reshape(m.shape[0], -1).sum(1).astype(np.int64)
+    m = maps.to(torch.int64)
+    return ((((mask >> m.clamp(max=31)) & 1) == 1) & (m < 32)).reshape(m.shape[0], -1).sum(1)
+
+
+_IPOS, _INEG = 2147483647, -2147483648      # csrc/pcgrl_algos.h PCGRL_IPOS / PCGRL_INEG: what stands for +-inf
+
+
+def _bound(torch, v, like):
+    """A band bound -- a number or a tensor, +-inf allowed -- as int64 with the kernels' stand-ins for +-inf."""
+    t = torch.as_tensor(v, device=like.device)
+    if t.is_floating_point():
+        t = t.to(torch.float64).clamp(min=float(_INEG), max=float(_IPOS))
+    return t.to(torch.int64)
+
+
+def get_range_reward(new_value, old_value, low, high):
+    """helper.py:366-376 elementwise on integer tensors (anything torch.as_tensor takes; broadcasting), by the integer rules the
+    kernels use (csrc/pcgrl_algos.h range_reward_i): statistics are integers, a bound is an integer or +-inf.  -> int64 tensor."""
+    import torch
+    nv = torch.as_tensor(new_value).to(torch.int64)
+    ov = torch.as_tensor(old_value, device=nv.device).to(torch.int64)
+    lo, hi = _bound(torch, low, nv), _bound(torch, high, nv)
+    nv, ov, lo, hi = torch.broadcast_tensors(nv, ov, lo, hi)
+    inside = (nv >= lo) & (nv <= hi) & (ov >= lo) & (ov <= hi)
+    below = (ov <= hi) & (nv <= hi)
+    above = (ov >= lo) & (nv >= lo)
+    r = torch.where((nv > hi) & (ov < lo), hi - nv + ov - lo, hi - ov + nv - lo)
+    r = torch.where(above, torch.maximum(ov, hi) - torch.maximum(nv, hi), r)
+    r = torch.where(below, torch.minimum(nv, lo) - torch.minimum(ov, lo), r)
+    return torch.where(inside, torch.zeros_like(r), r)

@@ -22,6 +22,8 @@
  *   pcgrl_get_smb_play               the same for smb's two agents, smb_prob.py:90-124
  *   pcgrl_get_paths                  the cells of the paths that binary's path-length (helper.py:250-264) and zelda's path-length /
  *                                    nearest-enemy (zelda_prob.py:91-110) measure, from the run_dikjstra maps (helper.py:222-237)
+ *   pcgrl_tile_graph                 helper.py:170-296 for any tile set: calc_num_regions with its color_map, calc_longest_path,
+ *                                    run_dikjstra's map, calc_num_reachable_tile -- what a custom Problem builds its get_stats from
  *
  * Conventions: plain pointers and sizes only; every function returns 0 on success or a negative
  * PCGRL_E* code (no exceptions cross the ABI); all device buffers are OWNED BY THE CALLER (hipMalloc,
@@ -57,6 +59,8 @@ extern "C" {
  *     Still 15: + pcgrl_get_paths_legs / pcgrl_get_paths_bytes / pcgrl_get_paths -- additive in the same way; detected by the symbol
  *     pcgrl_get_paths.
  *     Still 15: + pcgrl_get_changes_bytes / pcgrl_get_changes -- additive in the same way; detected by the symbol pcgrl_get_changes.
+ *     Still 15: + pcgrl_tile_graph_desc / pcgrl_tile_graph_bytes / pcgrl_tile_graph -- additive in the same way (one struct, two entry
+ *     points); detected by the symbol pcgrl_tile_graph.
  *     The developer switches pcgrl_tuning grew at their end (changes_grid, changes_chunk): fill them with pcgrl_tuning_defaults. */
 #define PCGRL_ABI_VERSION 15
 #define PCGRL_OK 0
@@ -475,6 +479,48 @@ int    pcgrl_get_changes(pcgrl_env* env, const uint8_t* maps, int32_t count,
                          const int32_t* cells, int32_t ncells, const int32_t* start_rows,
                          int32_t* base_rows_out, int32_t* rows_out, double* reward_out, uint8_t* over_out,
                          void* work, size_t work_bytes, void* stream);
+/* ---- helper.py for any tile set (helper.py:170-296): the functions a custom Problem builds its get_stats from -- calc_num_regions
+ * (:197-207) with the color_map it throws away, calc_longest_path (:250-264), run_dikjstra's whole map (:222-237) and
+ * calc_num_reachable_tile (:288-296) -- for `count` levels of any tiles 0..31, whatever problem the handle has.
+ * The set rule.  The reference's helpers take a LIST of passable values and _get_certain_tiles (:150-154) orders cells by list position
+ * first, row-major second: calc_longest_path's double sweep starts elsewhere in a component, and the color_map is numbered differently,
+ * for [0, 1] than for [1, 0].  Here `passable` is a SET (bit t: tile t), and every result is the reference's result on the level in
+ * which every passable tile has been renamed to one single value: a component's first sweep starts at its first cell in row-major
+ * order, regions are numbered 1, 2, ... by the row-major order of their first cell.  For a single passable value that is the reference
+ * exactly; for several, regions, dist and reach are still exactly the reference's, longest and the label numbering are the merged-tile
+ * ones (the reference's own longest depends on the order of its list).
+ *   maps          DEVICE u8 [count,H,W], read only.  A byte >= 32 is in no set (impassable) and reported (status bit 2).
+ *   passable, source_tiles, reach_tiles   tile sets, bit t = tile t.
+ *   sources       DEVICE i32 [count] or NULL: the source cell of each level, y * W + x, -1 = none; a value outside the map that is not
+ *                 -1 counts as none and is reported like a cell outside the map in pcgrl_get_changes (status bit 1).  NULL: the first
+ *                 cell in row-major order that holds a tile of source_tiles (_get_certain_tiles(locs, [start_value])[0]), none without one.
+ *   Outputs, DEVICE, each one optional: NULL = neither computed nor stored; at least one is needed.
+ *   regions_out   i32 [count]      calc_num_regions(map, locs, passable).
+ *   longest_out   i32 [count]      calc_longest_path(map, locs, passable) under the set rule.
+ *   labels_out    i16 [count,H,W]  the color_map: -1 on impassable cells, 1 .. regions elsewhere, numbered by the set rule.
+ *   dist_out      i16 [count,H,W]  run_dikjstra(source; passable)'s map: -1 where unreached or impassable; all -1 without a source or
+ *                                  with a source cell that is not passable.
+ *   reach_out     i32 [count]      calc_num_reachable_tile: the cells of reach_tiles with dist >= 0 (the source itself when in the set).
+ *   source_out    i32 [count]      the source cell that was used (passable or not), -1 if none.
+ * Every element of every requested output is stored exactly once, nothing else is written.
+ * Same contract as pcgrl_get_paths: a bound handle, no reset needed; only the device, the stream, the width, the height and the lane-group
+ * form are taken from the handle; no episode state read or written, of the handle only the sticky status word written; asynchronous.
+ *   work          DEVICE, 256-byte aligned, at least pcgrl_tile_graph_bytes(cfg, count) bytes; the call's own.
+ *   PCGRL_EINVAL: a NULL desc, maps or work, no output, count < 1, work not 256-byte aligned or too small, or a configuration for
+ *   which pcgrl_tile_graph_bytes is 0.  PCGRL_ESTATE before pcgrl_bind.
+ * pcgrl_tile_graph_bytes: from the configuration alone.  0: no form (maps beyond 64 x 64, smb, count < 1, a NULL or invalid cfg);
+ *   else >= 256. */
+typedef struct pcgrl_tile_graph_desc {
+    const uint8_t* maps;
+    int32_t count;
+    uint32_t passable, source_tiles, reach_tiles;
+    const int32_t* sources;
+    int32_t *regions_out, *longest_out;
+    int16_t *labels_out, *dist_out;
+    int32_t *reach_out, *source_out;
+} pcgrl_tile_graph_desc;
+size_t pcgrl_tile_graph_bytes(const pcgrl_config* cfg, int32_t count);
+int    pcgrl_tile_graph(pcgrl_env* env, const pcgrl_tile_graph_desc* desc, void* work, size_t work_bytes, void* stream);
 /* ActionMap.step for the wide representation (wrappers.py:139-154): flat DEVICE i32 [N] index into
  * (H, W, tiles) -> xyv DEVICE i32 [N,3] = (x, y, tile), the action pcgrl_step takes. */
 int pcgrl_action_map(pcgrl_env* env, const int32_t* flat, int32_t* xyv, void* stream);

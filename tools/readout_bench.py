@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Levels/s of the level read-outs of BatchedPcgrlEnv -- evaluate() (pcgrl_get_stats), solve() (pcgrl_get_solution), playthrough()
-(pcgrl_get_playthrough), playthrough_smb() (pcgrl_get_smb_play), paths() (pcgrl_get_paths) and changes() (pcgrl_get_changes) -- each next
-to the route it is compared with, on the GPU box.  One method: wall clock around the call with a device synchronisation, after a warm-up of each call (the handle,
+(pcgrl_get_playthrough), playthrough_smb() (pcgrl_get_smb_play), paths() (pcgrl_get_paths), changes() (pcgrl_get_changes) and
+connectivity() (pcgrl_tile_graph) -- each next to the route it is compared with, on the GPU box.  One method: wall clock around the call with a device synchronisation, after a warm-up of each call (the handle,
 the workspace, the kernels' code objects, the allocator's blocks); a call is a few ms and the box is shared, so the calls of a case run in
 ONE process on one handle, alternating, `rounds` rounds: minimum, median and maximum of each.  Every case runs in a child process of its
 own under a time limit, so that a hang ends there; a child that fails ends the session.  One JSON line at the end.
@@ -12,6 +12,7 @@ own under a time limit, so that a hang ends there; a child that fails ends the s
     python tools/readout_bench.py smb_play [M] [max_len]             (default: 4096 maps, max_len 255)
     python tools/readout_bench.py paths [M14 [M11x16 [M64]]]         (defaults: 65536 65536 4096)
     python tools/readout_bench.py changes [Mbinary [Mzelda [Msokoban [M16x40]]]]   (defaults: 1024 each)
+    python tools/readout_bench.py tile_graph [M14 [M64]]             (defaults: 65536 8192)
 
 evaluate: evaluate() next to the route there was before it -- a handle of M environments: reset(); set_maps(maps); stats -- three runs
 of each; the handle route is timed with and without building the handle (allocation + seeding + reset), which that route needs once per
@@ -23,7 +24,9 @@ with max_len 64 (the rows a drawing loop of short legs would ask for) next to ev
 30 rounds.  changes: changes() on M levels with all cells next to evaluate(stack, ref=...) on the materialised M * H * W * T stack of the
 same entries (built once, outside the clock: the yardstick gets its input for nothing), binary 14 x 14, zelda 7 x 11, sokoban 5 x 5 and
 binary 16 x 40 (64-bit row masks on sixteen rows: the shape at which changes() takes a wavefront a level where evaluate() takes four), 30
-rounds; the reported "levels" are entries.  The statistics rows of the calls of a case must agree.
+rounds; the reported "levels" are entries.  tile_graph: connectivity(passable=["empty"]) with the scalars only, with + dist (from the
+first empty cell, and the reachable count) and with + labels next to evaluate() on the same binary stack, 14 x 14 and 64 x 64, 30 rounds;
+the scalars must be evaluate()'s rows.  The statistics rows of the calls of a case must agree.
 """
 import argparse
 import json
@@ -210,6 +213,29 @@ def changes_child(prob, h, w, m):
     return out
 
 
+def tile_graph_child(h, w, m):
+    import torch
+    out = {"prob": "binary", "h": h, "w": w, "M": m}
+    maps = device_maps(levels("binary", m, h, w))
+    env = make_env("binary", (h, w))
+    out["s"], last = alternate({"evaluate": lambda: env.evaluate(maps), "scalars": lambda: env.connectivity(maps, passable=["empty"]),
+                                "+dist": lambda: env.connectivity(maps, passable=["empty"], source=["empty"], reach=["empty"], dist=True),
+                                "+labels": lambda: env.connectivity(maps, passable=["empty"], labels=True)}, 30)
+    rows = last["evaluate"].rows
+    for k in ("scalars", "+dist", "+labels"):
+        assert torch.equal(last[k].regions, rows[:, 0]) and torch.equal(last[k].longest, rows[:, 1]), "connectivity() and evaluate() disagree"
+    assert torch.equal(last["+labels"].labels.amax((1, 2)).clamp(min=0).to(torch.int32), rows[:, 0])
+    d = last["+dist"]
+    assert torch.equal((d.dist >= 0).sum((1, 2)).to(torch.int32), d.reach)
+    out["checksum"] = {k: int(r.rows[:, :2].to(torch.int64).sum().item()) if k == "evaluate" else int((r.regions.to(torch.int64) + r.longest).sum().item())
+                       for k, r in last.items()}
+    out["bytes_maps"] = {"evaluate": 0, "scalars": 0, "+dist": int(d.dist.numel() * 2), "+labels": int(last["+labels"].labels.numel() * 2)}
+    out["regions"] = int(rows[:, 0].to(torch.int64).sum().item())
+    out["farthest"] = int(d.dist.max().item())
+    assert env.check_status() == 0
+    return out
+
+
 # ---- the subcommands: arguments -> cases (label, child arguments); a note behind a call's report line; the results -> the JSON
 def moves_note(r, k):
     if k == "evaluate":
@@ -254,6 +280,8 @@ def arguments(p, sub):
         p.add_argument("ms", nargs="*", type=int, default=[], metavar="M", help="levels of binary 14 x 14, zelda 7 x 11, sokoban 5 x 5, binary 16 x 40 (1024 each)")
     elif sub == "paths":
         p.add_argument("ms", nargs="*", type=int, default=[], metavar="M", help="levels of binary 14 x 14, zelda 11 x 16, binary 64 x 64 (65536 65536 4096)")
+    elif sub == "tile_graph":
+        p.add_argument("ms", nargs="*", type=int, default=[], metavar="M", help="levels of binary 14 x 14 and binary 64 x 64 (65536 8192)")
     else:
         if sub == "playthrough":
             p.add_argument("--prob", default="mdungeon", choices=("mdungeon", "ddave"))
@@ -277,6 +305,9 @@ SPECS = {
     "changes": dict(child=changes_child, final=paths_final, note=lambda r, k: "   %d levels, %d no-op entries" % (r["levels"], r["noop"]),
                     cases=lambda a: [("%s %dx%d" % (prob, h, w), (prob, h, w, m))
                                      for (prob, h, w), m in zip((("binary", 14, 14), ("zelda", 7, 11), ("sokoban", 5, 5), ("binary", 16, 40)), a.ms + [1024, 1024, 1024, 1024][len(a.ms):])]),
+    "tile_graph": dict(child=tile_graph_child, final=paths_final,
+                       note=lambda r, k: "   %d regions, farthest %d, %.1f MB of maps" % (r["regions"], r["farthest"], r["bytes_maps"][k] / 1e6),
+                       cases=lambda a: [("binary %dx%d" % (h, w), (h, w, m)) for (h, w), m in zip(((14, 14), (64, 64)), a.ms + [65536, 8192][len(a.ms):])]),
 }
 
 
