@@ -48,7 +48,6 @@ __global__ __launch_bounds__(PCGRL_BLOCK, 8) void k_get_changes(PcgrlParams P, c
                                                               uint8_t* __restrict__ over_out, int32_t* status, int32_t* head, int32_t* jobs) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];      // per lane group: changes_group_bytes
     constexpr int GPW = 64 / G, WPB = PCGRL_BLOCK / 64;
-    constexpr int NSTATS = PROB == PCGRL_PROB_BINARY ? 2 : (PROB == PCGRL_PROB_ZELDA ? 7 : (PROB == PCGRL_PROB_SOKOBAN ? 6 : 8));
     constexpr bool SEARCH = PROB != PCGRL_PROB_BINARY && PROB != PCGRL_PROB_ZELDA;
     constexpr bool ONE_PLANE = PROB == PCGRL_PROB_BINARY;
     DevGroup<G, MaskT> g;
@@ -82,7 +81,7 @@ __global__ __launch_bounds__(PCGRL_BLOCK, 8) void k_get_changes(PcgrlParams P, c
             if (g.lane == 0 && have) {
 #pragma unroll
                 for (int k = 0; k < 8; k++) {
-                    own[k] = k < NSTATS ? sb[k] : 0;                     // (binary: the champion flag and bound of slots 2, 3 stay inside)
+                    own[k] = k < num_stats(PROB) ? sb[k] : 0;            // (store_stats_row's rule, column by column beside the start row)
                     own[8 + k] = (start_rows && !SEARCH) ? start_rows[(size_t)m * 8 + k] : own[k];
                 }
                 if (!SEARCH) own[16] = episode_over(P, own, own + 8, PROB) ? 1 : 0;
@@ -125,7 +124,7 @@ __global__ __launch_bounds__(PCGRL_BLOCK, 8) void k_get_changes(PcgrlParams P, c
                 if (g.lane == 0 && havek) {
                     const size_t e = (size_t)((item[0] + k) * T + t);
 #pragma unroll
-                    for (int q = NSTATS; q < 8; q++) s[q] = 0;           // (binary: the champion flag and bound of slots 2, 3 stay inside)
+                    for (int q = num_stats(PROB); q < 8; q++) s[q] = 0;  // (store_stats_row's rule, here before the reward reads the row)
                     if (rows_out) {
 #pragma unroll
                         for (int q = 0; q < 8; q++) rows_out[e * 8 + q] = s[q];

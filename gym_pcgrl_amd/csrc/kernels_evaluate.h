@@ -18,48 +18,77 @@ enum { EVAL_HEAD_NJOBS = 0, EVAL_HEAD_TICKET = 1 };
 
 // a tile id beyond the last counts as the last one: the one rule of every pass that reads the caller's bytes (eval_stage_map, k_changes_finish)
 __device__ __forceinline__ uint8_t eval_tile_clamped(uint8_t t, int ntiles) { return t >= ntiles ? (uint8_t)(ntiles - 1) : t; }
-// the caller's tile bytes of map m into the group's LDS stage: a tile id beyond the last is clamped here (the caller's map stays as
-// it is) and reported in the status word
+// the caller's tile bytes of map m into the group's LDS stage: a tile id from `ntiles` on is reported in the status word and, with
+// CLAMP, clamped here (the caller's map stays as it is); without, the byte is staged as it is (k_tile_graph: it is in no tile set)
+template <bool CLAMP = true>
 __device__ __forceinline__ void eval_stage_map(const uint8_t* __restrict__ maps, long long m, int cells, int ntiles, uint8_t* stage, int lane, int nlanes,
                                                int32_t* status) {
     const uint8_t* src = maps + (size_t)m * cells;
     for (int c = lane; c < cells; c += nlanes) {
         const uint8_t t = src[c];
         if (t >= ntiles) atomicOr(status, PCGRL_STATUS_BAD_TILE);
-        stage[c] = eval_tile_clamped(t, ntiles);
+        stage[c] = CLAMP ? eval_tile_clamped(t, ntiles) : t;
     }
+}
+
+// The frame of the kernels with a lane group per caller-supplied map (k_get_stats, k_get_paths; k_tile_graph has it written out, see
+// there; map_grid in pcgrl_abi.hip is its launch shape): four maps a wavefront at <= 16 rows, a wavefront per map beyond; `smem` holds
+// a stage of tile bytes per group.
+template <int G, class MaskT>
+struct MapLanes {
+    DevGroup<G, MaskT> g;
+    int wv, gw;                                                         // the wavefront in the block, the group in the wavefront
+    uint8_t* tiles;                                                     // the group's LDS stage
+    __device__ __forceinline__ MapLanes(uint8_t* smem, int cells) {
+        wv = threadIdx.x >> 6;
+        gw = (threadIdx.x & 63) / G;
+        tiles = smem + (size_t)(wv * (64 / G) + gw) * reset_tile_bytes(cells);
+    }
+    // f(m, have) for the group's maps, grid-stride over `count`.  A wave-uniform loop: the groups of a wavefront go round together, a
+    // group beyond `count` sits the round out (have = false: a whole lane group; the loop bound is the wavefront's)
+    template <class F>
+    __device__ __forceinline__ void each(int count, F f) const {
+        constexpr int GPW = 64 / G, WPB = PCGRL_BLOCK / 64;
+        for (long long base = ((long long)blockIdx.x * WPB + wv) * GPW; base < count; base += (long long)gridDim.x * WPB * GPW) {
+            const long long m = base + gw;
+            f(m, m < count);
+        }
+    }
+    // map m's bytes -> the stage -> this lane's words of the row planes; on return the stage is free for the next round
+    __device__ __forceinline__ void planes(const PcgrlParams& P, const uint8_t* __restrict__ maps, long long m, bool have, MaskT& b0, MaskT& b1, MaskT& b2,
+                                           int32_t* status) const {
+        if (have) eval_stage_map(maps, m, P.width * P.height, P.ntiles, tiles, g.lane, G, status);
+        __builtin_amdgcn_wave_barrier();
+        planes_from_tiles<MaskT>(P, tiles, (MaskT*)nullptr, have ? g.lane : -1, b0, b1, b2, false);
+        __builtin_amdgcn_wave_barrier();
+    }
+};
+// a statistics row as the caller gets it: the problem's columns, zeros behind them (binary: the champion flag and bound of slots 2, 3
+// stay inside)
+template <int PROB>
+__device__ __forceinline__ void store_stats_row(int32_t* row, const int32_t* s) {
+#pragma unroll
+    for (int k = 0; k < 8; k++) row[k] = k < num_stats(PROB) ? s[k] : 0;
 }
 
 template <int PROB, int G, class MaskT>
 __global__ __launch_bounds__(PCGRL_BLOCK) void k_get_stats(PcgrlParams P, const uint8_t* __restrict__ maps, int count, int32_t* __restrict__ rows_out,
                                                             int32_t* status, int32_t* head, int32_t* jobs) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];      // per lane group the tile bytes of its map
-    constexpr int GPW = 64 / G, WPB = PCGRL_BLOCK / 64;
-    constexpr int NSTATS = PROB == PCGRL_PROB_BINARY ? 2 : (PROB == PCGRL_PROB_ZELDA ? 7 : (PROB == PCGRL_PROB_SOKOBAN ? 6 : 8));
-    DevGroup<G, MaskT> g;
-    const int lane64 = threadIdx.x & 63, wv = threadIdx.x >> 6, gw = lane64 / G;
-    const int W = P.width, H = P.height, cells = W * H;
-    uint8_t* tiles = smem + (size_t)(wv * GPW + gw) * reset_tile_bytes(cells);
-    const MaskT rowmask = row_valid<MaskT>(g.lane, W, H);
-    // wave-uniform loop: the groups of a wavefront go round together, a group beyond `count` sits the round out
-    for (long long base = ((long long)blockIdx.x * WPB + wv) * GPW; base < count; base += (long long)gridDim.x * WPB * GPW) {
-        const long long m = base + gw;
-        const bool have = m < count;
-        if (have) eval_stage_map(maps, m, cells, P.ntiles, tiles, g.lane, G, status);
-        __builtin_amdgcn_wave_barrier();
+    const MapLanes<G, MaskT> L(smem, P.width * P.height);
+    const auto& g = L.g;
+    const MaskT rowmask = row_valid<MaskT>(g.lane, P.width, P.height);
+    L.each(count, [&](long long m, bool have) {
         MaskT b0, b1, b2;
-        planes_from_tiles<MaskT>(P, tiles, (MaskT*)nullptr, have ? g.lane : -1, b0, b1, b2, false);
-        __builtin_amdgcn_wave_barrier();                                // (the stage is free for the next round)
+        L.planes(P, maps, m, have, b0, b1, b2, status);
         int32_t s[PCGRL_MAX_STATS] = {0, 0, 0, 0, 0, 0, 0, 0};
         bool need_solver = false;
         if (have) need_solver = compute_item_stats<PROB>(g, P, b0, b1, b2, rowmask, s, status);
         if (g.lane == 0 && have) {
-            int32_t* row = rows_out + (size_t)m * 8;
-#pragma unroll
-            for (int k = 0; k < 8; k++) row[k] = k < NSTATS ? s[k] : 0;      // (binary: the champion flag and bound of slots 2, 3 stay inside)
+            store_stats_row<PROB>(rows_out + (size_t)m * 8, s);
             if (need_solver) jobs[atomicAdd(head + EVAL_HEAD_NJOBS, 1)] = (int32_t)m;
         }
-    }
+    });
 }
 
 // `Bs`: what search_game_run reads of a DevBufs -- status, sok_use_lds, sok_fast_maxc (SearchGame<PROB>::build) and `map`, which every

@@ -1,8 +1,7 @@
 // pcgrl_get_paths: the cells of the paths behind binary's `path-length` and zelda's `path-length` / `nearest-enemy` (path_trace.h).
 // Part of the single translation unit pcgrl_abi.hip.
-//   k_get_paths   k_get_stats' shape (kernels_evaluate.h): a lane group per map -- four maps a wavefront at <= 16 rows, a wavefront
-//                 per map beyond -- grid-stride over `count`; the caller's bytes -> the LDS stage -> row planes in registers ->
-//                 compute_item_stats for the row -> the legs.  The distance classes of a sweep and the walk-back live in registers:
+//   k_get_paths   k_get_stats' frame (MapLanes, kernels_evaluate.h): a lane group per map, grid-stride over `count`; the caller's bytes
+//                 -> the LDS stage -> row planes in registers -> compute_item_stats for the row -> the legs.  The distance classes of a sweep and the walk-back live in registers:
 //                 no LDS beyond the stage, no workspace per map.  Every element of a map's [legs, max_len] cells is stored exactly
 //                 once: the cells by the lane that owns each, then -1 from the end of the leg to the end of the row.
 #pragma once
@@ -26,30 +25,18 @@ template <int PROB, int G, class MaskT>
 __global__ __launch_bounds__(PCGRL_BLOCK) void k_get_paths(PcgrlParams P, const uint8_t* __restrict__ maps, int count, int max_len, int16_t* __restrict__ cells_out,
                                                             int32_t* __restrict__ length_out, int32_t* __restrict__ rows_out, int32_t* status) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];      // per lane group the tile bytes of its map
-    constexpr int GPW = 64 / G, WPB = PCGRL_BLOCK / 64, LEGS = paths_legs(PROB);
-    constexpr int NSTATS = PROB == PCGRL_PROB_BINARY ? 2 : 7;
-    DevGroup<G, MaskT> g;
-    const int lane64 = threadIdx.x & 63, wv = threadIdx.x >> 6, gw = lane64 / G;
-    const int W = P.width, H = P.height, cells = W * H;
-    uint8_t* tiles = smem + (size_t)(wv * GPW + gw) * reset_tile_bytes(cells);
-    const MaskT rowmask = row_valid<MaskT>(g.lane, W, H);
-    // wave-uniform loop: the groups of a wavefront go round together, a group beyond `count` sits the round out
-    for (long long base = ((long long)blockIdx.x * WPB + wv) * GPW; base < count; base += (long long)gridDim.x * WPB * GPW) {
-        const long long m = base + gw;
-        const bool have = m < count;
-        if (have) eval_stage_map(maps, m, cells, P.ntiles, tiles, g.lane, G, status);
-        __builtin_amdgcn_wave_barrier();
+    constexpr int LEGS = paths_legs(PROB);
+    const MapLanes<G, MaskT> L(smem, P.width * P.height);
+    const auto& g = L.g;
+    const int W = P.width;
+    const MaskT rowmask = row_valid<MaskT>(g.lane, W, P.height);
+    L.each(count, [&](long long m, bool have) {
         MaskT b0, b1, b2;
-        planes_from_tiles<MaskT>(P, tiles, (MaskT*)nullptr, have ? g.lane : -1, b0, b1, b2, false);
-        __builtin_amdgcn_wave_barrier();                                // (the stage is free for the next round)
-        if (!have) continue;                                            // (a whole lane group; the loop bound is the wavefront's)
+        L.planes(P, maps, m, have, b0, b1, b2, status);
+        if (!have) return;
         int32_t s[PCGRL_MAX_STATS] = {0, 0, 0, 0, 0, 0, 0, 0};
         compute_item_stats<PROB>(g, P, b0, b1, b2, rowmask, s, status);
-        if (g.lane == 0 && rows_out) {
-            int32_t* row = rows_out + (size_t)m * 8;
-#pragma unroll
-            for (int k = 0; k < 8; k++) row[k] = k < NSTATS ? s[k] : 0;      // (binary: the champion flag and bound of slots 2, 3 stay inside)
-        }
+        if (g.lane == 0 && rows_out) store_stats_row<PROB>(rows_out + (size_t)m * 8, s);
         DevPathSink<MaskT> sink = {cells_out + (size_t)m * LEGS * max_len, nullptr, max_len, W, g.lane};
         sink.leg(0);
         int len[PATHS_MAX_LEGS] = {-1, -1, -1};
@@ -62,5 +49,5 @@ __global__ __launch_bounds__(PCGRL_BLOCK) void k_get_paths(PcgrlParams P, const 
             for (int i = n + g.lane; i < max_len; i += G) sink.row[i] = (int16_t)-1;
             if (g.lane == 0) length_out[(size_t)m * LEGS + l] = len[l];
         }
-    }
+    });
 }

@@ -1,7 +1,9 @@
 // pcgrl_tile_graph: helper.py (helper.py:170-296) for any tile set on the caller's maps (tile_graph.h has the set rule).
 // Part of the single translation unit pcgrl_abi.hip.
-//   k_tile_graph  k_get_paths' shape (kernels_paths.h): a lane group per map -- four maps a wavefront at <= 16 rows, a wavefront per map
-//                 beyond -- grid-stride over `count`; the caller's bytes -> the LDS stage -> the pass / source / reach planes in registers,
+//   k_tile_graph  k_get_stats' shape (MapLanes, kernels_evaluate.h), with the preamble and the loop written out here: under MapLanes::each
+//                 the + dist call on 64 x 64 maps measured 0.5 - 0.8 % slower than this form in two sessions (profiles/readout_frame/NOTES.md).
+//                 A lane group per map, grid-stride over `count`; the caller's bytes, as they are (eval_stage_map<false>), -> the LDS
+//                 stage -> the pass / source / reach planes in registers,
 //                 built from three 32-bit tile sets (the problem's own tiles and planes_from_tiles are not used: tiles 0..31 are legal,
 //                 a byte >= 32 is in no set and reported).  The label and distance planes live in registers: no LDS beyond the stage,
 //                 no workspace per map.  Every output is optional (NULL: neither computed nor stored; the checks are on kernel
@@ -9,16 +11,6 @@
 //                 the lane that owns it, a map's row by the lane that holds it.
 #pragma once
 #include "tile_graph.h"
-
-// the caller's tile bytes of map m into the group's LDS stage as they are; a byte no set can name is reported
-__device__ __forceinline__ void tg_stage_map(const uint8_t* __restrict__ maps, long long m, int cells, uint8_t* stage, int lane, int nlanes, int32_t* status) {
-    const uint8_t* src = maps + (size_t)m * cells;
-    for (int c = lane; c < cells; c += nlanes) {
-        const uint8_t t = src[c];
-        if (t >= 32) atomicOr(status, PCGRL_STATUS_BAD_TILE);
-        stage[c] = t;
-    }
-}
 
 // row `lane` of a map's [H, W] i16 output from its NP planes, 32 columns of plane words at a time
 template <int NP, class MaskT>
@@ -46,11 +38,11 @@ __global__ __launch_bounds__(PCGRL_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 
     const int W = P.width, H = P.height, cells = W * H, count = D.count;
     uint8_t* tiles = smem + (size_t)(wv * GPW + gw) * reset_tile_bytes(cells);
     const bool want_scalars = D.regions_out || D.longest_out, want_sweep = D.dist_out || D.reach_out;
-    // wave-uniform loop: the groups of a wavefront go round together, a group beyond `count` sits the round out
+    // (MapLanes::each's loop and `have` rule)
     for (long long base = ((long long)blockIdx.x * WPB + wv) * GPW; base < count; base += (long long)gridDim.x * WPB * GPW) {
         const long long m = base + gw;
         const bool have = m < count;
-        if (have) tg_stage_map(D.maps, m, cells, tiles, g.lane, G, status);
+        if (have) eval_stage_map<false>(D.maps, m, cells, 32, tiles, g.lane, G, status);      // (a byte no set can name is reported)
         __builtin_amdgcn_wave_barrier();
         MaskT pass = 0, srcs = 0, goal = 0;
         if (have && g.lane < H) {
@@ -65,7 +57,7 @@ __global__ __launch_bounds__(PCGRL_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 
             }
         }
         __builtin_amdgcn_wave_barrier();                                // (the stage is free for the next round)
-        if (!have) continue;                                            // (a whole lane group; the loop bound is the wavefront's)
+        if (!have) continue;
         if (want_scalars) {
             int regions, path;
             regions_and_longest_path(g, pass, regions, path);

@@ -1945,11 +1945,12 @@ int pcgrl_get_smb_play(pcgrl_env* h, const uint8_t* maps, int32_t count, int32_t
 }
 
 // ---- pcgrl_get_paths (kernels_paths.h, path_trace.h): the cells behind binary's path-length and zelda's path-length / nearest-enemy --
-// The workspace, cut from one plan like pcgrl_get_stats': the kernel keeps a sweep's distance classes in registers and needs nothing
-// per map, so the plan is the head every such call has (the size the caller is told stays a whole 256-byte region).
-struct PathsPlan { Region head; size_t total; };
-static PathsPlan paths_plan(const pcgrl_config*, int) {
-    PathsPlan S = {};
+// The workspace of a read-out whose kernel keeps everything in registers (here a sweep's distance classes, in pcgrl_tile_graph the label
+// and distance planes) and needs nothing per map, cut from one plan like pcgrl_get_stats': the head every such call has (the size the
+// caller is told stays a whole 256-byte region).
+struct HeadPlan { Region head; size_t total; };
+static HeadPlan head_plan(const pcgrl_config*, int) {
+    HeadPlan S = {};
     Bump b = {0};
     S.head = b.take(256);
     S.total = b.off;
@@ -1959,7 +1960,7 @@ int32_t pcgrl_get_paths_legs(const pcgrl_config* c) { return c ? paths_legs(c->p
 size_t pcgrl_get_paths_bytes(const pcgrl_config* c, int32_t count, int32_t max_len) {
     pcgrl_config one;
     if (!c || paths_legs(c->prob) == 0 || max_len < 1 || pcgrl_get_stats_bytes(c, count) == 0 || !one_env(c, &one)) return 0;
-    return paths_plan(&one, count).total;
+    return head_plan(&one, count).total;
 }
 int pcgrl_get_paths(pcgrl_env* h, const uint8_t* maps, int32_t count, int32_t max_len, int16_t* cells_out, int32_t* length_out, int32_t* rows_out,
                     void* work, size_t work_bytes, void* stream) {
@@ -1969,20 +1970,11 @@ int pcgrl_get_paths(pcgrl_env* h, const uint8_t* maps, int32_t count, int32_t ma
 }
 
 // ---- pcgrl_tile_graph (kernels_tile_graph.h, tile_graph.h): helper.py:170-296 for any tile set ---------------------------------------
-// The workspace, cut from one plan like pcgrl_get_paths': the label and distance planes live in registers, nothing is needed per map,
-// so the plan is the head every such call has.
-struct TileGraphPlan { Region head; size_t total; };
-static TileGraphPlan tile_graph_plan(const pcgrl_config*, int) {
-    TileGraphPlan S = {};
-    Bump b = {0};
-    S.head = b.take(256);
-    S.total = b.off;
-    return S;
-}
+// (the workspace: head_plan, like pcgrl_get_paths')
 size_t pcgrl_tile_graph_bytes(const pcgrl_config* c, int32_t count) {
     pcgrl_config one;
     if (!c || count < 1 || c->prob == PCGRL_SMB || !one_env(c, &one) || big_map(&one)) return 0;
-    return tile_graph_plan(&one, count).total;
+    return head_plan(&one, count).total;
 }
 int pcgrl_tile_graph(pcgrl_env* h, const pcgrl_tile_graph_desc* d, void* work, size_t work_bytes, void* stream) {
     const bool ptrs = d && d->maps && (d->regions_out || d->longest_out || d->labels_out || d->dist_out || d->reach_out || d->source_out);

@@ -9,26 +9,18 @@
 // -DSIM_CHANGES_MAIN -fsanitize=address,undefined, as a stand-alone program that runs built-in levels of the GPU tests' shapes through
 // every (lane group, mask width) form.
 #include "sim_algos.cpp"
+#include "sim_forms.h"
 
-template <int G, class T>
-static void planes_of(const uint8_t* map, int h, int w, SimVec<T, G>& b0, SimVec<T, G>& b1, SimVec<T, G>& b2) {
-    b0 = SimVec<T, G>(); b1 = SimVec<T, G>(); b2 = SimVec<T, G>();
-    for (int y = 0; y < h; y++)
-        for (int x = 0; x < w; x++) {                // (planes_from_tiles, reset_env.h)
-            const T t = map[y * w + x];
-            b0.v[y] |= (t & 1) << x; b1.v[y] |= ((t >> 1) & 1) << x; b2.v[y] |= ((t >> 2) & 1) << x;
-        }
-}
 template <int G, class T>
 static bool same(const SimVec<T, G>& a, const SimVec<T, G>& b) { return memcmp(a.v, b.v, sizeof(a.v)) == 0; }
 
 // the number of (cell, tile) pairs checked, or -(entry + 1) of the first that fails; -1 000 000 000: the form does not hold the map
 template <int G, class T>
-static long run_changes(const uint8_t* map, int h, int w, int ntiles) {
+static long run_changes(SimGroup<G, T>, const uint8_t* map, int h, int w, int ntiles) {
     typedef SimVec<T, G> M;
     if (h > G || w > (int)(8 * sizeof(T)) || ntiles > 8) return -1000000000L;
     M k0, k1, k2;                                                        // the kept copy: written once per level
-    planes_of<G, T>(map, h, w, k0, k1, k2);
+    planes_of(map, h, w, k0, k1, k2);
     std::vector<uint8_t> edited(map, map + (size_t)h * w);
     long n = 0;
     M b0, b1, b2;                                                        // the working planes: edited in place, entry after entry
@@ -37,14 +29,14 @@ static long run_changes(const uint8_t* map, int h, int w, int ntiles) {
             b0 = k0; b1 = k1; b2 = k2;                                   // the restore: a reload of the kept copy
             {
                 M l0, l1, l2;
-                planes_of<G, T>(map, h, w, l0, l1, l2);
+                planes_of(map, h, w, l0, l1, l2);
                 if (!same(b0, l0) || !same(b1, l1) || !same(b2, l2)) return -(n + 1);      // after the entry before: the level's again
             }
             const int y = c / w, x = c - y * w;
             planes_set_cell(b0.v[y], b1.v[y], b2.v[y], x, t);           // the lane that owns row y
             edited[c] = (uint8_t)t;
             M r0, r1, r2;
-            planes_of<G, T>(edited.data(), h, w, r0, r1, r2);
+            planes_of(edited.data(), h, w, r0, r1, r2);
             edited[c] = map[c];
             if (!same(b0, r0) || !same(b1, r1) || !same(b2, r2)) return -(n + 1);
             for (int r = 0; r < G; r++)
@@ -58,20 +50,14 @@ static long run_changes(const uint8_t* map, int h, int w, int ntiles) {
 extern "C" {
 // group = 16 or 64 lanes, mask_bits = 32 or 64
 long sim_changes(const uint8_t* map, int h, int w, int ntiles, int group, int mask_bits) {
-    if (group == 16 && mask_bits == 32) return run_changes<16, uint32_t>(map, h, w, ntiles);
-    if (group == 16 && mask_bits == 64) return run_changes<16, uint64_t>(map, h, w, ntiles);
-    if (group == 64 && mask_bits == 32) return run_changes<64, uint32_t>(map, h, w, ntiles);
-    if (group == 64 && mask_bits == 64) return run_changes<64, uint64_t>(map, h, w, ntiles);
-    return -1000000000L;
+    return sim_with_form(group, mask_bits, -1000000000L, [&](auto g) { return run_changes(g, map, h, w, ntiles); });
 }
 }
 
 #ifdef SIM_CHANGES_MAIN
-static unsigned g_lcg = 2025u;
-static unsigned lcg() { g_lcg = g_lcg * 1664525u + 1013904223u; return g_lcg >> 8; }
+static SimLcg lcg = {2025u};
 
 int main() {
-    const int forms[4][2] = {{16, 32}, {16, 64}, {64, 32}, {64, 64}};
     // (tiles, rows, columns): binary and zelda at the shapes of tests/test_gpu_changes.py
     const int shapes[9][3] = {{2, 1, 1}, {2, 3, 5}, {2, 16, 32}, {2, 16, 33}, {2, 17, 32}, {2, 17, 33}, {2, 64, 64}, {8, 7, 11}, {8, 17, 33}};
     long checked = 0;
@@ -82,9 +68,9 @@ int main() {
             std::vector<uint8_t> map((size_t)h * w);
             for (auto& t : map) t = rep == 0 ? (uint8_t)(lcg() % nt) : (rep == 1 ? 0 : (uint8_t)(nt - 1));
             for (int f = 0; f < 4; f++) {
-                if (h > forms[f][0] || w > forms[f][1]) continue;
-                const long n = sim_changes(map.data(), h, w, nt, forms[f][0], forms[f][1]);
-                if (n != (long)h * w * nt) { printf("shape %d x %d form %d/%d: %ld\n", h, w, forms[f][0], forms[f][1], n); return 2; }
+                if (h > SIM_FORMS[f][0] || w > SIM_FORMS[f][1]) continue;
+                const long n = sim_changes(map.data(), h, w, nt, SIM_FORMS[f][0], SIM_FORMS[f][1]);
+                if (n != (long)h * w * nt) { printf("shape %d x %d form %d/%d: %ld\n", h, w, SIM_FORMS[f][0], SIM_FORMS[f][1], n); return 2; }
                 checked += n;
                 forms_seen |= 1 << f;
             }

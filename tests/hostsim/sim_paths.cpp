@@ -5,6 +5,7 @@
 // shared library for tests/test_paths_host.py and, with -DSIM_PATHS_MAIN -fsanitize=address,undefined, as a stand-alone program that
 // runs a few built-in levels through every (lane group, mask width) form.
 #include "sim_algos.cpp"
+#include "sim_forms.h"
 #include "../../gym_pcgrl_amd/csrc/path_trace.h"
 
 // path_trace.h's Sink: the lane (row) that holds the bit stores y * W + x
@@ -28,19 +29,11 @@ struct SimPathSink {
 };
 
 template <int G, class T>
-static int run_paths(int prob, const uint8_t* map, int h, int w, int max_len, int16_t* cells, int32_t* length, int32_t* row8) {
-    typedef SimGroup<G, T> Gp;
-    typedef typename Gp::mask_t M;
+static int run_paths(SimGroup<G, T> g, int prob, const uint8_t* map, int h, int w, int max_len, int16_t* cells, int32_t* length, int32_t* row8) {
     if (h > G || w > (int)(8 * sizeof(T))) return -1;
-    Gp g;
-    M b0, b1, b2, valid;
-    for (int y = 0; y < h; y++) {
-        valid.v[y] = (w >= (int)(8 * sizeof(T))) ? ~(T)0 : (((T)1 << w) - 1);
-        for (int x = 0; x < w; x++) {
-            T t = map[y * w + x];
-            b0.v[y] |= (t & 1) << x; b1.v[y] |= ((t >> 1) & 1) << x; b2.v[y] |= ((t >> 2) & 1) << x;
-        }
-    }
+    SimVec<T, G> b0, b1, b2, valid;
+    planes_of(map, h, w, b0, b1, b2);
+    for (int y = 0; y < h; y++) valid.v[y] = (w >= (int)(8 * sizeof(T))) ? ~(T)0 : (((T)1 << w) - 1);
     PcgrlParams P; memset(&P, 0, sizeof(P));
     P.prob = prob; P.width = w; P.height = h; P.prob_width = w; P.prob_height = h;
     int32_t s[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -68,11 +61,7 @@ static int run_paths(int prob, const uint8_t* map, int h, int w, int max_len, in
 extern "C" {
 // group = 16 or 64 lanes, mask_bits = 32 or 64; cells [legs][max_len], length [legs], row8 [8].  -1: the form does not hold the map.
 int sim_paths(int prob, const uint8_t* map, int h, int w, int group, int mask_bits, int max_len, int16_t* cells, int32_t* length, int32_t* row8) {
-    if (group == 16 && mask_bits == 32) return run_paths<16, uint32_t>(prob, map, h, w, max_len, cells, length, row8);
-    if (group == 16 && mask_bits == 64) return run_paths<16, uint64_t>(prob, map, h, w, max_len, cells, length, row8);
-    if (group == 64 && mask_bits == 32) return run_paths<64, uint32_t>(prob, map, h, w, max_len, cells, length, row8);
-    if (group == 64 && mask_bits == 64) return run_paths<64, uint64_t>(prob, map, h, w, max_len, cells, length, row8);
-    return -1;
+    return sim_with_form(group, mask_bits, -1, [&](auto g) { return run_paths(g, prob, map, h, w, max_len, cells, length, row8); });
 }
 }
 
@@ -90,11 +79,9 @@ static bool walk_ok(const int16_t* c, int len, int max_len, int h, int w) {
     }
     return true;
 }
-static unsigned g_lcg = 2024u;
-static unsigned lcg() { g_lcg = g_lcg * 1664525u + 1013904223u; return g_lcg >> 8; }
+static SimLcg lcg = {2024u};
 
 int main() {
-    const int forms[4][2] = {{16, 32}, {16, 64}, {64, 32}, {64, 64}};
     const int sizes[6][2] = {{1, 1}, {3, 7}, {16, 32}, {16, 33}, {17, 9}, {64, 64}};
     long legs_found = 0;
     for (int prob = 0; prob < 2; prob++) {
@@ -115,11 +102,11 @@ int main() {
                 std::vector<int16_t> want;
                 bool have_want = false;
                 for (int f = 0; f < 4; f++) {
-                    if (h > forms[f][0] || w > forms[f][1]) continue;
+                    if (h > SIM_FORMS[f][0] || w > SIM_FORMS[f][1]) continue;
                     for (int max_len : {1, 2, h * w, h * w + 3}) {
                         std::vector<int16_t> cells((size_t)3 * max_len + 2, 77);      // two guard words behind the rows
                         int32_t len[3] = {-9, -9, -9}, row[8];
-                        if (sim_paths(prob, map.data(), h, w, forms[f][0], forms[f][1], max_len, cells.data(), len, row) != 0) return 2;
+                        if (sim_paths(prob, map.data(), h, w, SIM_FORMS[f][0], SIM_FORMS[f][1], max_len, cells.data(), len, row) != 0) return 2;
                         const int legs = prob == 0 ? 1 : 3;
                         if (cells[(size_t)legs * max_len] != 77 || cells[(size_t)3 * max_len + 1] != 77) return 3;
                         for (int l = 0; l < legs; l++) {

@@ -5,6 +5,7 @@
 // tile_graph.h, each row unpacked once.  Built as a shared library for tests/test_tile_graph_host.py and, with -DSIM_TILE_GRAPH_MAIN
 // -fsanitize=address,undefined, as a stand-alone program that runs a few built-in levels through every (lane group, mask width) form.
 #include "sim_algos.cpp"
+#include "sim_forms.h"
 #include "../../gym_pcgrl_amd/csrc/tile_graph.h"
 
 // a map's [h, w] i16 output from its planes: row y by the words of lane y
@@ -20,14 +21,12 @@ static void store_planes(int16_t* out, const SimVec<T, G>* p, const SimVec<T, G>
 // source: -2 = the first cell of source_tiles, else the cell (-1, or outside the map: none).  Every output may be NULL.
 // Returns 0, or -1 when the form does not hold the map; *status gets 4 for a byte >= 32 and 2 for a source cell outside the map.
 template <int G, class T>
-static int run_tile_graph(const uint8_t* map, int h, int w, uint32_t passable, uint32_t source_tiles, uint32_t reach_tiles, int source,
+static int run_tile_graph(SimGroup<G, T> g, const uint8_t* map, int h, int w, uint32_t passable, uint32_t source_tiles, uint32_t reach_tiles, int source,
                           int32_t* regions_out, int32_t* longest_out, int16_t* labels_out, int16_t* dist_out, int32_t* reach_out,
                           int32_t* source_out, int32_t* status) {
-    typedef SimGroup<G, T> Gp;
-    typedef typename Gp::mask_t M;
+    typedef SimVec<T, G> M;
     constexpr int NP = tg_planes(G, 8 * (int)sizeof(T));
     if (h > G || w > (int)(8 * sizeof(T))) return -1;
-    Gp g;
     M pass, srcs, goal;
     for (int y = 0; y < h; y++)
         for (int x = 0; x < w; x++) {
@@ -76,19 +75,14 @@ extern "C" {
 int sim_tile_graph(const uint8_t* map, int h, int w, int group, int mask_bits, uint32_t passable, uint32_t source_tiles, uint32_t reach_tiles,
                    int source, int32_t* regions_out, int32_t* longest_out, int16_t* labels_out, int16_t* dist_out, int32_t* reach_out,
                    int32_t* source_out, int32_t* status) {
-#define TG_FORM(G, T) return run_tile_graph<G, T>(map, h, w, passable, source_tiles, reach_tiles, source, regions_out, longest_out, labels_out, dist_out, reach_out, source_out, status)
-    if (group == 16 && mask_bits == 32) TG_FORM(16, uint32_t);
-    if (group == 16 && mask_bits == 64) TG_FORM(16, uint64_t);
-    if (group == 64 && mask_bits == 32) TG_FORM(64, uint32_t);
-    if (group == 64 && mask_bits == 64) TG_FORM(64, uint64_t);
-#undef TG_FORM
-    return -1;
+    return sim_with_form(group, mask_bits, -1, [&](auto g) {
+        return run_tile_graph(g, map, h, w, passable, source_tiles, reach_tiles, source, regions_out, longest_out, labels_out, dist_out, reach_out, source_out, status);
+    });
 }
 }
 
 #ifdef SIM_TILE_GRAPH_MAIN
-static unsigned g_lcg = 2024u;
-static unsigned lcg() { g_lcg = g_lcg * 1664525u + 1013904223u; return g_lcg >> 8; }
+static SimLcg lcg = {2024u};
 
 // what the outputs must satisfy whatever the level: labels 1..regions exactly on the passable cells, each label 4-connected to
 // nothing of another label; dist 0 exactly at a passable source, neighbours within 1, every reached cell but the source with a
@@ -120,7 +114,6 @@ static int check(const uint8_t* map, int h, int w, uint32_t passable, uint32_t r
 }
 
 int main() {
-    const int forms[4][2] = {{16, 32}, {16, 64}, {64, 32}, {64, 64}};
     const int sizes[7][2] = {{1, 1}, {3, 7}, {16, 32}, {16, 33}, {17, 9}, {9, 64}, {64, 64}};
     long levels = 0, reached = 0;
     for (int si = 0; si < 7; si++) {
@@ -138,10 +131,10 @@ int main() {
             int32_t want[4] = {0, 0, 0, 0};
             bool have_want = false;
             for (int f = 0; f < 4; f++) {
-                if (h > forms[f][0] || w > forms[f][1]) continue;
+                if (h > SIM_FORMS[f][0] || w > SIM_FORMS[f][1]) continue;
                 std::vector<int16_t> lab((size_t)h * w + 2, 77), dist((size_t)h * w + 2, 77);      // a guard word at either end
                 int32_t out[4] = {-9, -9, -9, -9}, status = 0;
-                if (sim_tile_graph(map.data(), h, w, forms[f][0], forms[f][1], passable, source_tiles, reach_tiles, source, &out[0], &out[1],
+                if (sim_tile_graph(map.data(), h, w, SIM_FORMS[f][0], SIM_FORMS[f][1], passable, source_tiles, reach_tiles, source, &out[0], &out[1],
                                    lab.data() + 1, dist.data() + 1, &out[2], &out[3], &status) != 0) return 2;
                 if (lab[0] != 77 || lab[(size_t)h * w + 1] != 77 || dist[0] != 77 || dist[(size_t)h * w + 1] != 77) return 3;
                 if (status != ((rep == 5 && h * w > 1) ? 4 : 0) + (rep == 4 ? 2 : 0)) return 4;
@@ -149,7 +142,7 @@ int main() {
                 if (out[1] < 0 || out[1] >= h * w) return 5;
                 // each output alone gives the same value
                 int32_t alone = -9, st2 = 0;
-                if (sim_tile_graph(map.data(), h, w, forms[f][0], forms[f][1], passable, source_tiles, reach_tiles, source, nullptr, nullptr, nullptr, nullptr,
+                if (sim_tile_graph(map.data(), h, w, SIM_FORMS[f][0], SIM_FORMS[f][1], passable, source_tiles, reach_tiles, source, nullptr, nullptr, nullptr, nullptr,
                                    &alone, nullptr, &st2) != 0 || alone != out[2]) return 6;
                 if (!have_want) { want_lab = lab; want_dist = dist; memcpy(want, out, sizeof(out)); have_want = true; }
                 else if (want_lab != lab || want_dist != dist || memcmp(want, out, sizeof(out))) return 8;      // every form gives the same

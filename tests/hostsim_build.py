@@ -11,8 +11,8 @@ CSRC = os.path.join(os.path.dirname(HERE), "gym_pcgrl_amd", "csrc")
 
 
 def _build(out, src, flags):
-    """(a simulator may include another one: every simulator source and every kernel header counts as a source of each)"""
-    deps = glob.glob(os.path.join(HOSTSIM, "*.cpp")) + glob.glob(os.path.join(CSRC, "*.h"))
+    """(a simulator may include another one: every simulator source and header and every kernel header counts as a source of each)"""
+    deps = glob.glob(os.path.join(HOSTSIM, "*.cpp")) + glob.glob(os.path.join(HOSTSIM, "*.h")) + glob.glob(os.path.join(CSRC, "*.h"))
     if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(d) for d in deps):
         subprocess.check_call(["g++"] + list(flags) + ["-o", out, os.path.join(HOSTSIM, src)])
     return out

@@ -2,44 +2,28 @@
 k_get_changes (planes_set_cell, csrc/pcgrl_algos.h) on the CPU lane-group simulator (tests/hostsim/sim_changes.cpp), and the expansion
 rule of changes()' fallback -- entry order (m, k, t), no-op entries -- against hand levels scored by the oracle alone."""
 import ctypes as C
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import oracle_lib
-from hostsim_build import build_sanitized, build_so
+from host_kit import config as _config, header, plain_header, prototype, run_sanitized
+from hostsim_build import build_so
 from oracle_lib import _p
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 NTILES = {"binary": 2, "zelda": 8, "sokoban": 5, "mdungeon": 8, "ddave": 7, "smb": 7}
 # the shapes of tests/test_gpu_changes.py: (problem, rows, columns)
 SHAPES = [("binary", 1, 1), ("binary", 3, 5), ("binary", 16, 32), ("binary", 16, 33), ("binary", 17, 32), ("binary", 17, 33), ("binary", 64, 64),
           ("zelda", 7, 11), ("zelda", 17, 33)]
 
 
-def _config(prob, h, w, power=None):
-    from gym_pcgrl_amd.envs import BatchedPcgrlEnv
-    env = BatchedPcgrlEnv(prob=prob, rep="wide", num_envs=1, seed=0)
-    kw = dict(width=w, height=h)
-    if power is not None:
-        kw["solver_power"] = power
-    env.adjust_param(**kw)
-    return env._config()
-
-
 def test_declared_exported_and_mirrored():
     from gym_pcgrl_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "pcgrl_hip.h")).read()
-    plain = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    assert re.search(r"\bsize_t\s+pcgrl_get_changes_bytes\s*\(\s*const\s+pcgrl_config\s*\*\s*\w+\s*,\s*int32_t\s+\w+\s*,\s*int32_t\s+\w+\s*\)\s*;", plain)
-    assert re.search(r"\bint\s+pcgrl_get_changes\s*\(\s*pcgrl_env\s*\*\s*\w+\s*,\s*const\s+uint8_t\s*\*\s*\w+\s*,\s*int32_t\s+\w+\s*,"
-                     r"\s*const\s+int32_t\s*\*\s*\w+\s*,\s*int32_t\s+\w+\s*,\s*const\s+int32_t\s*\*\s*\w+\s*,"
-                     r"\s*int32_t\s*\*\s*\w+\s*,\s*int32_t\s*\*\s*\w+\s*,\s*double\s*\*\s*\w+\s*,\s*uint8_t\s*\*\s*\w+\s*,"
-                     r"\s*void\s*\*\s*\w+\s*,\s*size_t\s+\w+\s*,\s*void\s*\*\s*\w+\s*\)\s*;", plain)
+    hdr, plain = header(), plain_header()
+    assert re.search(prototype("size_t", "pcgrl_get_changes_bytes", ["const pcgrl_config*", "int32_t", "int32_t"]), plain)
+    assert re.search(prototype("int", "pcgrl_get_changes", ["pcgrl_env*", "const uint8_t*", "int32_t", "const int32_t*", "int32_t", "const int32_t*", "int32_t*", "int32_t*",
+                                                           "double*", "uint8_t*", "void*", "size_t", "void*"]), plain)
     assert "Still 15: + pcgrl_get_changes_bytes / pcgrl_get_changes" in hdr
     L = _lib.load()
     for name in ("pcgrl_get_changes_bytes", "pcgrl_get_changes"):
@@ -134,8 +118,7 @@ def test_edit_and_restore_on_every_form(sim):
 
 def test_sanitized_stand_alone_program():
     """sim_changes.cpp with its own main(), built with the address and undefined-behaviour sanitizers and run as a program."""
-    r = subprocess.run([build_sanitized("sim_changes.cpp", "SIM_CHANGES_MAIN")], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=300)
-    assert r.returncode == 0 and r.stdout.strip().endswith("ok") and "runtime error" not in r.stdout, r.stdout[-2000:]
+    run_sanitized("sim_changes.cpp", "SIM_CHANGES_MAIN", 300)
 
 
 # ------------------------------------------------------------------ the fallback's expansion rule, through the oracle alone

@@ -5,33 +5,15 @@ drops from two blocks per CU to one (C5 steady state 49.5 -> 58 us when one extr
 and a kernel that spills pays in HBM traffic (`k_stats<sokoban>`: 95 MB of scratch writes a step until its instantiation lost the reset
 code, round 4).  The parts of csrc/pcgrl_abi.hip that hold those kernels are compiled to assembly (`hipcc -S --cuda-device-only`, side
 by side) and the `.amdhsa_` resource directives of the kernels are read."""
-import os, re, subprocess, sys
 from concurrent.futures import ThreadPoolExecutor
 import pytest
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from gym_pcgrl_amd import _lib
-
-
-def _resources(part, tmp):
-    out = os.path.join(tmp, "part%d.s" % part)
-    hipcc = os.environ.get("HIPCC", "hipcc")
-    subprocess.check_call([hipcc] + [f for f in _lib.HIPCC_FLAGS if f not in ("-shared",)] + ["-DPCGRL_PART=%d" % part, "--cuda-device-only", "-S", _lib.SOURCES[0], "-o", out],
-                          stderr=subprocess.DEVNULL)
-    text = open(out).read()
-    res = {}
-    for m in re.finditer(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", text, re.S):
-        name = subprocess.run(["c++filt", m.group(1)], capture_output=True, text=True).stdout.strip()
-        g = lambda k: int(re.search(k + r"\s+(\d+)", m.group(2)).group(1))
-        res[name.split("(")[0]] = (g("next_free_vgpr"), g("private_segment_fixed_size"))
-    return res
+from host_kit import kernel_resources
 
 
 @pytest.fixture(scope="module")
-def resources(tmp_path_factory):
-    tmp = str(tmp_path_factory.mktemp("asm"))
+def resources():
     with ThreadPoolExecutor(2) as ex:
-        stats, step = ex.map(lambda p: _resources(p, tmp), (1, 3))      # PART_STATS, PART_STEP_BINARY (csrc/pcgrl_abi.hip)
+        stats, step = ex.map(kernel_resources, (1, 3))      # PART_STATS, PART_STEP_BINARY (csrc/pcgrl_abi.hip)
     return {**stats, **step}
 
 
@@ -42,17 +24,17 @@ def _find(resources, prefix):
 
 
 def test_wide_kernel_keeps_two_blocks_per_cu(resources):
-    for name, (vgpr, scratch) in _find(resources, "void k_stats_wide<").items():
+    for name, (vgpr, _, scratch) in _find(resources, "void k_stats_wide<").items():
         assert vgpr <= 128 and scratch == 0, (name, vgpr, scratch)
 
 
 def test_fused_step_kernels_fit_without_spills(resources):
-    for name, (vgpr, scratch) in _find(resources, "void k_step<0,").items():
+    for name, (vgpr, _, scratch) in _find(resources, "void k_step<0,").items():
         assert vgpr <= 128 and scratch == 0, (name, vgpr, scratch)
 
 
 def test_statistics_kernels_do_not_spill(resources):
-    for name, (vgpr, scratch) in _find(resources, "void k_stats<").items():
+    for name, (vgpr, _, scratch) in _find(resources, "void k_stats<").items():
         # (binary on 16-row maps of 33..64 columns through the two-launch pipeline -- cast representations, no_fused -- keeps a few
         #  dwords in scratch: a rarely taken instantiation, known since round 3)
         allowed = 64 if name.startswith("void k_stats<0, 16, unsigned long>") else 0

@@ -5,16 +5,15 @@ pcgrl_get_paths_bytes / pcgrl_get_paths."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-from hostsim_build import build_sanitized, build_so
+from host_kit import config as _config, forms, header, plain_header, prototype, run_sanitized
+from hostsim_build import build_so
 from oracle_lib import _p
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 G = os.path.join(HERE, "golden")
 PROB_ID = {"binary": 0, "zelda": 1}
 # what a leg may walk on (zelda_prob.py:98, :107, :109; binary_prob.py:84): tile ids
@@ -30,11 +29,6 @@ def groups(fix):
             yield name, prob, d["maps"], d["stats"]
         else:
             yield name, prob, fix["maps_" + name], fix["stats_" + name]
-
-
-def forms(h, w):
-    """The (lane group, mask width) forms that hold a map of h rows and w columns; the first is the one the library takes."""
-    return [(g, b) for g in (16, 64) if h <= g for b in (32, 64) if w <= b]
 
 
 @pytest.fixture(scope="module")
@@ -143,8 +137,7 @@ def test_fixture_covers_what_the_issue_lists(fix):
 def test_sanitized_stand_alone_program():
     """sim_paths.cpp with its own main(), built with the address and undefined-behaviour sanitizers and run as a program: built-in
     levels through every leg on every (lane group, mask width) form, with guard words behind the rows."""
-    r = subprocess.run([build_sanitized("sim_paths.cpp", "SIM_PATHS_MAIN")], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=120)
-    assert r.returncode == 0 and r.stdout.strip().endswith("ok") and "runtime error" not in r.stdout, r.stdout[-2000:]
+    run_sanitized("sim_paths.cpp", "SIM_PATHS_MAIN", 120)
 
 
 # ------------------------------------------------------------------ check_path(): the check that owes nothing to a fixture
@@ -183,22 +176,12 @@ def test_check_path_accepts_every_fixture_leg(fix):
 
 
 # ------------------------------------------------------------------ the ABI, without a device
-def _config(prob, h, w):
-    from gym_pcgrl_amd.envs import BatchedPcgrlEnv
-    env = BatchedPcgrlEnv(prob=prob, rep="wide", num_envs=1, seed=0)
-    env.adjust_param(width=w, height=h)
-    return env._config()
-
-
 def test_declared_exported_and_mirrored():
     from gym_pcgrl_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "pcgrl_hip.h")).read()
-    plain = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    assert re.search(r"\bint32_t\s+pcgrl_get_paths_legs\s*\(\s*const\s+pcgrl_config\s*\*\s*\w+\s*\)\s*;", plain)
-    assert re.search(r"\bsize_t\s+pcgrl_get_paths_bytes\s*\(\s*const\s+pcgrl_config\s*\*\s*\w+\s*,\s*int32_t\s+\w+\s*,\s*int32_t\s+\w+\s*\)\s*;", plain)
-    assert re.search(r"\bint\s+pcgrl_get_paths\s*\(\s*pcgrl_env\s*\*\s*\w+\s*,\s*const\s+uint8_t\s*\*\s*\w+\s*,\s*int32_t\s+\w+\s*,\s*int32_t\s+\w+\s*,"
-                     r"\s*int16_t\s*\*\s*\w+\s*,\s*int32_t\s*\*\s*\w+\s*,\s*int32_t\s*\*\s*\w+\s*,"
-                     r"\s*void\s*\*\s*\w+\s*,\s*size_t\s+\w+\s*,\s*void\s*\*\s*\w+\s*\)\s*;", plain)
+    hdr, plain = header(), plain_header()
+    assert re.search(prototype("int32_t", "pcgrl_get_paths_legs", ["const pcgrl_config*"]), plain)
+    assert re.search(prototype("size_t", "pcgrl_get_paths_bytes", ["const pcgrl_config*", "int32_t", "int32_t"]), plain)
+    assert re.search(prototype("int", "pcgrl_get_paths", ["pcgrl_env*", "const uint8_t*", "int32_t", "int32_t", "int16_t*", "int32_t*", "int32_t*", "void*", "size_t", "void*"]), plain)
     for cited in ("helper.py:222-237", "helper.py:250-264", "zelda_prob.py:91-110", "Still 15: + pcgrl_get_paths_legs / pcgrl_get_paths_bytes / pcgrl_get_paths"):
         assert cited in hdr, cited
     L = _lib.load()

@@ -1,45 +1,25 @@
 """pcgrl_render (level pictures drawn on the device): what can be checked without a GPU -- the entry point and its struct in the
 header, the library and the ctypes mirror; the grid-shape rule; the kernel's scratch use read from the compiler's assembly."""
 import ctypes as C
-import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from host_kit import header, kernel_resources, prototype, struct_fields
 
 _C_TYPES = {"const int32_t*": C.c_void_p, "const uint8_t*": C.c_void_p, "uint8_t*": C.c_void_p, "int32_t": C.c_int32}
 
 
-def _header_desc_fields():
-    """[(name, ctypes type)] of pcgrl_render_desc, parsed from the header (comments dropped, one declarator list per statement)."""
-    hdr = open(os.path.join(ROOT, "include", "pcgrl_hip.h")).read()
-    body = re.search(r"typedef struct pcgrl_render_desc \{(.*?)\} pcgrl_render_desc;", hdr, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = []
-    for decl in body.split(";"):
-        decl = " ".join(decl.split())
-        if not decl:
-            continue
-        m = re.match(r"(const\s+)?(\w+)\s*(\*?)\s*(.*)$", decl)
-        base = ("const " if m.group(1) else "") + m.group(2)
-        for i, name in enumerate(x.strip() for x in m.group(4).split(",")):
-            ptr = m.group(3) if i == 0 else ("*" if name.startswith("*") else "")
-            fields.append((name.lstrip("* "), _C_TYPES[base + ptr]))
-    return fields
-
-
 def test_entry_point_is_declared_exported_and_mirrored():
     from gym_pcgrl_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "pcgrl_hip.h")).read()
-    assert re.search(r"\bint\s+pcgrl_render\s*\(\s*pcgrl_env\s*\*\s*\w+\s*,\s*const\s+pcgrl_render_desc\s*\*\s*\w+\s*,\s*void\s*\*\s*\w+\s*\)\s*;", hdr)
+    hdr = header()
+    assert re.search(prototype("int", "pcgrl_render", ["pcgrl_env*", "const pcgrl_render_desc*", "void*"]), hdr)
     for cited in ("pcgrl_env.py:161-175", "problem.py:134-156", "narrow_rep.py:128-142", "turtle_rep.py:142"):
         assert cited in hdr, cited
     assert "pcgrl_render" in _lib.EXPORTS
     L = _lib.load()                      # (load() itself insists on every name of EXPORTS)
     assert hasattr(L, "pcgrl_render")
-    fields = _header_desc_fields()
+    fields = struct_fields("pcgrl_render_desc", _C_TYPES)
     assert [n for n, _ in fields] == ["indices", "count", "tiles", "tile_size", "border_x", "border_y", "border_tile", "cursor",
                                       "grid_rows", "grid_cols", "out"]
     assert [n for n, _ in _lib.RenderDesc._fields_] == [n for n, _ in fields]
@@ -79,18 +59,8 @@ def test_grid_shape_rule():
     assert picture_shape(14, 14, (1, 1), 16, 5, (3, 2)) == (768, 512, 3)
 
 
-def test_render_kernel_uses_no_scratch(tmp_path):
+def test_render_kernel_uses_no_scratch():
     """The core part of csrc/pcgrl_abi.hip compiled to gfx950 assembly: both forms of k_render report no private segment."""
-    from gym_pcgrl_amd import _lib
-    out = str(tmp_path / "part0.s")
-    hipcc = os.environ.get("HIPCC", "hipcc")
-    subprocess.check_call([hipcc] + [f for f in _lib.HIPCC_FLAGS if f != "-shared"] + ["-DPCGRL_PART=0", "--cuda-device-only", "-S", _lib.SOURCES[0], "-o", out],
-                          stderr=subprocess.DEVNULL)
-    text = open(out).read()
-    seen = {}
-    for m in re.finditer(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", text, re.S):
-        name = subprocess.run(["c++filt", m.group(1)], capture_output=True, text=True).stdout.strip().split("(")[0]
-        if name.startswith("void k_render<"):
-            seen[name] = int(re.search(r"private_segment_fixed_size\s+(\d+)", m.group(2)).group(1))
+    seen = {name: scratch for name, (_, _, scratch) in kernel_resources(0).items() if name.startswith("void k_render<")}
     assert len(seen) == 2, sorted(seen)
     assert all(v == 0 for v in seen.values()), seen

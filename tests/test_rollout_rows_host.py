@@ -1,46 +1,25 @@
 """pcgrl_bind_row (the step kernels write the rollout row): what can be checked without a GPU -- the entry point and its struct in
 the header, the library and the ctypes mirror; the collector's choice between the two loops; the argument checks."""
 import ctypes as C
-import os
 import re
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from host_kit import header, prototype, struct_fields
 
 _C_TYPES = {"int64_t*": C.c_void_p, "double*": C.c_void_p, "uint8_t*": C.c_void_p, "const uint8_t*": C.c_void_p, "int32_t*": C.c_void_p,
             "int32_t": C.c_int32}
 
 
-def _header_row_fields():
-    """[(name, ctypes type)] of pcgrl_row, parsed from the header (one declarator list per line, comments dropped)."""
-    hdr = open(os.path.join(ROOT, "include", "pcgrl_hip.h")).read()
-    body = re.search(r"typedef struct pcgrl_row \{(.*?)\} pcgrl_row;", hdr, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = []
-    for decl in body.split(";"):
-        decl = " ".join(decl.split())
-        if not decl:
-            continue
-        m = re.match(r"(const\s+)?(\w+)\s*(\*?)\s*(.*)$", decl)
-        base = (m.group(1) or "").strip() + (" " if m.group(1) else "") + m.group(2)
-        first_ptr = m.group(3)
-        for i, name in enumerate(x.strip() for x in m.group(4).split(",")):
-            ptr = first_ptr if i == 0 else ("*" if name.startswith("*") else "")
-            fields.append((name.lstrip("* "), _C_TYPES[base + ptr]))
-    return fields
-
-
 def test_entry_point_is_declared_exported_and_mirrored():
     from gym_pcgrl_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "pcgrl_hip.h")).read()
-    assert re.search(r"\bint\s+pcgrl_bind_row\s*\(\s*pcgrl_env\s*\*\s*\w+\s*,\s*const\s+pcgrl_row\s*\*\s*\w+\s*\)\s*;", hdr)
+    assert re.search(prototype("int", "pcgrl_bind_row", ["pcgrl_env*", "const pcgrl_row*"]), header())
     assert "pcgrl_bind_row" in _lib.EXPORTS
     L = _lib.load()                      # (load() itself insists on every name of EXPORTS)
     assert hasattr(L, "pcgrl_bind_row")
     assert L.pcgrl_abi_version() == _lib.ABI_VERSION == 15         # an addition within the version: found by its symbol
-    fields = _header_row_fields()
+    fields = struct_fields("pcgrl_row", _C_TYPES)
     assert [n for n, _ in fields] == list(_lib.ROW_FIELDS) + ["actions_i64"]
     assert [n for n, _ in _lib.Row._fields_] == [n for n, _ in fields]
 

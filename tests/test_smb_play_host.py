@@ -8,8 +8,9 @@ import re
 import numpy as np
 import pytest
 
+from host_kit import MOVES_PARAMS, config as _config, header, plain_header, prototype
+
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 G = os.path.join(HERE, "golden")
 FILES = ["4x9_p200", "6x12_p10000", "8x24_p400", "10x30_p10000", "14x40_p2500", "14x114_p1500", "14x114_p10000"]
 EDGES = ["w123", "w250", "h3", "p16383", "q4095"]
@@ -139,15 +140,6 @@ def test_replay_rules():
 
 
 # ------------------------------------------------------------------ the ABI, without a device
-def _config(prob, h, w, power=None):
-    from gym_pcgrl_amd.envs import BatchedPcgrlEnv
-    env = BatchedPcgrlEnv(prob=prob, rep="wide", num_envs=1, seed=0)
-    if power is not None:
-        env._prob._solver_power = int(power)
-    env.adjust_param(width=w, height=h)
-    return env._config()
-
-
 def _bytes(cfg, count, max_len):
     from gym_pcgrl_amd import _lib
     return int(_lib.load().pcgrl_get_smb_play_bytes(C.byref(cfg), count, max_len))
@@ -155,12 +147,9 @@ def _bytes(cfg, count, max_len):
 
 def test_declared_exported_and_mirrored():
     from gym_pcgrl_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "pcgrl_hip.h")).read()
-    plain = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    assert re.search(r"\bsize_t\s+pcgrl_get_smb_play_bytes\s*\(\s*const\s+pcgrl_config\s*\*\s*\w+\s*,\s*int32_t\s+\w+\s*,\s*int32_t\s+\w+\s*\)\s*;", plain)
-    assert re.search(r"\bint\s+pcgrl_get_smb_play\s*\(\s*pcgrl_env\s*\*\s*\w+\s*,\s*const\s+uint8_t\s*\*\s*\w+\s*,\s*int32_t\s+\w+\s*,\s*int32_t\s+\w+\s*,"
-                     r"\s*int8_t\s*\*\s*\w+\s*,\s*int32_t\s*\*\s*\w+\s*,\s*int8_t\s*\*\s*\w+\s*,\s*int32_t\s*\*\s*\w+\s*,"
-                     r"\s*void\s*\*\s*\w+\s*,\s*size_t\s+\w+\s*,\s*void\s*\*\s*\w+\s*\)\s*;", plain)
+    hdr, plain = header(), plain_header()
+    assert re.search(prototype("size_t", "pcgrl_get_smb_play_bytes", ["const pcgrl_config*", "int32_t", "int32_t"]), plain)
+    assert re.search(prototype("int", "pcgrl_get_smb_play", MOVES_PARAMS), plain)
     for cited in ("smb_prob.py:90-124", "engine.py:43-49", "Still 15: + pcgrl_get_smb_play_bytes / pcgrl_get_smb_play"):
         assert cited in hdr, cited
     L = _lib.load()

@@ -8,11 +8,11 @@ import re
 import numpy as np
 import pytest
 
+from host_kit import MOVES_PARAMS, config as _config, header, plain_header, prototype
 from hostsim_build import build_so
 from oracle_lib import _p
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 G = os.path.join(HERE, "golden")
 SIZES = ["4x6", "5x5", "5x6", "6x6", "7x7", "7x8", "8x8"]
 NHAND = 4
@@ -161,16 +161,6 @@ def test_replay_rules():
 
 
 # ------------------------------------------------------------------ the ABI, without a device
-def _config(prob, h, w, power=None):
-    from gym_pcgrl_amd.envs import BatchedPcgrlEnv
-    env = BatchedPcgrlEnv(prob=prob, rep="wide", num_envs=1, seed=0)
-    kw = dict(width=w, height=h)
-    if power is not None and prob != "smb":
-        kw["solver_power"] = power
-    env.adjust_param(**kw)
-    return env._config()
-
-
 def _bytes(cfg, count, max_len):
     from gym_pcgrl_amd import _lib
     return int(_lib.load().pcgrl_get_solution_bytes(C.byref(cfg), count, max_len))
@@ -178,12 +168,9 @@ def _bytes(cfg, count, max_len):
 
 def test_declared_exported_and_mirrored():
     from gym_pcgrl_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "pcgrl_hip.h")).read()
-    plain = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    assert re.search(r"\bsize_t\s+pcgrl_get_solution_bytes\s*\(\s*const\s+pcgrl_config\s*\*\s*\w+\s*,\s*int32_t\s+\w+\s*,\s*int32_t\s+\w+\s*\)\s*;", plain)
-    assert re.search(r"\bint\s+pcgrl_get_solution\s*\(\s*pcgrl_env\s*\*\s*\w+\s*,\s*const\s+uint8_t\s*\*\s*\w+\s*,\s*int32_t\s+\w+\s*,\s*int32_t\s+\w+\s*,"
-                     r"\s*int8_t\s*\*\s*\w+\s*,\s*int32_t\s*\*\s*\w+\s*,\s*int8_t\s*\*\s*\w+\s*,\s*int32_t\s*\*\s*\w+\s*,"
-                     r"\s*void\s*\*\s*\w+\s*,\s*size_t\s+\w+\s*,\s*void\s*\*\s*\w+\s*\)\s*;", plain)
+    hdr, plain = header(), plain_header()
+    assert re.search(prototype("size_t", "pcgrl_get_solution_bytes", ["const pcgrl_config*", "int32_t", "int32_t"]), plain)
+    assert re.search(prototype("int", "pcgrl_get_solution", MOVES_PARAMS), plain)
     for cited in ("sokoban_prob.py:133-145", "engine.py:38-44", "Still 15: + pcgrl_get_solution_bytes / pcgrl_get_solution"):
         assert cited in hdr, cited
     L = _lib.load()

@@ -4,23 +4,17 @@ side of pcgrl_tile_graph_bytes / pcgrl_tile_graph, the argument normalisation of
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-from hostsim_build import build_sanitized, build_so
+from host_kit import config as _config, forms, header, plain_header, prototype, run_sanitized, struct_fields
+from hostsim_build import build_so
 from oracle_lib import _p
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 G = os.path.join(HERE, "golden")
 COLS = ("passable", "source_tiles", "reach_tiles", "sources", "regions", "longest", "reach", "source")      # levels_<g>
-
-
-def forms(h, w):
-    """The (lane group, mask width) forms that hold a map of h rows and w columns; the first is the one the library takes."""
-    return [(g, b) for g in (16, 64) if h <= g for b in (32, 64) if w <= b]
 
 
 @pytest.fixture(scope="module")
@@ -117,39 +111,21 @@ def test_status_bits_and_optional_outputs_on_the_simulator(sim):
 def test_sanitized_stand_alone_program():
     """sim_tile_graph.cpp with its own main(), built with the address and undefined-behaviour sanitizers and run as a program: built-in
     levels on every (lane group, mask width) form, with guard words around the maps."""
-    r = subprocess.run([build_sanitized("sim_tile_graph.cpp", "SIM_TILE_GRAPH_MAIN")], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=300)
-    assert r.returncode == 0 and r.stdout.strip().endswith("ok") and "runtime error" not in r.stdout, r.stdout[-2000:]
+    run_sanitized("sim_tile_graph.cpp", "SIM_TILE_GRAPH_MAIN", 300)
 
 
 # ------------------------------------------------------------------ the ABI, without a device
-def _config(prob, h, w):
-    from gym_pcgrl_amd.envs import BatchedPcgrlEnv
-    env = BatchedPcgrlEnv(prob=prob, rep="wide", num_envs=1, seed=0)
-    env.adjust_param(width=w, height=h)
-    return env._config()
-
-
 def test_declared_exported_and_mirrored():
     from gym_pcgrl_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "pcgrl_hip.h")).read()
-    plain = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    assert re.search(r"\bsize_t\s+pcgrl_tile_graph_bytes\s*\(\s*const\s+pcgrl_config\s*\*\s*\w+\s*,\s*int32_t\s+\w+\s*\)\s*;", plain)
-    assert re.search(r"\bint\s+pcgrl_tile_graph\s*\(\s*pcgrl_env\s*\*\s*\w+\s*,\s*const\s+pcgrl_tile_graph_desc\s*\*\s*\w+\s*,\s*void\s*\*\s*\w+\s*,"
-                     r"\s*size_t\s+\w+\s*,\s*void\s*\*\s*\w+\s*\)\s*;", plain)
+    hdr, plain = header(), plain_header()
+    assert re.search(prototype("size_t", "pcgrl_tile_graph_bytes", ["const pcgrl_config*", "int32_t"]), plain)
+    assert re.search(prototype("int", "pcgrl_tile_graph", ["pcgrl_env*", "const pcgrl_tile_graph_desc*", "void*", "size_t", "void*"]), plain)
     for cited in ("helper.py:170-296", "Still 15: + pcgrl_tile_graph_desc / pcgrl_tile_graph_bytes / pcgrl_tile_graph", "renamed to one single value"):
         assert cited in hdr, cited
     # the struct mirror: field order, types and size against the header
-    body = re.search(r"typedef\s+struct\s+pcgrl_tile_graph_desc\s*\{(.*?)\}\s*pcgrl_tile_graph_desc\s*;", plain, re.S).group(1)
-    fields = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        base = re.match(r"(const\s+)?(\w+)", decl).group(2)
-        for part in decl[re.match(r"(const\s+)?(\w+)", decl).end():].split(","):
-            fields.append((part.replace("*", "").strip(), "ptr" if "*" in part else base))
-    ctype = {"ptr": C.c_void_p, "int32_t": C.c_int32, "uint32_t": C.c_uint32}
-    assert [(n, ctype[t]) for n, t in fields] == list(_lib.TileGraphDesc._fields_)
+    ptr = C.c_void_p
+    fields = struct_fields("pcgrl_tile_graph_desc", {"const uint8_t*": ptr, "const int32_t*": ptr, "int32_t*": ptr, "int16_t*": ptr, "int32_t": C.c_int32, "uint32_t": C.c_uint32})
+    assert fields == list(_lib.TileGraphDesc._fields_)
     assert [n for n, _ in fields] == ["maps", "count", "passable", "source_tiles", "reach_tiles", "sources", "regions_out", "longest_out",
                                       "labels_out", "dist_out", "reach_out", "source_out"]
     assert C.sizeof(_lib.TileGraphDesc) == 80 and _lib.TileGraphDesc.sources.offset == 24 and _lib.TileGraphDesc.source_out.offset == 72
