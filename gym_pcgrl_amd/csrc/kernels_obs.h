@@ -62,7 +62,7 @@ struct ObsBytes {
 // ---- general routine: any depth, any size; `rem` = byte offset inside the image of environment e
 template <class Src>
 __device__ __forceinline__ int obs_cell(const Src& src, const ObsView& V, int e, int i, uint32_t mg_ow, int oy, int ox) {
-    const int r = (int)__umulhi((uint32_t)i, mg_ow), c = i - r * V.ow;
+    const int r = V.ow == 1 ? i : (int)__umulhi((uint32_t)i, mg_ow), c = i - r * V.ow;       // (obs_magic(1) is 0: no 32-bit factor gives i / 1)
     const int y = r + oy, x = c + ox;
     if ((unsigned)y >= (unsigned)V.H || (unsigned)x >= (unsigned)V.W) return V.pad;
     return src.tile(e, y, x);
@@ -291,6 +291,8 @@ __device__ __forceinline__ void obs_write_block(const Src& src, const ObsView& V
     for (int e = __builtin_amdgcn_readfirstlane(tid >> 6); e < ne; e += nthreads >> 6) obs_write_env_lean(src, V, pos, e, tid & 63);
 }
 
+#define OBS_EPB 64       /* environments per block of k_obs (a multiple of 16: every block's stretch starts 16-byte aligned) */
+#ifndef PCGRL_OBS_HOST_SIM      // (tests/hostsim/sim_obs.cpp compiles the routines above for the CPU: the kernels stay out of that)
 // The observation target of a handle (pcgrl_bind_observation): part of DevBufs.
 __device__ __forceinline__ ObsView obs_view(const PcgrlParams& P, const ObsSpec& S, int e0) {
     ObsView V;
@@ -299,7 +301,6 @@ __device__ __forceinline__ ObsView obs_view(const PcgrlParams& P, const ObsSpec&
     return V;
 }
 
-#define OBS_EPB 64       /* environments per block of k_obs (a multiple of 16: every block's stretch starts 16-byte aligned) */
 // SRC 0: byte map; 1: one u32 plane (binary); 2: one u64 plane (binary, maps wider than 32 columns); 3: three u32 planes (zelda,
 // sokoban, mdungeon, ddave on maps of at most 32 columns).  With planes the block first copies the planes and cursors of its
 // environments into LDS (one coalesced burst; dynamic LDS: OBS_EPB * (bytes of an environment's planes + 2)): a piece is a chain of
@@ -357,3 +358,4 @@ __global__ __launch_bounds__(256) void k_obs_huge(PcgrlParams P, DevBufs B, ObsS
         else for (int k = 0; k < nb; k++) S.out[o + k] = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
     }
 }
+#endif  // PCGRL_OBS_HOST_SIM
