@@ -494,9 +494,10 @@ void sim_mt_random(const uint32_t* key624, int count, double* out) {
     for (int i = 0; i < count; i++) out[i] = mt_random(ring, cur);
 }
 // the reset kernel's parallel generation (reset_env.h wave_reset_env), emulated lane by lane: a round makes the words of 113 cells --
-// lane l those of cell c0 + l, lanes 0..48 also those of cell c0 + 64 + l -- with every read before every write
-void sim_mt_mapgen(const uint32_t* key624, const double* prob, int ntiles, int w, int h, uint8_t* tiles, int* xy, uint32_t* ring_out, int* cur_out) {
-    uint32_t mt[624]; memcpy(mt, key624, sizeof(mt)); int cur = 0;
+// lane l those of cell c0 + l, lanes 0..48 also those of cell c0 + 64 + l -- with every read before every write.  `ring624` is a lazy
+// ring with its cursor at `cur0` (0 with a freshly seeded state).
+void sim_mt_mapgen(const uint32_t* ring624, int cur0, const double* prob, int ntiles, int w, int h, uint8_t* tiles, int* xy, uint32_t* ring_out, int* cur_out) {
+    uint32_t mt[624]; memcpy(mt, ring624, sizeof(mt)); int cur = cur0;
     double cdf[8]; pcgrl_build_cdf(prob, ntiles, cdf);
     int cells = w * h;
     for (int c0 = 0; c0 < cells; c0 += 113) {

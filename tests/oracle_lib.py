@@ -86,6 +86,10 @@ def lib(big=False):
         L.orc_tile_prob.restype = C.c_double
         L.orc_rollout.argtypes = [C.c_void_p] + [C.c_void_p, C.c_int] + [C.c_void_p] * 6
         L.orc_rollout.restype = C.c_int
+        L.orc_rollout_stream.argtypes = L.orc_rollout.argtypes + [C.c_void_p]
+        L.orc_rollout_stream.restype = C.c_int
+        L.orc_rep_cursor.argtypes = [C.c_void_p]
+        L.orc_rep_cursor.restype = C.c_int
         L.orc_get_stats.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.orc_range_reward.argtypes = [C.c_double] * 4
         L.orc_range_reward.restype = C.c_double
@@ -244,8 +248,14 @@ class OracleEnv:
         inf["max_changes"] = self.max_changes
         return self.obs(), r.value, bool(d.value), inf
 
-    def rollout(self, actions, want_maps=True, want_heat=True):
-        """actions [T,k<=9] int32 -> dict of per-step arrays (auto-reset semantics)."""
+    def rep_cursor(self):
+        """The ring cursor of the representation stream: words drawn since seed(), mod 624."""
+        return lib(self._big).orc_rep_cursor(self._h)
+
+    def rollout(self, actions, want_maps=True, want_heat=True, want_stream=False):
+        """actions [T,k<=9] int32 -> dict of per-step arrays (auto-reset semantics).  want_stream: also stream [T, 4] -- the ring cursor
+        of the representation stream and the cursor position (x, y) after the step, before the reset of an episode that ended there, and
+        the ring cursor after that reset."""
         L = lib(self._big)
         actions = np.asarray(actions, dtype=np.int32)
         if actions.ndim == 1:
@@ -262,5 +272,9 @@ class OracleEnv:
         rew = np.zeros(T, np.float64)
         done = np.zeros(T, np.uint8)
         info = np.zeros((T, ni), np.int64)
-        ended = L.orc_rollout(self._h, _p(actions), T, _p(maps), _p(pos), _p(heat), _p(rew), _p(done), _p(info))
-        return dict(maps=maps, pos=pos, heatmap=heat, reward=rew, done=done.astype(bool), info=info, episodes=ended)
+        stream = np.zeros((T, 4), np.int32) if want_stream else None
+        ended = L.orc_rollout_stream(self._h, _p(actions), T, _p(maps), _p(pos), _p(heat), _p(rew), _p(done), _p(info), _p(stream))
+        out = dict(maps=maps, pos=pos, heatmap=heat, reward=rew, done=done.astype(bool), info=info, episodes=ended)
+        if want_stream:
+            out["stream"] = stream
+        return out

@@ -25,7 +25,7 @@ def sim():
     L.sim_range_reward.restype = C.c_double
     L.sim_mt_randint.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     L.sim_mt_random.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-    L.sim_mt_mapgen.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.sim_mt_mapgen.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     return L
 
 
@@ -373,7 +373,7 @@ def test_parallel_mapgen_matches_numpy(sim):
             xy = np.zeros(2, np.int32)
             ring = np.zeros(624, np.uint32)
             cur = C.c_int()
-            sim.sim_mt_mapgen(_p(key), _p(np.ascontiguousarray(p)), nt, w, h, _p(tiles), _p(xy), _p(ring), C.byref(cur))
+            sim.sim_mt_mapgen(_p(key), 0, _p(np.ascontiguousarray(p)), nt, w, h, _p(tiles), _p(xy), _p(ring), C.byref(cur))
             assert np.array_equal(tiles, d[name][si])
             rs = np.random.RandomState()
             rs.set_state(("MT19937", key, 624))
@@ -386,12 +386,52 @@ def test_parallel_mapgen_matches_numpy(sim):
     ring = np.zeros(624, np.uint32)
     cur = C.c_int()
     p = np.array([0.37, 0.63])
-    sim.sim_mt_mapgen(_p(key), _p(p), 2, 64, 64, _p(tiles), _p(xy), _p(ring), C.byref(cur))
+    sim.sim_mt_mapgen(_p(key), 0, _p(p), 2, 64, 64, _p(tiles), _p(xy), _p(ring), C.byref(cur))
     rs = np.random.RandomState()
     rs.set_state(("MT19937", key, 624))
     exp = rs.choice([0, 1], size=(64, 64), p=[0.37, 0.63]).astype(np.uint8)
     assert np.array_equal(tiles, exp)
     assert xy[0] == rs.randint(64) and xy[1] == rs.randint(64)
+
+
+@pytest.mark.parametrize("cells", [64, 65, 112, 113, 114])
+def test_parallel_mapgen_rounds_from_any_cursor(sim, cells):
+    """The 113-cell rounds of wave_reset_env (nA / nB: 64 cells -- nB = 0; 65 -- nB = 1; 112 -- nB = 48; 113 -- nB = 49, one full round;
+    114 -- a second round of one cell) started in the middle of a lazy ring: from cursors 0, 1, 511 and 623, and from those at which the
+    round's own words, the second batch (128 words on) or the words 397 on straddle slot 623 -> 0.  Tiles, the cursor position drawn
+    after them, the ring left behind (stream_model's lazy-ring image) and the cursor, against numpy."""
+    import stream_model as sm
+    d = np.load(os.path.join(G, "rng.npz"))
+    w, h = cells, 1
+    p = np.array([0.3, 0.7])
+    words = 2 * cells
+    cursors = {0, 1, 511, 623}
+    for edge in (624, 624 - 128, 624 - 397):          # the stretch [cur + off, cur + off + words) crosses the wrap: at its first, a middle, its last word
+        cursors |= {(edge - k) % 624 for k in (1, 2, words // 2, words - 1, min(words, 226) - 1)}
+    for si in (0, 1):
+        m = sm.StreamModel(int(d["seeds"][si]), w, h, "narrow")
+        assert np.array_equal(m.ring_image(), d["mt_key"][si])
+        for cur0 in sorted(cursors):
+            m.seed(int(d["seeds"][si]))
+            m.rs.random_sample(312)          # a lap first: both generations of the lazy ring are made words
+            m.words = 624
+            if cur0:
+                m.rs.randint(0, 2 ** 32, size=cur0, dtype=np.uint32)          # one word each
+                m.words += cur0
+            assert m._pos() == cur0 == m.cursor
+            ring0 = np.ascontiguousarray(m.ring_image())
+            tiles = np.zeros((h, w), np.uint8)
+            xy = np.zeros(2, np.int32)
+            ring = np.zeros(624, np.uint32)
+            cur = C.c_int()
+            sim.sim_mt_mapgen(_p(ring0), cur0, _p(p), 2, w, h, _p(tiles), _p(xy), _p(ring), C.byref(cur))
+            exp = m.rs.choice([0, 1], size=(h, w), p=p).astype(np.uint8)
+            m.words += words
+            c0, kx, ky, x, y = m.draw_xy()
+            assert np.array_equal(tiles, exp), (cells, si, cur0)
+            assert (xy[0], xy[1]) == (x, y), (cells, si, cur0)
+            assert cur.value == m.cursor, (cells, si, cur0)
+            assert np.array_equal(ring, m.ring_image()), (cells, si, cur0, np.nonzero(ring != m.ring_image())[0])
 
 
 def test_general_searches_vs_golden(sim):
