@@ -91,7 +91,18 @@ class TileGraphDesc(C.Structure):
                 ("dist_out", C.c_void_p), ("reach_out", C.c_void_p), ("source_out", C.c_void_p)]
 
 
-ABI_VERSION = 15         # include/pcgrl_hip.h PCGRL_ABI_VERSION (pcgrl_bind_row, pcgrl_render, pcgrl_get_stats, pcgrl_get_solution, pcgrl_get_playthrough, pcgrl_get_smb_play, pcgrl_get_paths, pcgrl_get_changes, pcgrl_tile_graph are additions within 15: found by their symbols)
+MAX_OFFSETS = 16         # include/pcgrl_hip.h PCGRL_MAX_OFFSETS
+
+
+# include/pcgrl_hip.h pcgrl_tile_local_desc: what pcgrl_tile_local reads and writes (device pointers; an output None = not wanted)
+class TileLocalDesc(C.Structure):
+    _fields_ = [("maps", C.c_void_p), ("count", C.c_int32), ("from_tiles", C.c_uint32), ("floor_tiles", C.c_uint32), ("group_tiles", C.c_uint32),
+                ("group_min", C.c_int32), ("group_max", C.c_int32), ("noffsets", C.c_int32), ("offsets", (C.c_int8 * 2) * MAX_OFFSETS),
+                ("counts_out", C.c_void_p), ("floor_dist_out", C.c_void_p), ("floor_map_out", C.c_void_p), ("grouping_out", C.c_void_p),
+                ("group_map_out", C.c_void_p), ("changes_out", C.c_void_p)]
+
+
+ABI_VERSION = 15         # include/pcgrl_hip.h PCGRL_ABI_VERSION (pcgrl_bind_row, pcgrl_render, pcgrl_get_stats, pcgrl_get_solution, pcgrl_get_playthrough, pcgrl_get_smb_play, pcgrl_get_paths, pcgrl_get_changes, pcgrl_tile_graph, pcgrl_tile_local are additions within 15: found by their symbols)
 EXPORTS = ("pcgrl_abi_version", "pcgrl_error_string", "pcgrl_last_hip_error", "pcgrl_query_layout", "pcgrl_create",
            "pcgrl_destroy", "pcgrl_bind", "pcgrl_configure", "pcgrl_seed", "pcgrl_set_tile_probs", "pcgrl_reset",
            "pcgrl_step", "pcgrl_set_maps", "pcgrl_observe", "pcgrl_action_map", "pcgrl_status", "pcgrl_profile",
@@ -101,7 +112,8 @@ EXPORTS = ("pcgrl_abi_version", "pcgrl_error_string", "pcgrl_last_hip_error", "p
            "pcgrl_bind_row", "pcgrl_render", "pcgrl_get_stats_bytes", "pcgrl_get_stats", "pcgrl_get_reward",
            "pcgrl_get_solution_bytes", "pcgrl_get_solution", "pcgrl_get_playthrough_bytes", "pcgrl_get_playthrough",
            "pcgrl_get_smb_play_bytes", "pcgrl_get_smb_play", "pcgrl_get_paths_legs", "pcgrl_get_paths_bytes", "pcgrl_get_paths",
-           "pcgrl_get_changes_bytes", "pcgrl_get_changes", "pcgrl_tile_graph_bytes", "pcgrl_tile_graph")
+           "pcgrl_get_changes_bytes", "pcgrl_get_changes", "pcgrl_tile_graph_bytes", "pcgrl_tile_graph",
+           "pcgrl_tile_local_bytes", "pcgrl_tile_local")
 NPHASE = 6
 # the six intervals between the seven event marks of a step; sokoban: update, stats, reset, solver, reset2, solver2;
 # other problems: update, stats(+resets), -, reset (only with PCGRL_INLINE_RESET=0), -, -
@@ -237,6 +249,9 @@ def load():
     L.pcgrl_tile_graph_bytes.restype = C.c_size_t
     # handle, desc, work, work_bytes, stream
     L.pcgrl_tile_graph.argtypes = [C.c_void_p, C.POINTER(TileGraphDesc), C.c_void_p, C.c_size_t, C.c_void_p]
+    L.pcgrl_tile_local_bytes.argtypes = [C.POINTER(Config), C.c_int32]
+    L.pcgrl_tile_local_bytes.restype = C.c_size_t
+    L.pcgrl_tile_local.argtypes = [C.c_void_p, C.POINTER(TileLocalDesc), C.c_void_p, C.c_size_t, C.c_void_p]
     L.pcgrl_action_map.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pcgrl_step_flat.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.pcgrl_selftest_heap.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -88,6 +88,7 @@
 #include "kernels_changes.h"      // (after kernels_evaluate.h: eval_stage_map, the job source of k_get_stats_search)
 #include "kernels_paths.h"
 #include "kernels_tile_graph.h"
+#include "kernels_tile_local.h"
 #include "kernels_moves.h"
 #include "kernels_smb_play.h"     // (after kernels_moves.h: SolOut)
 #include "search_big.h"
@@ -636,6 +637,7 @@ PCGRL_LOCAL int launch_get_stats(pcgrl_env* h, const uint8_t* maps, int count, i
 PCGRL_LOCAL int launch_get_stats_search(pcgrl_env* h, const uint8_t* maps, int32_t* rows_out, int32_t* head, const int32_t* jobs, SokNode* pools, int blocks, hipStream_t st);
 PCGRL_LOCAL int launch_get_paths(pcgrl_env* h, const uint8_t* maps, int count, int max_len, int16_t* cells_out, int32_t* length_out, int32_t* rows_out, hipStream_t st);
 PCGRL_LOCAL int launch_tile_graph(pcgrl_env* h, const pcgrl_tile_graph_desc& D, hipStream_t st);
+PCGRL_LOCAL int launch_tile_local(pcgrl_env* h, const pcgrl_tile_local_desc& D, hipStream_t st);
 struct ChangesArgs {      // pcgrl_get_changes' arguments as its launches take them; chunk / nchunks / grid_cap: the host's cut into work items
     const uint8_t* maps; int count; const int32_t* cells; int ncells; const int32_t* start_rows;
     int32_t* base_rows; int32_t* rows; double* reward; uint8_t* over;
@@ -822,6 +824,18 @@ PCGRL_LOCAL int launch_tile_graph(pcgrl_env* h, const pcgrl_tile_graph_desc& D, 
     return with_lanes(P.group, P.mask_bytes, [&](auto g, auto m) {
         return launch<k_tile_graph<g(), type_of<decltype(m)>>>(h, G.grid, PCGRL_BLOCK, G.lds, st, P, D, h->B.status);
     });
+}
+// pcgrl_tile_local (kernels_tile_local.h): map_grid's shape for the lane group the map's width asks for; the stage only where the map fits it
+PCGRL_LOCAL int launch_tile_local(pcgrl_env* h, const pcgrl_tile_local_desc& D, hipStream_t st) {
+    const int W = h->P.width, H = h->P.height;
+    const bool staged = tl_staged(W, H);
+    const int group = tl_group(W, H), per_block = (PCGRL_BLOCK / 64) * (64 / group);
+    const long long blocks = ((long long)D.count + per_block - 1) / per_block;
+    const int grid = (int)(blocks < 8192 ? blocks : 8192);
+    const size_t lds = staged ? (size_t)per_block * reset_tile_bytes(W * H) : 0;
+    if (!staged) return launch<k_tile_local<64, false>>(h, grid, PCGRL_BLOCK, lds, st, W, H, D, h->B.status);
+    if (group == 16) return launch<k_tile_local<16, true>>(h, grid, PCGRL_BLOCK, lds, st, W, H, D, h->B.status);
+    return launch<k_tile_local<64, true>>(h, grid, PCGRL_BLOCK, lds, st, W, H, D, h->B.status);
 }
 // pcgrl_get_changes, first launch (kernels_changes.h): launch_get_stats' stage and grid over the (level, chunk of cells) items
 PCGRL_LOCAL int launch_get_changes(pcgrl_env* h, const ChangesArgs& A, int32_t* head, int32_t* jobs, hipStream_t st) {
@@ -1981,6 +1995,25 @@ int pcgrl_tile_graph(pcgrl_env* h, const pcgrl_tile_graph_desc* d, void* work, s
     if (int rc = readout_check(h, ptrs, d ? d->count : 0, 1, work, work_bytes, h && d ? pcgrl_tile_graph_bytes(&h->cfg, d->count) : 0)) return rc;
     DeviceGuard guard(h->device);
     return launch_tile_graph(h, *d, (hipStream_t)stream);
+}
+
+// ---- pcgrl_tile_local (kernels_tile_local.h, tile_local.h): helper.py:37-137 for any tile set, on every configuration -----------------
+// (the workspace: head_plan -- the kernel keeps everything in registers and its lane group's LDS stage)
+// The rules read the tile bytes alone, so what makes a configuration valid here is only what the kernel takes: a problem and a
+// representation the library knows and a map within the largest sides validate_config lets any of them have -- a superset of the
+// configurations a handle can be created for (pcgrl_tile_local itself needs a bound handle).
+size_t pcgrl_tile_local_bytes(const pcgrl_config* c, int32_t count) {
+    if (!c || count < 1 || c->prob < 0 || c->prob > 5 || c->rep < 0 || c->rep > 5) return 0;
+    if (c->width < 1 || c->width > PCGRL_MAX_DIM_WIDE || c->height < 1 || c->height > PCGRL_MAX_DIM_WIDE) return 0;
+    return head_plan(c, count).total;
+}
+int pcgrl_tile_local(pcgrl_env* h, const pcgrl_tile_local_desc* d, void* work, size_t work_bytes, void* stream) {
+    const bool group = d && (d->grouping_out || d->group_map_out);
+    const bool ptrs = d && d->maps && (d->counts_out || d->floor_dist_out || d->floor_map_out || group || d->changes_out) &&
+                      !(group && (d->noffsets < 0 || d->noffsets > PCGRL_MAX_OFFSETS));
+    if (int rc = readout_check(h, ptrs, d ? d->count : 0, 1, work, work_bytes, h && d ? pcgrl_tile_local_bytes(&h->cfg, d->count) : 0)) return rc;
+    DeviceGuard guard(h->device);
+    return launch_tile_local(h, *d, (hipStream_t)stream);
 }
 
 }  // extern "C"

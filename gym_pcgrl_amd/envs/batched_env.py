@@ -141,6 +141,17 @@ class Connectivity:
         self.regions, self.longest, self.labels, self.dist, self.reach, self.source = regions, longest, labels, dist, reach, source
 
 
+class TileStats:
+    """What BatchedPcgrlEnv.tile_stats() returns, all on the device, None where not asked for: `counts` int32 [M, 32] (the cells that
+    hold tile t), `floor_dist` int32 [M] (get_floor_dist), `floor_map` int16 [M, H, W] (_calc_dist_floor of every cell), `grouping`
+    int32 [M] (get_type_grouping), `group_map` int8 [M, H, W] (_calc_group_value of every cell), `changes` int32 [M, 2]
+    (get_changes horizontal, vertical)."""
+    __slots__ = ("counts", "floor_dist", "floor_map", "grouping", "group_map", "changes")
+
+    def __init__(self, counts, floor_dist, floor_map, grouping, group_map, changes):
+        self.counts, self.floor_dist, self.floor_map, self.grouping, self.group_map, self.changes = counts, floor_dist, floor_map, grouping, group_map, changes
+
+
 def expand_changes(flat, cells, first, n, ntiles):
     """The expansion rule of changes(): entries `first` .. `first + n - 1` in the order (m, k, t) -- entry (m * K + k) * T + t is level m
     with cell cells[m, k] set to tile t -- of `flat` uint8 [M, H * W] and `cells` int64 [M, K] (torch tensors on one device, the CPU
@@ -989,6 +1000,52 @@ class BatchedPcgrlEnv:
         d = _lib.TileGraphDesc(ptr(m), M, pass_set, src if kind == "tiles" else 0, reach_set, ptr(cells), ptr(out.regions), ptr(out.longest),
                                ptr(out.labels), ptr(out.dist), ptr(out.reach), ptr(out.source))
         _lib.check(self._lib.pcgrl_tile_graph(self._handle, C.byref(d), *work, self._stream()), "pcgrl_tile_graph")
+        return out
+
+    # ---- the local half of helper.py for any tile set: floor distance, grouping, changes, tile counts (pcgrl_tile_local)
+    def tile_stats(self, maps=None, counts=False, floor=None, floor_from=None, floor_map=False, group=None, offsets=(), group_min=0, group_max=None,
+                   group_map=False, changes=False):
+        """gym_pcgrl/envs/helper.py's local helpers (helper.py:37-137) on the device for `maps` -- array-like uint8 [M, H, W] as for
+        evaluate(), of any tile values 0..31 whatever this environment's problem; None: this environment's current levels (after a
+        reset(); the handle's own map buffer is read in place).  Tiles are ints or this problem's tile names, one or a list.
+        Returns a TileStats (counts, floor_dist, floor_map, grouping, group_map, changes), None where not asked for:
+        `counts` (counts=True) the cells of every tile 0..31; `floor_dist` (`floor_from` and `floor`) get_floor_dist(map, floor_from,
+        floor); `floor_map` (floor_map=True, with `floor`) _calc_dist_floor of every cell; `grouping` (`group`, with `offsets` = relLocs,
+        (dx, dy) each, at most 16, and group_min .. group_max, by default 0 .. len(offsets)) get_type_grouping; `group_map`
+        (group_map=True, with `group`) _calc_group_value of every cell; `changes` (changes=True) get_changes horizontal, vertical.
+        The reference only tests `in types`: a tile set is the reference exactly.
+        A pure function like evaluate(): episodes, random streams and pending asynchronous searches are not touched, a byte >= 32 is
+        in no set and reported by check_status(), nothing is waited for; the workspace is evaluate()'s (the same one-stream rule).
+        There is a form for every configuration: smb and maps beyond 64 x 64 included."""
+        from ..helper import offsets_arg, tile_set
+        torch = self._torch
+        names = self._prob.get_tile_types()
+        if floor_from is not None and floor is None:
+            raise ValueError("tile_stats(): floor_from needs floor: the distance is measured to the floor tiles")
+        if floor_map and floor is None:
+            raise ValueError("tile_stats(): floor_map needs floor")
+        if group_map and group is None:
+            raise ValueError("tile_stats(): group_map needs group")
+        want_fd, want_gr = floor_from is not None, group is not None
+        if not (counts or want_fd or floor_map or want_gr or group_map or changes):
+            raise ValueError("tile_stats(): nothing was asked for")
+        from_set, floor_set, group_set = tile_set(floor_from, names, "floor_from"), tile_set(floor, names, "floor"), tile_set(group, names, "group")
+        offs = offsets_arg(offsets) if want_gr else []
+        group_max = len(offs) if group_max is None else int(group_max)
+        m, M, _, work = self._readout("tile_stats", "reads levels", "pcgrl_tile_local_bytes", lambda w, h: (
+            "tile_stats(): the library does not take this configuration (problem %r, maps of %d rows x %d columns)" % (self._prob.name, h, w)), maps, None, None)
+        w, h = self._alloc_dims
+        new = lambda want, shape, dtype: torch.empty(shape, dtype=dtype, device=self.device) if want else None
+        out = TileStats(new(counts, (M, 32), torch.int32), new(want_fd, (M,), torch.int32), new(floor_map, (M, h, w), torch.int16),
+                        new(want_gr, (M,), torch.int32), new(group_map, (M, h, w), torch.int8), new(changes, (M, 2), torch.int32))
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        clip = lambda v: max(-2 ** 31, min(2 ** 31 - 1, int(v)))
+        d = _lib.TileLocalDesc(ptr(m), M, from_set, floor_set, group_set, clip(group_min), clip(group_max), len(offs))
+        for k, (dx, dy) in enumerate(offs):
+            d.offsets[k][0], d.offsets[k][1] = dx, dy
+        d.counts_out, d.floor_dist_out, d.floor_map_out = ptr(out.counts), ptr(out.floor_dist), ptr(out.floor_map)
+        d.grouping_out, d.group_map_out, d.changes_out = ptr(out.grouping), ptr(out.group_map), ptr(out.changes)
+        _lib.check(self._lib.pcgrl_tile_local(self._handle, C.byref(d), *work, self._stream()), "pcgrl_tile_local")
         return out
 
     # ---- every one-cell change of a level: rows, reward and episode end (pcgrl_get_changes)

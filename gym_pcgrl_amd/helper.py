@@ -20,8 +20,22 @@ exactly; for several, calc_num_regions, run_dikjstra and calc_num_reachable_tile
 calc_longest_path and the label numbering are the merged-tile ones.  calc_num_reachable_tile takes the first cell of `start_value` in
 row-major order and counts nothing when there is none (the reference raises IndexError).
 
-The device functions are BatchedPcgrlEnv.connectivity() (C ABI: pcgrl_tile_graph) on a private one-environment handle per (device,
-H, W), made once, cached and closed at exit; maps up to 64 x 64.  Nothing is waited for on the torch route.
+The local half of the file (helper.py:37-137), behind smb's dist-floor, disjoint-tubes and noise and ddave's dist-floor:
+
+    d = helper.get_floor_dist(maps, [2], [1, 3, 4, 6])           # int32 [M]      helper.py:56-62
+    g = helper.get_type_grouping(maps, [6], [(-1, 0), (1, 0)], 1, 1)      # int32 [M]      helper.py:100-108
+    c = helper.get_changes(maps, vertical=False)                 # int32 [M]      helper.py:120-137
+    fmap = helper.floor_dist_map(maps, [1, 3, 4, 6])             # int16 [M, H, W]: _calc_dist_floor of every cell (helper.py:37-43)
+    gmap = helper.group_value_map(maps, [6], [(-1, 0), (1, 0)])  # int8 [M, H, W]: _calc_group_value of every cell (helper.py:77-85)
+    n = helper.count_tiles(maps)                                 # int32 [M, 32]: the cells of every tile value
+
+There is no set rule here: the reference only tests `in types`, so these are the reference exactly, for any list of tiles (at most
+16 relLocs, each within -128..127).  get_tile_locations is not provided: on stacks its use is to feed the other helpers, which take
+`maps` here, and torch.nonzero(maps == t) gives the positions.
+
+The device functions are BatchedPcgrlEnv.connectivity() (C ABI: pcgrl_tile_graph) and BatchedPcgrlEnv.tile_stats() (pcgrl_tile_local)
+on a private one-environment handle per (device, H, W), made once, cached and closed at exit.  The graph helpers take maps up to
+64 x 64; the local ones take every size a handle exists for.  Nothing is waited for on the torch route.
 """
 import atexit
 
@@ -79,6 +93,25 @@ def source_arg(source, width, height, names=None):
     raise ValueError("source: None, a cell, cells [M], (x, y), a tile name or a list of tiles -- got %r" % (source,))
 
 
+def offsets_arg(offsets):
+    """get_type_grouping's relLocs -- a sequence (or an array [K, 2]) of at most 16 pairs (dx, dy) of ints in -128..127 -- as a list
+    of int pairs."""
+    try:
+        offs = [tuple(o) for o in offsets]
+    except TypeError:
+        raise ValueError("offsets: a sequence of (dx, dy) pairs, got %r" % (offsets,))
+    if len(offs) > 16:
+        raise ValueError("offsets: at most 16 relative positions, got %d" % len(offs))
+    out = []
+    for o in offs:
+        if len(o) != 2 or not all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in o):
+            raise ValueError("offsets: each entry is a pair (dx, dy) of ints, got %r" % (o,))
+        if not all(-128 <= int(v) <= 127 for v in o):
+            raise ValueError("offsets: (dx, dy) = %r outside -128..127" % (o,))
+        out.append((int(o[0]), int(o[1])))
+    return out
+
+
 def _close_all():
     for env in _HANDLES.values():
         env.close()
@@ -87,7 +120,7 @@ def _close_all():
 
 def _handle(device, height, width):
     """The private handle for levels of this size on this device: binary, wide, one environment -- only its device, size and lane-group
-    form matter to pcgrl_tile_graph."""
+    form matter to pcgrl_tile_graph, only its device and size to pcgrl_tile_local (which it serves beyond 64 x 64 too)."""
     import torch
     from .envs import BatchedPcgrlEnv
     dev = torch.device("cuda:0" if device is None else device)
@@ -114,6 +147,61 @@ def _connectivity(maps, **kw):
     device = maps.device if (not on_host and maps.is_cuda) else None
     out = _handle(device, shape[1], shape[2]).connectivity(maps, **kw)
     return out, (lambda t: t.cpu().numpy()) if on_host else (lambda t: t)
+
+
+def _tile_stats(maps, **kw):
+    """tile_stats() of the cached handle for `maps`; -> (the TileStats, the conversion of a result for this kind of input)."""
+    import torch
+    shape = tuple(maps.shape) if hasattr(maps, "shape") else np.asarray(maps).shape
+    if len(shape) != 3:
+        raise ValueError("helper: maps must be [M, H, W], got shape %s" % (shape,))
+    on_host = not torch.is_tensor(maps)
+    device = maps.device if (not on_host and maps.is_cuda) else None
+    out = _handle(device, shape[1], shape[2]).tile_stats(maps, **kw)
+    return out, (lambda t: t.cpu().numpy()) if on_host else (lambda t: t)
+
+
+def get_floor_dist(maps, fromTypes, floorTypes):
+    """helper.py:56-62 for every level: the sum over the cells of `fromTypes` of their distance to the nearest `floorTypes` tile at or
+    below (0: standing on it, -1: the cell is itself a floor tile, H - 1: none below): int32 [M]."""
+    s, conv = _tile_stats(maps, floor_from=_listed(fromTypes), floor=_listed(floorTypes))
+    return conv(s.floor_dist)
+
+
+def floor_dist_map(maps, floorTypes):
+    """_calc_dist_floor (helper.py:37-43) of every cell, which get_floor_dist sums and throws away: int16 [M, H, W]."""
+    s, conv = _tile_stats(maps, floor=_listed(floorTypes), floor_map=True)
+    return conv(s.floor_map)
+
+
+def get_type_grouping(maps, types, relLocs, min, max):
+    """helper.py:100-108 for every level: the cells of `types` with min <= (the relLocs (dx, dy) whose cell is inside the map and holds
+    one of `types`) <= max: int32 [M].  At most 16 relLocs, each within -128..127."""
+    s, conv = _tile_stats(maps, group=_listed(types), offsets=relLocs, group_min=min, group_max=max)
+    return conv(s.grouping)
+
+
+def group_value_map(maps, types, relLocs):
+    """_calc_group_value (helper.py:77-85) of every cell, whatever its own tile: int8 [M, H, W]."""
+    s, conv = _tile_stats(maps, group=_listed(types), offsets=relLocs, group_map=True)
+    return conv(s.group_map)
+
+
+def get_changes(maps, vertical=False):
+    """helper.py:120-137 for every level: the horizontally (vertical=True: vertically) adjacent pairs of unequal tiles: int32 [M]."""
+    s, conv = _tile_stats(maps, changes=True)
+    return conv(s.changes[:, 1 if vertical else 0])
+
+
+def count_tiles(maps):
+    """The cells that hold tile t, for t = 0..31 (what the reference reads off get_tile_locations): int32 [M, 32]."""
+    s, conv = _tile_stats(maps, counts=True)
+    return conv(s.counts)
+
+
+def _listed(tiles):
+    """A tile argument for tile_stats(), where None means `not asked for`: an empty reference list stays an empty set."""
+    return [] if tiles is None else tiles
 
 
 def calc_num_regions(maps, passable_values):

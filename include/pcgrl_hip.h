@@ -24,6 +24,8 @@
  *                                    nearest-enemy (zelda_prob.py:91-110) measure, from the run_dikjstra maps (helper.py:222-237)
  *   pcgrl_tile_graph                 helper.py:170-296 for any tile set: calc_num_regions with its color_map, calc_longest_path,
  *                                    run_dikjstra's map, calc_num_reachable_tile -- what a custom Problem builds its get_stats from
+ *   pcgrl_tile_local                 helper.py:37-137 for any tile set: get_floor_dist, get_type_grouping, get_changes with their
+ *                                    per-cell maps, on every map size and problem
  *
  * Conventions: plain pointers and sizes only; every function returns 0 on success or a negative
  * PCGRL_E* code (no exceptions cross the ABI); all device buffers are OWNED BY THE CALLER (hipMalloc,
@@ -61,6 +63,8 @@ extern "C" {
  *     Still 15: + pcgrl_get_changes_bytes / pcgrl_get_changes -- additive in the same way; detected by the symbol pcgrl_get_changes.
  *     Still 15: + pcgrl_tile_graph_desc / pcgrl_tile_graph_bytes / pcgrl_tile_graph -- additive in the same way (one struct, two entry
  *     points); detected by the symbol pcgrl_tile_graph.
+ *     Still 15: + pcgrl_tile_local_desc / pcgrl_tile_local_bytes / pcgrl_tile_local -- additive in the same way (one struct, two entry
+ *     points); detected by the symbol pcgrl_tile_local.
  *     The developer switches pcgrl_tuning grew at their end (changes_grid, changes_chunk): fill them with pcgrl_tuning_defaults. */
 #define PCGRL_ABI_VERSION 15
 #define PCGRL_OK 0
@@ -521,6 +525,54 @@ typedef struct pcgrl_tile_graph_desc {
 } pcgrl_tile_graph_desc;
 size_t pcgrl_tile_graph_bytes(const pcgrl_config* cfg, int32_t count);
 int    pcgrl_tile_graph(pcgrl_env* env, const pcgrl_tile_graph_desc* desc, void* work, size_t work_bytes, void* stream);
+/* ---- the local half of helper.py for any tile set (helper.py:37-137): get_floor_dist (:56-62), get_type_grouping (:100-108) and
+ * get_changes (:120-137) -- the helpers behind smb's dist-floor, disjoint-tubes and noise and ddave's dist-floor -- with the per-cell
+ * values the reference computes and throws away, _calc_dist_floor (:37-43) and _calc_group_value (:77-85), and a count of every tile,
+ * for `count` levels of any tiles 0..31.  These rules read the tile bytes alone: there is a form for EVERY configuration a handle can
+ * be created for -- smb's 114 x 14, maps beyond 64 x 64 -- whatever problem the handle has.  The reference only tests `in types`, so a
+ * tile SET is the reference exactly (no set rule as in pcgrl_tile_graph).
+ *   maps          DEVICE u8 [count,H,W], read only.  A byte >= 32 is in no set and in no counts column, and reported (status bit 2);
+ *                 changes compares it as it is.
+ *   from_tiles, floor_tiles   get_floor_dist's fromTypes / floorTypes, bit t = tile t.
+ *   group_tiles, group_min, group_max, noffsets, offsets   get_type_grouping's types, min, max and relLocs: (dx, dy) each, the first
+ *                 noffsets (0 .. PCGRL_MAX_OFFSETS) count; an offset listed twice counts twice, (0, 0) counts the cell itself.
+ *   Outputs, DEVICE, each one optional: NULL = neither computed nor stored; at least one is needed.
+ *   counts_out      i32 [count,32]   the cells that hold tile t.
+ *   floor_dist_out  i32 [count]      get_floor_dist(map, from, floor): the sum of floor_map over the cells of from_tiles; can be negative.
+ *   floor_map_out   i16 [count,H,W]  _calc_dist_floor(map, x, y, floor) of EVERY cell: the smallest dy >= 0 with y + dy < H and
+ *                                    map[y+dy][x] in floor_tiles gives dy - 1 (a floor cell itself: -1); without one H - 1, whatever y.
+ *   grouping_out    i32 [count]      get_type_grouping: the cells of group_tiles with group_min <= group_map <= group_max (min > max: 0).
+ *   group_map_out   i8  [count,H,W]  _calc_group_value of EVERY cell: the offsets whose cell is inside the map and holds a group tile.
+ *   changes_out     i32 [count,2]    get_changes(map, False), get_changes(map, True): unequal horizontally / vertically adjacent pairs
+ *                                    of raw bytes.
+ * Every element of every requested output is stored exactly once, nothing else is written.
+ * Same contract as pcgrl_tile_graph: a bound handle, no reset needed; only the device, the stream, the width and the height are taken
+ * from the handle; no episode state read or written, of the handle only the sticky status word written; asynchronous.
+ *   work          DEVICE, 256-byte aligned, at least pcgrl_tile_local_bytes(cfg, count) bytes; the call's own.
+ *   PCGRL_EINVAL: a NULL desc, maps or work, no output, count < 1, noffsets outside 0 .. PCGRL_MAX_OFFSETS when grouping_out or
+ *   group_map_out is asked for, work not 256-byte aligned or too small, or a configuration for which pcgrl_tile_local_bytes is 0.
+ *   PCGRL_ESTATE before pcgrl_bind.  A refused call writes nothing.
+ * pcgrl_tile_local_bytes: from the configuration alone.  >= 256 for every configuration a handle can be created for (with
+ *   num_envs = 1), smb and maps beyond 64 x 64 included; 0 for count < 1, a NULL cfg and an invalid one: here a problem or a
+ *   representation the library does not know, or a side outside 1 .. 4096 -- the rules read the tile bytes alone, the problem's own
+ *   limits do not matter to them. */
+#define PCGRL_MAX_OFFSETS 16
+typedef struct pcgrl_tile_local_desc {
+    const uint8_t* maps;
+    int32_t count;
+    uint32_t from_tiles, floor_tiles;
+    uint32_t group_tiles;
+    int32_t group_min, group_max, noffsets;
+    int8_t offsets[PCGRL_MAX_OFFSETS][2];
+    int32_t* counts_out;
+    int32_t* floor_dist_out;
+    int16_t* floor_map_out;
+    int32_t* grouping_out;
+    int8_t* group_map_out;
+    int32_t* changes_out;
+} pcgrl_tile_local_desc;
+size_t pcgrl_tile_local_bytes(const pcgrl_config* cfg, int32_t count);
+int    pcgrl_tile_local(pcgrl_env* env, const pcgrl_tile_local_desc* desc, void* work, size_t work_bytes, void* stream);
 /* ActionMap.step for the wide representation (wrappers.py:139-154): flat DEVICE i32 [N] index into
  * (H, W, tiles) -> xyv DEVICE i32 [N,3] = (x, y, tile), the action pcgrl_step takes. */
 int pcgrl_action_map(pcgrl_env* env, const int32_t* flat, int32_t* xyv, void* stream);

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Levels/s of the level read-outs of BatchedPcgrlEnv -- evaluate() (pcgrl_get_stats), solve() (pcgrl_get_solution), playthrough()
 (pcgrl_get_playthrough), playthrough_smb() (pcgrl_get_smb_play), paths() (pcgrl_get_paths), changes() (pcgrl_get_changes) and
-connectivity() (pcgrl_tile_graph) -- each next to the route it is compared with, on the GPU box.  One method: wall clock around the call with a device synchronisation, after a warm-up of each call (the handle,
+connectivity() (pcgrl_tile_graph), tile_stats() (pcgrl_tile_local) -- each next to the route it is compared with, on the GPU box.  One method: wall clock around the call with a device synchronisation, after a warm-up of each call (the handle,
 the workspace, the kernels' code objects, the allocator's blocks); a call is a few ms and the box is shared, so the calls of a case run in
 ONE process on one handle, alternating, `rounds` rounds: minimum, median and maximum of each.  Every case runs in a child process of its
 own under a time limit, so that a hang ends there; a child that fails ends the session.  One JSON line at the end.
@@ -13,6 +13,7 @@ own under a time limit, so that a hang ends there; a child that fails ends the s
     python tools/readout_bench.py paths [M14 [M11x16 [M64]]]         (defaults: 65536 65536 4096)
     python tools/readout_bench.py changes [Mbinary [Mzelda [Msokoban [M16x40]]]]   (defaults: 1024 each)
     python tools/readout_bench.py tile_graph [M14 [M64]]             (defaults: 65536 8192)
+    python tools/readout_bench.py tile_local [M14 [M64 [Msmb]]]      (defaults: 65536 8192 16384)
 
 evaluate: evaluate() next to the route there was before it -- a handle of M environments: reset(); set_maps(maps); stats -- three runs
 of each; the handle route is timed with and without building the handle (allocation + seeding + reset), which that route needs once per
@@ -26,7 +27,10 @@ same entries (built once, outside the clock: the yardstick gets its input for no
 binary 16 x 40 (64-bit row masks on sixteen rows: the shape at which changes() takes a wavefront a level where evaluate() takes four), 30
 rounds; the reported "levels" are entries.  tile_graph: connectivity(passable=["empty"]) with the scalars only, with + dist (from the
 first empty cell, and the reachable count) and with + labels next to evaluate() on the same binary stack, 14 x 14 and 64 x 64, 30 rounds;
-the scalars must be evaluate()'s rows.  The statistics rows of the calls of a case must agree.
+the scalars must be evaluate()'s rows.  tile_local: tile_stats() with the four scalars (floor distance, grouping, the two changes;
+from {2}, floor {1, 3, 4, 6}, group {6} with its left and right neighbours in 1..1) and with + both per-cell maps, each next to a plain
+torch restatement of the same quantities (torch_local: what a user writes today), on binary 14 x 14, binary 64 x 64 (both also next to
+evaluate() for scale) and smb 14 x 114, 30 rounds; the results must be equal.  The statistics rows of the calls of a case must agree.
 """
 import argparse
 import json
@@ -236,6 +240,54 @@ def tile_graph_child(h, w, m):
     return out
 
 
+TL_FROM, TL_FLOOR, TL_GROUP, TL_OFFSETS = [2], [1, 3, 4, 6], [6], [(-1, 0), (1, 0)]      # the query of the tile_local leg; the range is 1..1
+
+
+def torch_local(maps, with_maps):
+    """What a user writes today for get_floor_dist, get_type_grouping and the two get_changes on a stack: plain torch.
+    -> (floor_dist, grouping, changes [M, 2], floor_map or None, group_map or None)"""
+    import torch
+    M, H, W = maps.shape
+    dev = maps.device
+    member = lambda tiles: torch.isin(maps, torch.tensor(tiles, dtype=torch.uint8, device=dev))
+    rows = torch.arange(H, dtype=torch.int32, device=dev).view(1, H, 1)
+    none = torch.tensor(1 << 20, dtype=torch.int32, device=dev)
+    near = torch.where(member(TL_FLOOR), rows, none).flip(1).cummin(1).values.flip(1)          # the nearest floor row at or below
+    fmap = torch.where(near < none, near - rows - 1, torch.tensor(H - 1, dtype=torch.int32, device=dev))
+    floor_dist = (fmap * member(TL_FROM)).sum((1, 2), dtype=torch.int32)
+    g = member(TL_GROUP)
+    gmap = torch.zeros((M, H, W), dtype=torch.int8, device=dev)
+    gmap[:, :, 1:] += g[:, :, :-1]
+    gmap[:, :, :-1] += g[:, :, 1:]
+    grouping = (g & (gmap == 1)).sum((1, 2), dtype=torch.int32)
+    changes = torch.stack([(maps[:, :, 1:] != maps[:, :, :-1]).sum((1, 2), dtype=torch.int32), (maps[:, 1:] != maps[:, :-1]).sum((1, 2), dtype=torch.int32)], 1)
+    return floor_dist, grouping, changes, fmap.to(torch.int16) if with_maps else None, gmap if with_maps else None
+
+
+def tile_local_child(prob, h, w, m):
+    import torch
+    out = {"prob": prob, "h": h, "w": w, "M": m}
+    maps = device_maps(levels(prob, m, h, w))
+    env = make_env(prob, (h, w))
+    q = dict(floor_from=TL_FROM, floor=TL_FLOOR, group=TL_GROUP, offsets=TL_OFFSETS, group_min=1, group_max=1, changes=True)
+    calls = {"scalars": lambda: env.tile_stats(maps, **q), "torch scalars": lambda: torch_local(maps, False),
+             "+maps": lambda: env.tile_stats(maps, floor_map=True, group_map=True, **q), "torch +maps": lambda: torch_local(maps, True)}
+    if prob == "binary":
+        calls["evaluate"] = lambda: env.evaluate(maps)          # (for scale)
+    out["s"], last = alternate(calls, 30)
+    for k, with_maps in (("scalars", False), ("+maps", True)):
+        s, t = last[k], last["torch " + k]
+        assert torch.equal(s.floor_dist, t[0]) and torch.equal(s.grouping, t[1]) and torch.equal(s.changes, t[2]), "tile_stats() and the torch restatement disagree"
+        if with_maps:
+            assert torch.equal(s.floor_map, t[3]) and torch.equal(s.group_map, t[4]), "tile_stats() and the torch restatement disagree on the maps"
+    s = last["scalars"]
+    out["checksum"] = {k: int((r.floor_dist.to(torch.int64) + r.grouping + r.changes.sum(1)).sum().item()) for k, r in last.items() if k in ("scalars", "+maps")}
+    out["bytes_maps"] = {k: (int(maps.numel() * 3) if "+maps" in k else 0) for k in calls}
+    out["floor_dist"], out["grouping"] = int(s.floor_dist.to(torch.int64).sum().item()), int(s.grouping.to(torch.int64).sum().item())
+    assert env.check_status() == 0
+    return out
+
+
 # ---- the subcommands: arguments -> cases (label, child arguments); a note behind a call's report line; the results -> the JSON
 def moves_note(r, k):
     if k == "evaluate":
@@ -280,6 +332,8 @@ def arguments(p, sub):
         p.add_argument("ms", nargs="*", type=int, default=[], metavar="M", help="levels of binary 14 x 14, zelda 7 x 11, sokoban 5 x 5, binary 16 x 40 (1024 each)")
     elif sub == "paths":
         p.add_argument("ms", nargs="*", type=int, default=[], metavar="M", help="levels of binary 14 x 14, zelda 11 x 16, binary 64 x 64 (65536 65536 4096)")
+    elif sub == "tile_local":
+        p.add_argument("ms", nargs="*", type=int, default=[], metavar="M", help="levels of binary 14 x 14, binary 64 x 64 and smb 14 x 114 (65536 8192 16384)")
     elif sub == "tile_graph":
         p.add_argument("ms", nargs="*", type=int, default=[], metavar="M", help="levels of binary 14 x 14 and binary 64 x 64 (65536 8192)")
     else:
@@ -305,6 +359,10 @@ SPECS = {
     "changes": dict(child=changes_child, final=paths_final, note=lambda r, k: "   %d levels, %d no-op entries" % (r["levels"], r["noop"]),
                     cases=lambda a: [("%s %dx%d" % (prob, h, w), (prob, h, w, m))
                                      for (prob, h, w), m in zip((("binary", 14, 14), ("zelda", 7, 11), ("sokoban", 5, 5), ("binary", 16, 40)), a.ms + [1024, 1024, 1024, 1024][len(a.ms):])]),
+    "tile_local": dict(child=tile_local_child, final=paths_final,
+                       note=lambda r, k: "   floor-dist %d, grouping %d, %.1f MB of maps" % (r["floor_dist"], r["grouping"], r["bytes_maps"][k] / 1e6),
+                       cases=lambda a: [("%s %dx%d" % (prob, h, w), (prob, h, w, m))
+                                        for (prob, h, w), m in zip((("binary", 14, 14), ("binary", 64, 64), ("smb", 14, 114)), a.ms + [65536, 8192, 16384][len(a.ms):])]),
     "tile_graph": dict(child=tile_graph_child, final=paths_final,
                        note=lambda r, k: "   %d regions, farthest %d, %.1f MB of maps" % (r["regions"], r["farthest"], r["bytes_maps"][k] / 1e6),
                        cases=lambda a: [("binary %dx%d" % (h, w), (h, w, m)) for (h, w), m in zip(((14, 14), (64, 64)), a.ms + [65536, 8192][len(a.ms):])]),
